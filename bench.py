@@ -1,7 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- scored triples/s of the link-prediction sweep (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line. --dump-outputs DIR
+also writes what the last timed step returned (C2: the count table and the metrics reduced from
+it) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+--full adds everything beside the headline figure, each after the timed region: the sweep
+kernel alone and the roofline block, the filter record, the reference's CPU baseline and the
+parity block against it, the per-rank breakdown and the sharded-vs-one-GPU parity (N > 1), and
+the other configs' per-part timings and CPU baselines.
 
 One step = one complete filtered link-prediction evaluation of the configured workload
 (default C2: FB15K-237-ZS test set, TransE d=200, norm_flag, all 17,596 test triples in both
@@ -370,6 +378,7 @@ def bench_zsl(args, world, rank, dev, dist):
     n_rows = int(len(rows))
     pad = max(int(m.sum()) for m in masks)
     host = torch.empty(world * pad, dtype=torch.int32, pin_memory=True)
+    last_ranks = [None]  # the last step's per-query ranks (--dump-outputs)
 
     def step(ev=None):
         pack = pack_weights(ex)
@@ -395,6 +404,7 @@ def bench_zsl(args, world, rank, dev, dist):
         for k in range(world):
             ids = np.nonzero(masks[k])[0]
             full[ids] = got[k * pad:k * pad + len(ids)]
+        last_ranks[0] = full
         return {"hits10": float((full <= 10).mean()), "hits5": float((full <= 5).mean()),
                 "hits1": float((full <= 1).mean()), "mrr": float((1.0 / full).mean())}
 
@@ -419,6 +429,9 @@ def bench_zsl(args, world, rank, dev, dist):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     total = int(off[-1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"ranks": last_ranks[0], "metrics": np.array(
+            [m[k] for k in ("hits10", "hits5", "hits1", "mrr")], np.float64)})
     if rank == 0:
         flops = 8.0 * d * d * n_rows  # proj1 (d -> 2d) + proj2 (2d -> d), 2 flops per MAC
         ach = flops / (kern_ms * 1e-3) / 1e12
@@ -436,7 +449,7 @@ def bench_zsl(args, world, rank, dev, dist):
                             "kernel": "k_extractor_encode<200>", "kernel_ms": kern_ms,
                             "flops_per_row": 8 * d * d, "rows_per_launch": n_rows},
                "metrics": m}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_zsl(w)
         print(json.dumps(_with_build(out)), flush=True)
     if dist:
@@ -577,6 +590,46 @@ def bench_ns(args, world, rank, dev, dist):
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if graph is not None:
+        loss = g_loss.detach().clone()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left its caller: the loss it returned, the tables it updated in place
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1), **{
+            name: x.detach() for name, x in (("ent", ent), ("rel", rel), ("ent_im", ent_im), ("rel_im", rel_im))
+            if x is not None}})
+
+    def result_head():
+        return {"metric": f"training triples/sec, {CONFIGS['ns']['workload']}",
+                "value": n_rows * args.steps * world / elapsed, "unit": "training triples/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+                "data": f"synthetic {model} tables (OpenKE init, seed 0); training triples = 272,115 synthetic "
+                        "+ the FB15K-237-ZS test triples",
+                "config": {"workload": CONFIGS["ns"]["workload"] if model == "transe" else
+                           f"{model} d=200 training step at the C2 training shape (margin loss)", "model": model,
+                           "batch": B, "neg_ent": k, "rows_per_step": n_rows,
+                           "dim": d, "margin": margin, "parallelism": f"data-parallel replicas x{world}",
+                           "step": (("mmre_ns_step_openke_pipe (fused loss kernel; row owner + SGD + loss reduction "
+                                     "+ the next batch's sampler + the updated rows' pre-pass: 2 launches)" if model == "transe"
+                                     else "mmre_ns_step_openke_gen_pipe (forward; slot records; row owner + SGD + loss "
+                                     "reduction + the next batch's sampler: 3 launches)")
+                                    if tstep is not None and tstep.pipeline else
+                                    "mmre_ns_step_openke (sampler + pre-pass, fused loss, row owner + SGD + loss "
+                                    "reduction: 3 launches)" if tstep is not None else
+                                    "sampler.sample + fused_ns_loss + backward + SGD.step (drop-in path)"),
+                           "launch": ("eager" if not graph else "hipGraph replay of the whole step" +
+                                      ("" if (not args.ns_prefetch) else ", next batch sampled on a forked stream (prefetch)"))}}
+
+    if not args.full:
+        if dist:
+            tt = torch.tensor([elapsed], dtype=torch.float64, device=_coll_dev(dist, dev))
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            elapsed = float(tt.item())
+        if rank == 0:
+            print(json.dumps(_with_build({**result_head(), "last_loss": float(loss.detach())})), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
     pipe_ms = None
     if graph is not None and tstep is not None and tstep.pipeline:
         # the pipelined step's two launches (fused loss kernel; row owner with SGD, the loss, the
@@ -668,26 +721,7 @@ def bench_ns(args, world, rank, dev, dist):
         pmc_cfg = "ns" if model == "transe" else f"ns_{model}"  # profiles/pmc_<pmc_cfg>.json
         traffic, tsrc, tper = (pmc_step_traffic(pmc_cfg, step_kernels) if (world == 1 and d == 200 and k == 25)
                                else (None, None, None))
-        out = {"metric": f"training triples/sec, {CONFIGS['ns']['workload']}",
-               "value": n_rows * args.steps * world / elapsed, "unit": "training triples/s", "n_gpus": world,
-               "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-               "data": f"synthetic {model} tables (OpenKE init, seed 0); training triples = 272,115 synthetic "
-                       "+ the FB15K-237-ZS test triples",
-               "config": {"workload": CONFIGS["ns"]["workload"] if model == "transe" else
-                          f"{model} d=200 training step at the C2 training shape (margin loss)", "model": model,
-                          "batch": B, "neg_ent": k, "rows_per_step": n_rows,
-                          "dim": d, "margin": margin, "parallelism": f"data-parallel replicas x{world}",
-                          "step": (("mmre_ns_step_openke_pipe (fused loss kernel; row owner + SGD + loss reduction "
-                                    "+ the next batch's sampler + the updated rows' pre-pass: 2 launches)" if model == "transe"
-                                    else "mmre_ns_step_openke_gen_pipe (forward; slot records; row owner + SGD + loss "
-                                    "reduction + the next batch's sampler: 3 launches)")
-                                   if tstep is not None and tstep.pipeline else
-                                   "mmre_ns_step_openke (sampler + pre-pass, fused loss, row owner + SGD + loss "
-                                   "reduction: 3 launches)" if tstep is not None else
-                                   "sampler.sample + fused_ns_loss + backward + SGD.step (drop-in path)"),
-                          "launch": ("eager" if not graph else "hipGraph replay of the whole step" +
-                                     ("" if (not args.ns_prefetch) else ", next batch sampled on a forked stream (prefetch)"))},
+        out = {**result_head(),
                "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                             "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
                             "traffic_unit": "HBM bytes per step's loss + gradient kernels (rocprofv3 PMC, "
@@ -840,18 +874,23 @@ def bench_gan(args, world, rank, dev, dist):
         out = one(batches[args.warmup + i])
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # the same iteration launched eagerly (no graph), for the launch-overhead comparison
-    torch.cuda.synchronize()
-    te = time.perf_counter()
-    k_e = max(3, args.steps // 4)
-    for i in range(k_e):
-        bt = batches[i]
-        noise = torch.randn(n, 15, device=dev)
-        alpha = torch.rand(n, 1, device=dev)
-        step.d_step(bt["rel"], bt["q_head"], bt["q_tail"], bt["f_head"], bt["f_tail"], bt["labels"], noise, alpha)
-        step.g_step(bt["rel"], bt["q_head"], bt["q_tail"], bt["f_head"], bt["f_tail"], bt["labels"], noise)
-    torch.cuda.synchronize()
-    eager_ms = (time.perf_counter() - te) / k_e * 1e3
+    last_losses = [float(x) for x in out.cpu()]  # the last timed iteration's return value
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"losses_G": np.asarray(last_losses, np.float64)})
+    eager_ms = None
+    if args.full:
+        # the same iteration launched eagerly (no graph), for the launch-overhead comparison
+        torch.cuda.synchronize()
+        te = time.perf_counter()
+        k_e = max(3, args.steps // 4)
+        for i in range(k_e):
+            bt = batches[i]
+            noise = torch.randn(n, 15, device=dev)
+            alpha = torch.rand(n, 1, device=dev)
+            step.d_step(bt["rel"], bt["q_head"], bt["q_tail"], bt["f_head"], bt["f_tail"], bt["labels"], noise, alpha)
+            step.g_step(bt["rel"], bt["q_head"], bt["q_tail"], bt["f_head"], bt["f_tail"], bt["labels"], noise)
+        torch.cuda.synchronize()
+        eager_ms = (time.perf_counter() - te) / k_e * 1e3
     res = {"metric": f"GAN iterations/sec, {CONFIGS['gan']['workload']}", "value": args.steps / elapsed,
            "unit": "iterations/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -860,8 +899,10 @@ def bench_gan(args, world, rank, dev, dist):
                    "generator / Discriminator (weights_init), random relation CLS rows and batches",
            "config": {"workload": CONFIGS["gan"]["workload"], "rows": n, "dim": d, "centroids": n_lab,
                       "parallelism": "single GPU, hipGraph replay per D / G step"},
-           "eager_ms_per_step": eager_ms, "last_losses_G": [float(x) for x in out.cpu()]}
-    if not args.no_cpu_baseline:
+           "last_losses_G": last_losses}
+    if args.full:
+        res["eager_ms_per_step"] = eager_ms
+    if args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_gan(w, centroids.cpu(), n_lab)
     print(json.dumps(_with_build(res)), flush=True)
 
@@ -1001,6 +1042,27 @@ def bench_m3ae(args, world, rank, dev, dist):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=_coll_dev(dist, dev))
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"relation_embeddings": host.numpy()})  # the last step's (N, 200) rows
+
+    def result_head():
+        return {"metric": f"relation embeddings generated/sec, {CONFIGS['m3ae']['workload']}",
+                "value": R * S * args.steps / elapsed, "unit": "relation embeddings/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+                "data": "real FB15K-237-ZS relation-description lengths (synthetic token ids: no BERT vocabulary "
+                        "offline), random-init M3AE-small encoder and generator"}
+
+    if not args.full:
+        if rank == 0:
+            out = result_head()
+            out["config"] = {"workload": CONFIGS["m3ae"]["workload"], "descriptions": R, "rows": R * S,
+                             "tokens_per_row": int(w["tok"].shape[1]),
+                             "parallelism": f"descriptions round-robin x{world}, no collective"}
+            print(json.dumps(_with_build(out)), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
     # roofline: the dominant kernel, fc1 (+GELU) of a block over the packed rows, timed alone
     plan = torch.empty(int(_lib_m3ae_plan_size(n)), dtype=torch.int32, device=dev)
     call("mmre_m3ae_plan", ptr(tok), ptr(msk), n, int(tok.shape[1]), 1, w["vocab"], ptr(plan), stream_ptr(dev))
@@ -1025,12 +1087,7 @@ def bench_m3ae(args, world, rank, dev, dist):
     flops = 2.0 * packed * d * hid
     ach = flops / (k_ms * 1e-3) / 1e12
     if rank == 0:
-        out = {"metric": f"relation embeddings generated/sec, {CONFIGS['m3ae']['workload']}",
-               "value": R * S * args.steps / elapsed, "unit": "relation embeddings/s", "n_gpus": world,
-               "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-               "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-               "data": "real FB15K-237-ZS relation-description lengths (synthetic token ids: no BERT vocabulary "
-                       "offline), random-init M3AE-small encoder and generator",
+        out = {**result_head(),
                "config": {"workload": CONFIGS["m3ae"]["workload"], "descriptions": R, "rows": R * S,
                           "tokens_per_row": int(w["tok"].shape[1]), "unique_descriptions_rank0": n_unique,
                           "packed_rows_rank0": packed,
@@ -1094,6 +1151,81 @@ def rank_breakdown(ev, dist, dev, sweep_ms, n_local, entity_sharded, reps=20, fi
         summ[k + "_min"] = float(allv[:, names.index(k)].min())
         summ[k + "_max"] = float(allv[:, names.index(k)].max())
     return per, summ
+
+
+def link_result(args, cfg, w, world, dist, ev, elapsed, metrics, graphed, roofline=None):
+    """The link configs' result line from the timed steps alone: the headline figure, what was
+    measured and how, and the last timed evaluation's metrics. --full adds the roofline block
+    (its kernel timings take runs of their own) and the parity block's place."""
+    model, dim, E, n = cfg["model"], cfg["dim"], w["n_ent"], len(w["test_h"])
+    tc = bool(args.type_constrain)
+    data = {"c1": "synthetic TransE tables trained on the FB15K-237-ZS test triples",
+            "c2": "synthetic TransE tables trained on the FB15K-237-ZS test triples",
+            "c5": "synthetic 1M-entity DistMult table; relation table = the zsl_module generator (random-init "
+                  "UnifiedModel SN layers + LayerNormalization, HIP) over synthetic 384-d text CLS rows + noise; "
+                  "4,096 random test triples (= the filter set)"}.get(args.config, f"synthetic {model} tables")
+    if "tables" in w:
+        data += (" -- structured tables (mmre.workloads.structured_tables: each test triple pulls its tail "
+                 "toward the model's image of its head, so truths rank near the top)")
+    elif "trained" not in w:
+        data += " (OpenKE init, seed 0)"
+    if args.config != "c5":
+        data += (f" ({args.train_steps} steps of this build's HIP trainer: bit-exact OpenKE sampler + fused margin"
+                 f" loss, SGD 1.0, margin 5, neg 25)" if "trained" in w else "") + \
+            f" over the real {w['dataset']} test triples; filter set = all test triples + 272,115 synthetic train"
+    if tc:
+        data += ("; type_constrain.txt built from the filter set by the reference n-n.py's rule (each "
+                 "relation's known heads / tails)")
+    coll = "RCCL" if not dist or dist.get_backend() == "nccl" else "gloo rehearsal (every rank on cuda:0)"
+    metric = METRIC if args.config == "c2" else f"scored triples/sec, {cfg['workload']}"
+    if tc:
+        metric += " (type-constrained: Tester.run_link_prediction(type_constrain=True))"
+    grp = "filter_tc" if tc else "filter"
+    out = {"metric": metric,
+           "value": 2 * n * E * args.steps / elapsed, "unit": "scored triples/s", "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+           "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": data,
+           "config": {"workload": cfg["workload"], "n_entities": E, "dim": dim, "n_sweeps": 2 * n,
+                      "parallelism": (f"entity-sharded x{world} (1/N of the entity tiles per rank), {coll} all-reduce "
+                                      f"of the count table" if args.shard == "entity" else
+                                      f"query-sharded x{world} (relation-major LPT with relation splits"
+                                      f"{', packed by calibrated per-query cost' if getattr(ev, 'weights', None) is not None else ''}"
+                                      f"), {coll} all-gather of rank counts"),
+                      "launch": ("hipGraph replay of each rank's local evaluation" if graphed else "eager") +
+                                (", two evaluation slots on two HIP streams (consecutive evaluations overlap)"
+                                 if getattr(ev, "_streams", None) else "")}}
+    if args.full:
+        out["roofline"] = roofline
+    out["metrics"] = {"group": grp, "hit10": metrics[grp]["hit10"], "hit3": metrics[grp]["hit3"],
+                      "hit1": metrics[grp]["hit1"], "mrr": metrics[grp]["mrr"], "mr": metrics[grp]["mr"]}
+    if args.full:
+        out["parity"] = None
+    if "trained" in w:
+        out["config"]["tables"] = w["trained"]
+    elif "tables" in w:
+        out["config"]["tables"] = w["tables"]
+    return out
+
+
+DUMP_LIMIT = 64 * 2 ** 20   # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: array} as path/<name>.npy, float64 arrays as they are and
+    everything else as float32 (the integer counts stay exact: they are below 2^24). An array
+    over its share of DUMP_LIMIT is cut to a fixed, seeded sample of its flattened elements (in
+    index order), the same from run to run."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def _with_build(out):
@@ -1236,6 +1368,14 @@ def main():
     ap.add_argument("--shard", default="relation", choices=["relation", "entity"],
                     help="N > 1 link configs: split the queries (relation-sharded, one all-gather; default) or "
                          "the entity table (every query against 1/N of the entities, one all-reduce)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline figure: the "
+                         "sweep kernel alone and the roofline block, the filter record, the CPU baseline and the "
+                         "parity block against the reference, per-rank breakdowns (N > 1), per-part timings of the "
+                         "other configs (default: set up, warm up, time the steps, print the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64; rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1327,15 +1467,17 @@ def main():
     def steps(k, evs=None):
         # evaluation i + 1 is enqueued before the host reduces evaluation i's metrics, so that
         # reduction overlaps the next sweep; every evaluation's metrics are reduced in the loop
-        metrics, pending = None, None
+        # (metrics, counts) of the last one: what finish() hands its caller (the counts in the
+        # ticket's pinned buffer, valid until the next launch)
+        last, pending = (None, None), None
         for i in range(k):
             ticket = ev.launch(evs[i] if evs else None)
             if pending is not None:
-                metrics = ev.finish(pending, copy_counts=False)[0]
+                last = ev.finish(pending, copy_counts=False)
             pending = ticket
         if pending is not None:
-            metrics = ev.finish(pending, copy_counts=False)[0]
-        return metrics
+            last = ev.finish(pending, copy_counts=False)
+        return last
 
     steps(args.warmup)
     torch.cuda.synchronize()
@@ -1347,11 +1489,29 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    metrics = steps(args.steps, evs)
+    metrics, last_counts = steps(args.steps, evs)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and last_counts is not None:
+        # the last timed evaluation's return value: the (4, 2n) count table (raw, filtered, and the
+        # two type-constrained rows; head block then tail block) and the metrics reduced from it
+        grp = "filter_tc" if args.type_constrain else "filter"
+        dump_outputs(args.dump_outputs, {
+            "counts": np.asarray(last_counts),
+            "metrics": np.array([metrics[grp][k] for k in ("mrr", "mr", "hit10", "hit3", "hit1")], np.float64)})
+    if dist:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=_coll_dev(dist, dev))
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(_with_build(link_result(args, cfg, w, world, dist, ev, elapsed, metrics, graphed))),
+                  flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
 
     fixed_ms = None
     if graphed and n_local:  # the sweep kernel alone: events on the launch stream of eager evaluations
@@ -1371,10 +1531,6 @@ def main():
         print(f"eager twin filter record: {twin_fst}", file=sys.stderr)
         del sw, bufs
     sweep_ms = float(np.mean([a.elapsed_time(b) for a, b in evs])) if n_local else 0.0
-    if dist:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=_coll_dev(dist, dev))
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
     _, counts = ev.run()  # one more evaluation outside the timed region: the counts the parity check reads
     fst = ev.filter_stats() if hasattr(ev, "filter_stats") else None  # the count-only filter's record (l1q / bf3)
     print(f"evaluation filter record: {fst}", file=sys.stderr)
@@ -1382,8 +1538,6 @@ def main():
     if world > 1:  # every rank's local / sweep / fixed / collective time, gathered (all ranks take part)
         breakdown = rank_breakdown(ev, dist, dev, sweep_ms, n_local, args.shard == "entity", fixed_ms=fixed_ms)
 
-    total_triples = 2 * n * E
-    value = total_triples * args.steps / elapsed
     if rank == 0:
         bpt = bytes_per_triple(model, dim)
         triples_launch = n_local * e_local
@@ -1454,45 +1608,7 @@ def main():
                     "DistMult/ComplEx. hbm_algorithmic_x = SURVEY 8(d) algorithmic bytes (one entity row per "
                     "scored triple) / 8 TB/s: > 1 because each entity row is reused across a 128-query LDS tile; "
                     "the measured HBM traffic is in traffic / hbm_measured_GBs"})
-        data = {"c1": "synthetic TransE tables trained on the FB15K-237-ZS test triples",
-                "c2": "synthetic TransE tables trained on the FB15K-237-ZS test triples",
-                "c5": "synthetic 1M-entity DistMult table; relation table = the zsl_module generator (random-init "
-                      "UnifiedModel SN layers + LayerNormalization, HIP) over synthetic 384-d text CLS rows + noise; "
-                      "4,096 random test triples (= the filter set)"}.get(args.config, f"synthetic {model} tables")
-        if "tables" in w:
-            data += (" -- structured tables (mmre.workloads.structured_tables: each test triple pulls its tail "
-                     "toward the model's image of its head, so truths rank near the top)")
-        elif "trained" not in w:
-            data += " (OpenKE init, seed 0)"
-        if args.config != "c5":
-            data += (f" ({args.train_steps} steps of this build's HIP trainer: bit-exact OpenKE sampler + fused margin"
-                     f" loss, SGD 1.0, margin 5, neg 25)" if "trained" in w else "") + \
-                f" over the real {w['dataset']} test triples; filter set = all test triples + 272,115 synthetic train"
-        coll = "RCCL" if not dist or dist.get_backend() == "nccl" else "gloo rehearsal (every rank on cuda:0)"
-        metric = METRIC if args.config == "c2" else f"scored triples/sec, {cfg['workload']}"
-        if tc:
-            metric += " (type-constrained: Tester.run_link_prediction(type_constrain=True))"
-        grp = "filter_tc" if tc else "filter"
-        out = {"metric": metric,
-               "value": value, "unit": "scored triples/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-               "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": data,
-               "config": {"workload": cfg["workload"], "n_entities": E, "dim": dim, "n_sweeps": 2 * n,
-                          "parallelism": (f"entity-sharded x{world} (1/N of the entity tiles per rank), {coll} all-reduce "
-                                          f"of the count table" if args.shard == "entity" else
-                                          f"query-sharded x{world} (relation-major LPT with relation splits"
-                                          f"{', packed by calibrated per-query cost' if getattr(ev, 'weights', None) is not None else ''}"
-                                          f"), {coll} all-gather of rank counts"),
-                          "launch": ("hipGraph replay of each rank's local evaluation" if graphed else "eager") +
-                                    (", two evaluation slots on two HIP streams (consecutive evaluations overlap)"
-                                     if getattr(ev, "_streams", None) else "")},
-               "roofline": roof,
-               "metrics": {"group": grp, "hit10": metrics[grp]["hit10"], "hit3": metrics[grp]["hit3"],
-                           "hit1": metrics[grp]["hit1"], "mrr": metrics[grp]["mrr"], "mr": metrics[grp]["mr"]},
-               "parity": None}
-        if tc:
-            out["data"] += ("; type_constrain.txt built from the filter set by the reference n-n.py's rule (each "
-                            "relation's known heads / tails)")
+        out = link_result(args, cfg, w, world, dist, ev, elapsed, metrics, graphed, roofline=roof)
         if fst is not None and fst["kind"] == "l1q":
             pairs = int(n_local) * int(e_local)
             out["l1_filter"] = {"undecided_pairs": fst["undecided"],
@@ -1512,10 +1628,6 @@ def main():
                                           "with the canonical f32 chain (mmre_link_bf3_stats, rank 0's last "
                                           "evaluation); fallback_to_f32 = the pair list overflowed and the exact f32 "
                                           "MFMA sweep counted"}
-        if "trained" in w:
-            out["config"]["tables"] = w["trained"]
-        elif "tables" in w:
-            out["config"]["tables"] = w["tables"]
         if breakdown is not None:
             out["per_rank"], out["per_rank_summary"] = breakdown
             out["per_rank_note"] = ("medians of 20 runs per rank after the timed region: local_ms = the rank's local "

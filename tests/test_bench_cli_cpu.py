@@ -44,6 +44,32 @@ def test_gpu_count_comes_from_kfd_without_hip():
         assert n == 0
 
 
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: integer counts become float32 exactly, float64 stays, and an array over
+    its share of the size limit is cut to the same seeded sample on every call."""
+    import importlib.util
+
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    assert m.DUMP_LIMIT <= 64 * 2 ** 20
+    counts = np.arange(4 * 37, dtype=np.int32).reshape(4, 37) * 1000
+    metrics = np.array([0.1, 2.5], np.float64)
+    m.dump_outputs(str(tmp_path / "a"), {"counts": counts, "metrics": metrics})
+    c = np.load(tmp_path / "a" / "counts.npy")
+    assert c.dtype == np.float32 and c.shape == (4, 37) and np.array_equal(c, counts)
+    g = np.load(tmp_path / "a" / "metrics.npy")
+    assert g.dtype == np.float64 and np.array_equal(g, metrics)
+    monkeypatch.setattr(m, "DUMP_LIMIT", 2 * 4 * 10)  # two arrays: 10 float32 elements each
+    big = np.arange(1000, dtype=np.float32)
+    for d in ("b", "c"):
+        m.dump_outputs(str(tmp_path / d), {"x": big, "y": big[:5]})
+    xb, xc = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert xb.shape == (10,) and np.array_equal(xb, xc) and np.all(np.diff(xb) > 0) and np.all(np.isin(xb, big))
+    assert np.array_equal(np.load(tmp_path / "b" / "y.npy"), big[:5])
+
+
 def test_world_size_mismatch_refuses():
     r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0"], {"WORLD_SIZE": "3", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 2, (r.returncode, r.stderr[-500:])
