@@ -35,6 +35,10 @@ enum {
   MMRE_ROTATE = 4
 };
 enum { MMRE_HEAD_BATCH = 0, MMRE_TAIL_BATCH = 1 };
+/* Loss of the negative-sampling entry points (mmre_ns_opts_t) and the optimizer whose step the
+ * row owner applies. */
+enum { MMRE_LOSS_MARGIN = 0, MMRE_LOSS_SOFTPLUS = 1, MMRE_LOSS_SIGMOID = 2 };
+enum { MMRE_OPT_SGD = 0, MMRE_OPT_ADAGRAD = 1 };
 enum {
   MMRE_OK = 0,
   MMRE_ERR_ARG = 1,
@@ -349,6 +353,17 @@ int mmre_sampler_repo(const int64_t* d_eh, const int64_t* d_et, const int64_t* d
 int mmre_sgd_step(float* const* params, const float* const* grads, const int64_t* numel, int count, float lr,
                   void* stream);
 
+/* Adagrad step (torch.optim.Adagrad with lr_decay 0, weight_decay 0, maximize False -- the
+ * optimizer of OpenKE/examples/train_distmult_WN18RR.py and train_complex_WN18RR.py through
+ * Trainer.py:66-72) over `count` <= 8 float32 tensors in one launch, per element
+ *   sum <- sum + g * g;  std = sqrt(sum) + eps;  p <- p + (g * -lr) / std
+ * with every operation rounded once (the product before the add; IEEE sqrt and quotient): torch's foreach step on
+ * this ROCm build bit for bit (scripts/probes/adagrad_rounding.py). sums[t] is torch's
+ * state["sum"]. params[t] / grads[t] / sums[t] 16-B aligned, numel[t] elements each;
+ * MMRE_ERR_ARG otherwise, or for count outside 1..8 (checked before anything is launched). */
+int mmre_adagrad_step(float* const* params, const float* const* grads, float* const* sums, const int64_t* numel,
+                      int count, float lr, float eps, void* stream);
+
 /* ====================================================================== *
  *  Negative-sampling margin loss, fused (OpenKE strategy/NegativeSampling *
  *  .py:23-32 + loss/MarginLoss.py:24-28 + model forward/regularization;   *
@@ -493,6 +508,93 @@ int mmre_ns_step_openke_gen_pipe(const int64_t* d_train_list, int64_t train_tota
                                  float* d_grad_ent, float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im,
                                  float* d_work, float lr, void* stream, int64_t prepared, int64_t* d_next_h,
                                  int64_t* d_next_t, int64_t* d_next_r, float* d_next_y);
+
+/* ---- Other losses and optimizers: the `_ex` twin of each entry point above takes one more
+ * argument, a const mmre_ns_opts_t* (NULL: the entry point without the suffix, which is a
+ * one-line wrapper around its twin; values unchanged).
+ *
+ * loss_kind. MMRE_LOSS_MARGIN: as above. With p_b positive b's score, n_bj its k negatives,
+ * B = batch, T = adv_temperature:
+ *   MMRE_LOSS_SOFTPLUS (OpenKE SoftplusLoss.py:19-26, nn.Softplus(): sp(x) = x > 20 ? x :
+ *     log1p(exp(x))):        L = ( (1/B) sum_b sp(-p_b) + sum_b sum_j c_bj sp(n_bj) ) / 2
+ *   MMRE_LOSS_SIGMOID (SigmoidLoss.py:19-26, nn.LogSigmoid(): ls(x) = min(x, 0) -
+ *     log1p(exp(-|x|))):     L = -( (1/B) sum_b ls(p_b) + sum_b sum_j c_bj ls(-n_bj) ) / 2
+ *   c_bj = 1 / (B k), or with T > 0 softmax_j(+T n_bj) / B, detached (MarginLoss's weights
+ *   use -T n). dL/dp_b = -sigma(-p_b) / (2 B), dL/dn_bj = c_bj sigma(n_bj) / 2 (softplus:
+ *   sigma is exactly 1 past the threshold). + regul_rate * regularization exactly as for the
+ *   margin loss; loss_margin is ignored (these losses have no such term). Evaluated without
+ *   overflow for any finite score. An unknown kind: MMRE_ERR_ARG.
+ *   Models: every model through mmre_ns_forward_ex / mmre_ns_backward_ex; DistMult, ComplEx and
+ *   RotatE through the fused entry points and the one-call step as well. TransE's fused kernel
+ *   is margin-only: the fused entry points return MMRE_ERR_MODEL for TransE with another loss
+ *   (callers route it to mmre_ns_forward_ex / mmre_ns_backward_ex; mmre.ns does).
+ *
+ * optimizer (mmre_ns_fused_grad_sgd_ex, mmre_ns_step_openke_gen_pipe_ex; DistMult / ComplEx /
+ * RotatE). MMRE_OPT_SGD: p <- fma(-lr, g, p) as above. MMRE_OPT_ADAGRAD: the row owner
+ * applies mmre_adagrad_step's arithmetic to every table row with a slot -- sum <- sum + g * g,
+ * p <- p + (g * -lr) / (sqrt(sum) + eps) -- reading and writing the row of the sum
+ * table (torch's state["sum"], shaped like its parameter table): d_sum_ent [n_ent, dim] (RotatE
+ * [n_ent, 2 dim]), d_sum_rel [n_rel, dim], d_sum_ent_im / d_sum_rel_im for ComplEx. Rows
+ * without a slot have a zero gradient, for which the step leaves p and sum unchanged, so they
+ * are skipped. Missing sum tables, or Adagrad on TransE: MMRE_ERR_ARG. The workspaces are those
+ * of the entry points without the suffix. */
+typedef struct mmre_ns_opts {
+  int loss_kind; /* MMRE_LOSS_* */
+  int optimizer; /* MMRE_OPT_* */
+  float eps;     /* Adagrad's eps */
+  float* d_sum_ent;
+  float* d_sum_ent_im;
+  float* d_sum_rel;
+  float* d_sum_rel_im;
+} mmre_ns_opts_t;
+
+int mmre_ns_forward_ex(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
+                       const float* d_ent_im, const float* d_rel, const float* d_rel_im, int dim, float phase_denom,
+                       const int64_t* d_h, const int64_t* d_t, const int64_t* d_r, int64_t batch, int64_t neg,
+                       float loss_margin, float adv_temperature, float regul_rate, float* d_score, float* d_loss,
+                       float* d_work, void* stream, const mmre_ns_opts_t* opts);
+int mmre_ns_backward_ex(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
+                        const float* d_ent_im, const float* d_rel, const float* d_rel_im, int dim,
+                        float phase_denom, const int64_t* d_h, const int64_t* d_t, const int64_t* d_r, int64_t batch,
+                        int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
+                        const float* d_score, const float* d_grad_loss, float* d_grad_ent, float* d_grad_ent_im,
+                        float* d_grad_rel, float* d_grad_rel_im, int64_t n_ent, int64_t n_rel, float* d_work,
+                        int64_t work_floats, void* stream, const mmre_ns_opts_t* opts);
+int mmre_ns_fused_forward_ex(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
+                             const float* d_ent_im, const float* d_rel, const float* d_rel_im, int64_t n_ent,
+                             int64_t n_rel, int dim, float phase_denom, const int64_t* d_h, const int64_t* d_t,
+                             const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin, float adv_temperature,
+                             float regul_rate, float* d_score, float* d_loss, float* d_work, void* stream,
+                             const mmre_ns_opts_t* opts);
+int mmre_ns_fused_grad_ex(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
+                          const float* d_ent_im, const float* d_rel, const float* d_rel_im, int64_t n_ent,
+                          int64_t n_rel, int dim, float phase_denom, const int64_t* d_h, const int64_t* d_t,
+                          const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin, float adv_temperature,
+                          float regul_rate, const float* d_score, const float* d_grad_loss, float* d_grad_ent,
+                          float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work, void* stream,
+                          const mmre_ns_opts_t* opts);
+int mmre_ns_fused_grad_sgd_ex(int model, int norm_flag, float model_margin, int use_model_margin, float* d_ent,
+                              float* d_ent_im, float* d_rel, float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim,
+                              float phase_denom, const int64_t* d_h, const int64_t* d_t, const int64_t* d_r,
+                              int64_t batch, int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
+                              const float* d_score, const float* d_grad_loss, float* d_grad_ent, float* d_grad_ent_im,
+                              float* d_grad_rel, float* d_grad_rel_im, float* d_work, float lr, void* stream,
+                              const mmre_ns_opts_t* opts);
+int mmre_ns_step_openke_gen_pipe_ex(const int64_t* d_train_list, int64_t train_total, const int64_t* d_head_hrt,
+                                    const int64_t* d_tail_hrt, const int64_t* d_rel_hrt, const int64_t* d_lef_head,
+                                    const int64_t* d_rig_head, const int64_t* d_lef_tail, const int64_t* d_rig_tail,
+                                    const int64_t* d_lef_rel, const int64_t* d_rig_rel, const float* d_left_mean,
+                                    const float* d_right_mean, uint64_t* d_seeds, int64_t work_threads, int64_t mode,
+                                    const int32_t* d_blocks, int64_t n_blocks, int64_t* d_batch_h, int64_t* d_batch_t,
+                                    int64_t* d_batch_r, float* d_batch_y, int32_t* d_ticket, int model,
+                                    float model_margin, int use_model_margin, float* d_ent, float* d_ent_im,
+                                    float* d_rel, float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim,
+                                    float phase_denom, int64_t batch, int64_t neg, float loss_margin,
+                                    float adv_temperature, float regul_rate, float* d_score, float* d_loss,
+                                    float* d_grad_ent, float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im,
+                                    float* d_work, float lr, void* stream, int64_t prepared, int64_t* d_next_h,
+                                    int64_t* d_next_t, int64_t* d_next_r, float* d_next_y,
+                                    const mmre_ns_opts_t* opts);
 
 /* model(data) in 'normal' mode for n_rows arbitrary rows is mmre_ns_forward with
  * batch = n_rows, neg = 0, d_loss = NULL. Its backward (OpenKE Model.forward under any loss,

@@ -114,4 +114,74 @@ __device__ __forceinline__ void canon_sincos(float x, float* s_out, float* c_out
   *c_out = c;
 }
 
+// ---------------------------------------------------------------------------------------
+// Loss head of the Softplus / Sigmoid negative-sampling losses (OpenKE SoftplusLoss.py:19-26,
+// nn.Softplus() with beta 1 and threshold 20; SigmoidLoss.py:19-26, nn.LogSigmoid()), shared by
+// every kernel that forms a loss or its d/d(score) (ns.hip). p: the positive's score, n_j its
+// K negatives, T the self-adversarial temperature:
+//   L = sum_b [ f+(p_b) + sum_j w_bj f-(n_bj) ] / (2 B),   w_bj = softmax_j(+T n_bj) or 1 / K,
+//   softplus: f+(p) = sp(-p), f-(n) = sp(n);   sigmoid: f+(p) = -ls(p), f-(n) = -ls(-n).
+// The bracket is the per-positive partial (ns_loss_partial): the 1/K or softmax weight is folded
+// in before it is stored, so the positive's term and the negatives' sum share the one 1 / (2 B)
+// the reduction applies. expf only ever sees an argument <= 0, or one behind the threshold.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ float ns_softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
+__device__ __forceinline__ float ns_logsigmoid(float x) { return fminf(x, 0.0f) - log1pf(expf(-fabsf(x))); }
+// sigma(x) = 1 / (1 + e^-x), through e^-|x| alone
+__device__ __forceinline__ float ns_sigmoid(float x) {
+  const float e = expf(-fabsf(x));
+  return (x >= 0.0f ? 1.0f : e) / (1.0f + e);
+}
+// f-(x) of a negative's score x; a positive's f+(p) is f-(-p) for both kinds
+__device__ __forceinline__ float ns_loss_term(int kind, float x) {
+  return kind == MMRE_LOSS_SOFTPLUS ? ns_softplus(x) : -ns_logsigmoid(-x);
+}
+// d f-(x) / dx = sigma(x); softplus: exactly 1 past the threshold, as torch's backward has it
+__device__ __forceinline__ float ns_loss_dterm(int kind, float x) {
+  return (kind == MMRE_LOSS_SOFTPLUS && x > 20.0f) ? 1.0f : ns_sigmoid(x);
+}
+
+// The per-positive partial, by one lane: f+(p) + sum_j w_j f-(n[j]). The sums run in double (K
+// terms in index order: bit-reproducible), the result is rounded to float once.
+__device__ __forceinline__ float ns_loss_partial(int kind, float p, const float* n, int64_t K, float adv_t) {
+  double neg = 0.0;
+  if (adv_t > 0.0f) {
+    float mx = -INFINITY;
+    for (int64_t j = 0; j < K; ++j) mx = fmaxf(mx, n[j] * adv_t);
+    double den = 0.0;
+    for (int64_t j = 0; j < K; ++j) {
+      const float e = expf(n[j] * adv_t - mx);
+      den += (double)e;
+      neg += (double)e * (double)ns_loss_term(kind, n[j]);
+    }
+    neg = K > 0 ? neg / den : 0.0;
+  } else {
+    for (int64_t j = 0; j < K; ++j) neg += (double)ns_loss_term(kind, n[j]);
+    neg = K > 0 ? neg / (double)K : 0.0;
+  }
+  return (float)((double)ns_loss_term(kind, -p) + neg);
+}
+
+// d(loss)/d(score) of one row, unit upstream gradient: a positive's -sigma(-p) / (2 B); a
+// negative's c sigma(n) / 2 with c = softmax_j(T n) / B (mx, den: its positive's max of T n and
+// sum of exp(T n - mx)) or 1 / (B K).
+__device__ __forceinline__ float ns_row_coef(int kind, bool positive, float s, float adv_t, float mx, float den,
+                                             int64_t B, int64_t K) {
+  if (positive) return -ns_loss_dterm(kind, -s) / (2.0f * (float)B);
+  const float c = adv_t > 0.0f ? (expf(s * adv_t - mx) / den) / (float)B : 1.0f / (float)(B * K);
+  return c * ns_loss_dterm(kind, s) * 0.5f;
+}
+
+// torch.optim.Adagrad's plain step per element (lr_decay 0, weight_decay 0; its foreach
+// implementation's operation sequence and roundings, scripts/probes/adagrad_rounding.py):
+// addcmul_(sum, g, g, value=1) is sum + 1 * (g * g): the product is rounded before the add (the
+// scalar's multiply is what contracts with the add, and it is exact); the square root, + eps,
+// g * -lr, the quotient and the final add are rounded once each (torch's device sqrt and
+// quotient are the correctly rounded ones, as sqrtf and / are in this library). Shared by
+// mmre_adagrad_step and the fused row owner (ns.hip).
+__device__ __forceinline__ float adagrad_sum(float sum, float g) { return sum + g * g; }
+__device__ __forceinline__ float adagrad_param(float p, float g, float sum_new, float lr, float eps) {
+  return p + (g * -lr) / (sqrtf(sum_new) + eps);
+}
+
 }  // namespace mmre

@@ -37,7 +37,28 @@ struct NSArgs {
   const int64_t *h, *t, *r;
   int64_t B, K;  // positives, negatives per positive
   float loss_margin, adv_t, regul_rate;
+  int loss_kind;  // MMRE_LOSS_*: the margin arithmetic below, or the shared loss head (mmre_common.h)
 };
+
+// Adagrad in the generic row owner (mmre_ns_opts_t): sum tables shaped like the parameter tables
+struct NSOpt {
+  int adagrad;
+  float eps;
+  float *sum_ent, *sum_ent_im, *sum_rel, *sum_rel_im;
+};
+
+// Softplus / Sigmoid self-adversarial weights softmax_j(+T n_bj) of positive b, by its wave: the
+// maximum of T n and the sum of exp(T n - mx) (lane-strided partials, butterfly sums: the same
+// value in every lane, the same every run). Without a temperature: mx, den untouched.
+__device__ __forceinline__ void ns_adv_stats(const NSArgs& A, const float* __restrict__ score, int64_t b, int lane,
+                                             float& mx, float& den) {
+  if (!(A.adv_t > 0.0f)) return;
+  for (int64_t j = lane; j < A.K; j += kWave) mx = fmaxf(mx, score[b + (j + 1) * A.B] * A.adv_t);
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s));
+  for (int64_t j = lane; j < A.K; j += kWave) den += expf(score[b + (j + 1) * A.B] * A.adv_t - mx);
+  den = wave_sum(den);
+}
 
 // Raw score s of one row (before the model's margin transform) and, optionally, the
 // accumulation of g * d(score)/d(embeddings) into gradient tables.
@@ -137,7 +158,9 @@ __global__ __launch_bounds__(256) void k_ns_forward(NSArgs A, float* __restrict_
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   float loss = 0.0f;
   if (lane == 0) {
-    if (A.adv_t > 0.0f) {
+    if (A.loss_kind != MMRE_LOSS_MARGIN) {
+      loss = ns_loss_partial(A.loss_kind, p, s_n[w], A.K, A.adv_t);
+    } else if (A.adv_t > 0.0f) {
       float den = 0.0f;
       for (int64_t j = 0; j < A.K; ++j) den += expf(-s_n[w][j] * A.adv_t - mx);
       for (int64_t j = 0; j < A.K; ++j) {
@@ -158,7 +181,10 @@ __global__ __launch_bounds__(256) void k_ns_forward(NSArgs A, float* __restrict_
 // Fixed-order reduction of the per-positive partials (bit-reproducible loss) by threads
 // 0..255 of the workgroup (every thread of it must call: it synchronises): strided double sums
 // per thread, xor-butterfly wave sums (a + b and b + a agree, so every lane holds the same
-// total), the four wave totals in a fixed order; one barrier.
+// total), the four wave totals in a fixed order; one barrier. ANY_LOSS: the Softplus / Sigmoid
+// normalisation as well (false: the margin loss alone -- the TransE row owner, whose fused kernel
+// is margin-only, keeps the code it had).
+template <bool ANY_LOSS>
 __device__ void ns_reduce_block(const NSArgs& A, const float* part, float* loss) {
   __shared__ double red[7][4];
   double acc[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -192,6 +218,9 @@ __device__ void ns_reduce_block(const NSArgs& A, const float* part, float* loss)
     const double Bd = (double)A.B, Kd = (double)A.K;
     double l = A.adv_t > 0.0f ? t[0] / Bd : t[0] / (Bd * Kd);
     l += A.loss_margin;
+    if constexpr (ANY_LOSS) {
+      if (A.loss_kind != MMRE_LOSS_MARGIN) l = t[0] / (2.0 * Bd);  // partials carry their 1 / K or softmax weights
+    }
     if (A.regul_rate != 0.0f) {
       const double N = Bd * (1.0 + Kd);
       const double d = (double)A.dim;
@@ -208,7 +237,7 @@ __device__ void ns_reduce_block(const NSArgs& A, const float* part, float* loss)
 }
 
 __global__ __launch_bounds__(256) void k_ns_reduce(NSArgs A, const float* __restrict__ part, float* __restrict__ loss) {
-  ns_reduce_block(A, part, loss);
+  ns_reduce_block<true>(A, part, loss);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -397,7 +426,9 @@ __global__ __launch_bounds__(256) void k_ns_transe_forward(NSArgs A, float* __re
   // hinge max(p - n, -m) over the negatives, self-adversarial weights softmax(-n T) (detached)
   const float m = A.loss_margin;
   float loss = 0.0f;
-  if (A.adv_t > 0.0f) {
+  if (A.loss_kind != MMRE_LOSS_MARGIN) {
+    if (lane == 0) loss = ns_loss_partial(A.loss_kind, p, s_n, A.K, A.adv_t);
+  } else if (A.adv_t > 0.0f) {
     float mx = -INFINITY;
     for (int64_t j = lane; j < A.K; j += kWave) mx = fmaxf(mx, -s_n[j] * A.adv_t);
 #pragma unroll
@@ -1416,7 +1447,7 @@ __global__ __launch_bounds__(256, NC > 4 ? 5 : 7) void k_ns_row_owner(const floa
   __shared__ uint16_t s_bits[256];
   __shared__ int32_t s_hc[2];
   if ((int64_t)blockIdx.x == reduce_block) {  // the training step's loss (mmre_ns_step_openke): one extra workgroup
-    ns_reduce_block(RA, part, loss);
+    ns_reduce_block<false>(RA, part, loss);
     return;
   }
   if ((int64_t)blockIdx.x >= nx.block0 && (int64_t)blockIdx.x < nx.block0 + nx.n_blocks) {  // the next batch
@@ -1718,7 +1749,9 @@ __global__ __launch_bounds__(256) void k_ns_gen_forward(NSArgs A_, float* __rest
     if (lane != 0) return;
   }
   float loss = 0.0f;
-  if (A.adv_t > 0.0f) {
+  if (A.loss_kind != MMRE_LOSS_MARGIN) {
+    loss = ns_loss_partial(A.loss_kind, p, sn, A.K, A.adv_t);
+  } else if (A.adv_t > 0.0f) {
     float den = 0.0f;
     for (int64_t j = 0; j < A.K; ++j) den += expf(-sn[j] * A.adv_t - mx);
     for (int64_t j = 0; j < A.K; ++j) {
@@ -1764,23 +1797,29 @@ __global__ __launch_bounds__(256) void k_ns_gen_slots(NSArgs A_, const float* __
   const bool lead = SPLIT ? w == 0 : true;
   const float p = score[b];
   float mx = -INFINITY, den = 0.0f;
-  if (A.adv_t > 0.0f) {
+  const bool hinge = A.loss_kind == MMRE_LOSS_MARGIN;  // else Softplus / Sigmoid: the shared loss head
+  if (!hinge) {
+    ns_adv_stats(A, score, b, lane, mx, den);
+  } else if (A.adv_t > 0.0f) {
     for (int64_t j = lane; j < A.K; j += kWave) mx = fmaxf(mx, -score[b + (j + 1) * A.B] * A.adv_t);
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s));
     for (int64_t j = lane; j < A.K; j += kWave) den += expf(-score[b + (j + 1) * A.B] * A.adv_t - mx);
     den = wave_sum(den);
   }
+  // minus d(loss)/d(score) of negative j (the hinge: also what it adds to its positive's)
   auto coef = [&](int64_t j) {
     const float n = score[b + (j + 1) * A.B];
+    if (!hinge) return -ns_row_coef(A.loss_kind, false, n, A.adv_t, mx, den, A.B, A.K);
     const float x = p - n, m = -A.loss_margin;
     const float ind = x > m ? 1.0f : (x == m ? 0.5f : 0.0f);  // maximum(): ties split the gradient
     const float c = A.adv_t > 0.0f ? (expf(-n * A.adv_t - mx) / den) / (float)A.B : 1.0f / (float)(A.B * A.K);
     return c * ind;
   };
   float gp = 0.0f;
-  for (int64_t j = lane; j < A.K; j += kWave) gp += coef(j);
+  for (int64_t j = lane; hinge && j < A.K; j += kWave) gp += coef(j);
   gp = wave_sum(gp);
+  if (!hinge) gp = ns_row_coef(A.loss_kind, true, p, A.adv_t, mx, den, A.B, A.K);
   const int64_t ph = A.h[b], pr = A.r[b], pt = A.t[b];
   Row2<NC> H, R, T, Gh, Gr, Gt, dH, dR, dT;
   gen_load(H, A, true, ph, lane);
@@ -1923,7 +1962,8 @@ template <int NC, class Ord>
 __device__ __forceinline__ void gen_owner_row(Ord& ord, bool active, const NSArgs& A, int64_t row, int n,
                                               const Row2<NC>& v, int64_t n_ent, float reg_ent, float reg_rel,
                                               const float* __restrict__ rec, const float* __restrict__ grad_loss,
-                                              float* oa, float* ob, float* pa, float* pb, float sgd_lr) {
+                                              float* oa, float* ob, float* pa, float* pb, float sgd_lr,
+                                              float adagrad_eps = 0.0f, float* sa = nullptr, float* sb = nullptr) {
   const int lane = threadIdx.x & 63;
   const bool is_ent = row < n_ent;
   const int d = A.dim;
@@ -1964,7 +2004,24 @@ __device__ __forceinline__ void gen_owner_row(Ord& ord, bool active, const NSArg
   }
   vstore(oa, dy.a, d, lane);
   if (two) vstore(ob, dy.b, d, lane);
-  if (sgd_lr != 0.0f) {
+  bool adagrad = false;
+  if constexpr (NC <= 8) adagrad = sgd_lr != 0.0f && sa;  // the fused path's widths (gen_nc); the wider rows
+                                                           // instances (rows backward) never step
+  if (adagrad) {  // Adagrad (mmre_adagrad_step's arithmetic) on the row and its sum row
+    Row2<NC> s, p;
+    vload(s.a, sa, d, lane);
+    if (two) vload(s.b, sb, d, lane); else vzero(s.b);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      s.a.v[c] = adagrad_sum(s.a.v[c], dy.a.v[c]);
+      s.b.v[c] = adagrad_sum(s.b.v[c], dy.b.v[c]);
+      p.a.v[c] = adagrad_param(v.a.v[c], dy.a.v[c], s.a.v[c], sgd_lr, adagrad_eps);
+      p.b.v[c] = adagrad_param(v.b.v[c], dy.b.v[c], s.b.v[c], sgd_lr, adagrad_eps);
+    }
+    vstore(sa, s.a, d, lane);
+    vstore(pa, p.a, d, lane);
+    if (two) { vstore(sb, s.b, d, lane); vstore(pb, p.b, d, lane); }
+  } else if (sgd_lr != 0.0f) {
     Row2<NC> p;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -1991,7 +2048,7 @@ __global__ __launch_bounds__(256) void k_ns_gen_owner(NSArgs A, int64_t n_ent, i
                                                       float* pent, float* pent_im, float* prel, float* prel_im,
                                                       int64_t row_block0, int n_hub_wg, int64_t n_slots,
                                                       const float* __restrict__ part, float* __restrict__ loss,
-                                                      int64_t reduce_block, NSNext nx) {
+                                                      int64_t reduce_block, NSNext nx, NSOpt opt) {
   __shared__ int64_t s_hub[4][NS_HUB];
   __shared__ uint16_t s_bits[256];
   __shared__ int32_t s_hc[2];
@@ -1999,7 +2056,7 @@ __global__ __launch_bounds__(256) void k_ns_gen_owner(NSArgs A, int64_t n_ent, i
   // the one-call training step (mmre_ns_step_openke_gen_pipe): the loss reduction and the next
   // batch's sampler workgroups ride in this grid (the forward zeroes the slot counts itself)
   if ((int64_t)blockIdx.x == reduce_block) {
-    ns_reduce_block(A, part, loss);
+    ns_reduce_block<(NC <= 8)>(A, part, loss);  // the wider instances (rows backward) never reduce a loss
     return;
   }
   if ((int64_t)blockIdx.x >= nx.block0 && (int64_t)blockIdx.x < nx.block0 + nx.n_blocks) {
@@ -2009,10 +2066,20 @@ __global__ __launch_bounds__(256) void k_ns_gen_owner(NSArgs A, int64_t n_ent, i
   const int lane = threadIdx.x & 63;
   const int d = A.dim;
   // output rows of the two halves of table row `row`
-  auto outs = [&](int64_t row, float*& oa, float*& ob, float*& pa, float*& pb) {
+  auto outs = [&](int64_t row, float*& oa, float*& ob, float*& pa, float*& pb, float*& sa, float*& sb) {
     const bool is_ent = row < n_ent;
     const int64_t id = is_ent ? row : row - n_ent;
-    ob = pa = pb = nullptr;
+    ob = pa = pb = sa = sb = nullptr;
+    if constexpr (NC <= 8) if (opt.adagrad) {  // the row of the sum table(s), laid out like the parameter row
+      if (is_ent) {
+        if (A.model == MMRE_COMPLEX) { sa = opt.sum_ent + id * d; sb = opt.sum_ent_im + id * d; }
+        else if (A.model == MMRE_ROTATE) { sa = opt.sum_ent + id * 2 * d; sb = sa + d; }
+        else sa = opt.sum_ent + id * d;
+      } else {
+        sa = opt.sum_rel + id * d;
+        if (A.model == MMRE_COMPLEX) sb = opt.sum_rel_im + id * d;
+      }
+    }
     if (is_ent) {
       if (A.model == MMRE_COMPLEX) { oa = gent + id * d; ob = gent_im + id * d; pa = pent ? pent + id * d : nullptr; pb = pent_im ? pent_im + id * d : nullptr; }
       else if (A.model == MMRE_ROTATE) { oa = gent + id * 2 * d; ob = oa + d; pa = pent ? pent + id * 2 * d : nullptr; pb = pa ? pa + d : nullptr; }
@@ -2027,13 +2094,13 @@ __global__ __launch_bounds__(256) void k_ns_gen_owner(NSArgs A, int64_t n_ent, i
     for_hub_rows(counts, n_ent + n_rel, (int)blockIdx.x, n_hub_wg, s_bits,
                  [&](int64_t row, int n) {
                    const bool is_ent = row < n_ent;
-                   float *oa, *ob, *pa, *pb;
-                   outs(row, oa, ob, pa, pb);
+                   float *oa, *ob, *pa, *pb, *sa, *sb;
+                   outs(row, oa, ob, pa, pb, sa, sb);
                    Row2<NC> v;
                    gen_load(v, A, is_ent, is_ent ? row : row - n_ent, lane);
                    HubOrder ord = hub_order(s_hub, s_hc, bucket, ovf, ovf_n[0], n, row, n_slots);
                    gen_owner_row<NC>(ord, threadIdx.x < 64, A, row, n, v, n_ent, reg_ent, reg_rel, rec, grad_loss, oa,
-                                     ob, pa, pb, sgd_lr);
+                                     ob, pa, pb, sgd_lr, opt.eps, sa, sb);
                  });
     return;
   }
@@ -2043,8 +2110,8 @@ __global__ __launch_bounds__(256) void k_ns_gen_owner(NSArgs A, int64_t n_ent, i
   const int64_t id = is_ent ? row : row - n_ent;
   const int64_t pre = bucket[row * NS_BUCKET + lane];
   const bool two = A.model == MMRE_COMPLEX || (A.model == MMRE_ROTATE && is_ent);
-  float *oa, *ob, *pa, *pb;
-  outs(row, oa, ob, pa, pb);
+  float *oa, *ob, *pa, *pb, *sa, *sb;
+  outs(row, oa, ob, pa, pb, sa, sb);
   const int n = counts[row];
   if (n > NS_HUB) return;  // a hub workgroup's row
   if (n == 0) {
@@ -2059,7 +2126,8 @@ __global__ __launch_bounds__(256) void k_ns_gen_owner(NSArgs A, int64_t n_ent, i
   gen_load(v, A, is_ent, id, lane);
   SlotOrder ord{ovf, n > NS_BUCKET ? ovf_n[0] : 0, n, lane, row, s_hub[threadIdx.x >> 6], pre, 0, 0};
   ord.init();
-  gen_owner_row<NC>(ord, true, A, row, n, v, n_ent, reg_ent, reg_rel, rec, grad_loss, oa, ob, pa, pb, sgd_lr);
+  gen_owner_row<NC>(ord, true, A, row, n, v, n_ent, reg_ent, reg_rel, rec, grad_loss, oa, ob, pa, pb, sgd_lr, opt.eps,
+                    sa, sb);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2131,6 +2199,15 @@ __global__ __launch_bounds__(256) void k_ns_row_coef(NSArgs A, const float* __re
   if (b >= A.B) return;
   const float p = score[b];
   float mx = -INFINITY, den = 0.0f;
+  if (A.loss_kind != MMRE_LOSS_MARGIN) {  // Softplus / Sigmoid: the shared loss head
+    ns_adv_stats(A, score, b, lane, mx, den);
+    for (int64_t j = lane; j < A.K; j += kWave) {
+      const int64_t row = b + (j + 1) * A.B;
+      coef[row] = ns_row_coef(A.loss_kind, false, score[row], A.adv_t, mx, den, A.B, A.K);
+    }
+    if (lane == 0) coef[b] = ns_row_coef(A.loss_kind, true, p, A.adv_t, mx, den, A.B, A.K);
+    return;
+  }
   if (A.adv_t > 0.0f) {
     for (int64_t j = lane; j < A.K; j += kWave) mx = fmaxf(mx, -score[b + (j + 1) * A.B] * A.adv_t);
 #pragma unroll
@@ -2205,6 +2282,16 @@ static int ns_args(NSArgs& A, int model, int norm_flag, float model_margin, int 
   A.ent = ent; A.ent_im = ent_im; A.rel = rel; A.rel_im = rel_im;
   A.h = h; A.t = t; A.r = r; A.B = batch; A.K = neg;
   A.loss_margin = loss_margin; A.adv_t = adv_t; A.regul_rate = regul_rate;
+  A.loss_kind = MMRE_LOSS_MARGIN;
+  return MMRE_OK;
+}
+
+// the options' checks that need no other argument (first in every _ex entry point: before any launch)
+static int ns_opts_check(const mmre_ns_opts_t* o) {
+  if (!o) return MMRE_OK;
+  if (o->loss_kind != MMRE_LOSS_MARGIN && o->loss_kind != MMRE_LOSS_SOFTPLUS && o->loss_kind != MMRE_LOSS_SIGMOID)
+    return MMRE_ERR_ARG;
+  if (o->optimizer != MMRE_OPT_SGD && o->optimizer != MMRE_OPT_ADAGRAD) return MMRE_ERR_ARG;
   return MMRE_OK;
 }
 
@@ -2217,15 +2304,19 @@ extern "C" int64_t mmre_ns_workspace(int64_t batch, int64_t neg) {
   return 7 * (batch > 0 ? batch : 1);
 }
 
-extern "C" int mmre_ns_forward(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
-                               const float* d_ent_im, const float* d_rel, const float* d_rel_im, int dim,
-                               float phase_denom, const int64_t* d_h, const int64_t* d_t, const int64_t* d_r,
-                               int64_t batch, int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
-                               float* d_score, float* d_loss, float* d_work, void* stream) {
+extern "C" int mmre_ns_forward_ex(int model, int norm_flag, float model_margin, int use_model_margin,
+                                  const float* d_ent, const float* d_ent_im, const float* d_rel, const float* d_rel_im,
+                                  int dim, float phase_denom, const int64_t* d_h, const int64_t* d_t,
+                                  const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin,
+                                  float adv_temperature, float regul_rate, float* d_score, float* d_loss, float* d_work,
+                                  void* stream, const mmre_ns_opts_t* opts) {
   NSArgs A;
-  int rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
-                   phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  int rc = ns_opts_check(opts);
   if (rc) return rc;
+  rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
+               phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  if (rc) return rc;
+  if (opts) A.loss_kind = opts->loss_kind;
   if (!d_score || !d_work) return MMRE_ERR_ARG;
   if (neg > NS_MAXK) return MMRE_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
@@ -2252,6 +2343,16 @@ extern "C" int mmre_ns_forward(int model, int norm_flag, float model_margin, int
     MMRE_CHECK_LAUNCH();
   }
   return MMRE_OK;
+}
+
+extern "C" int mmre_ns_forward(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
+                               const float* d_ent_im, const float* d_rel, const float* d_rel_im, int dim,
+                               float phase_denom, const int64_t* d_h, const int64_t* d_t, const int64_t* d_r,
+                               int64_t batch, int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
+                               float* d_score, float* d_loss, float* d_work, void* stream) {
+  return mmre_ns_forward_ex(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
+                            phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate, d_score,
+                            d_loss, d_work, stream, nullptr);
 }
 
 // Workspace of the rows backward (floats): per-row coefficients, 3 slot records per row,
@@ -2307,7 +2408,7 @@ static int rows_backward_impl(const NSArgs& A, const float* d_coef, int64_t n_ro
     hipLaunchKernelGGL((k_ns_gen_owner<NC_>), hgrid, blk, 0, st, A, n_ent, n_rel, reg_ent, reg_rel, S.rec, S.counts, \
                        S.bucket, S.ovf, S.ovf_n, 0, d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel,             \
                        d_grad_rel_im, 0.0f, nullptr, nullptr, nullptr, nullptr, (int64_t)NS_HUB_WG, NS_HUB_WG,        \
-                       3 * n_rows, nullptr, nullptr, (int64_t)-1, NSNext{});                                        \
+                       3 * n_rows, nullptr, nullptr, (int64_t)-1, NSNext{}, NSOpt{});                               \
   } while (0)
   if (nc == 1) MMRE_ROWS(1);
   else if (nc == 2) MMRE_ROWS(2);
@@ -2320,18 +2421,21 @@ static int rows_backward_impl(const NSArgs& A, const float* d_coef, int64_t n_ro
   return MMRE_OK;
 }
 
-extern "C" int mmre_ns_backward(int model, int norm_flag, float model_margin, int use_model_margin,
-                                const float* d_ent, const float* d_ent_im, const float* d_rel, const float* d_rel_im,
-                                int dim, float phase_denom, const int64_t* d_h, const int64_t* d_t,
-                                const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin,
-                                float adv_temperature, float regul_rate, const float* d_score,
-                                const float* d_grad_loss, float* d_grad_ent, float* d_grad_ent_im, float* d_grad_rel,
-                                float* d_grad_rel_im, int64_t n_ent, int64_t n_rel, float* d_work,
-                                int64_t work_floats, void* stream) {
+extern "C" int mmre_ns_backward_ex(int model, int norm_flag, float model_margin, int use_model_margin,
+                                   const float* d_ent, const float* d_ent_im, const float* d_rel,
+                                   const float* d_rel_im, int dim, float phase_denom, const int64_t* d_h,
+                                   const int64_t* d_t, const int64_t* d_r, int64_t batch, int64_t neg,
+                                   float loss_margin, float adv_temperature, float regul_rate, const float* d_score,
+                                   const float* d_grad_loss, float* d_grad_ent, float* d_grad_ent_im,
+                                   float* d_grad_rel, float* d_grad_rel_im, int64_t n_ent, int64_t n_rel,
+                                   float* d_work, int64_t work_floats, void* stream, const mmre_ns_opts_t* opts) {
   NSArgs A;
-  int rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
-                   phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  int rc = ns_opts_check(opts);
   if (rc) return rc;
+  rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
+               phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  if (rc) return rc;
+  if (opts) A.loss_kind = opts->loss_kind;
   if (!d_score || !d_grad_ent || !d_grad_rel || !d_work || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
   if (model == MMRE_COMPLEX && (!d_grad_ent_im || !d_grad_rel_im)) return MMRE_ERR_ARG;
   const int64_t n_rows = batch * (1 + neg);
@@ -2354,6 +2458,20 @@ extern "C" int mmre_ns_backward(int model, int norm_flag, float model_margin, in
   R.K = 0;
   return rows_backward_impl(R, d_work + w.coef, n_rows, n_ent, n_rel, reg_ent, reg_rel, d_grad_loss, d_grad_ent,
                             d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, w, st);
+}
+
+extern "C" int mmre_ns_backward(int model, int norm_flag, float model_margin, int use_model_margin,
+                                const float* d_ent, const float* d_ent_im, const float* d_rel, const float* d_rel_im,
+                                int dim, float phase_denom, const int64_t* d_h, const int64_t* d_t,
+                                const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin,
+                                float adv_temperature, float regul_rate, const float* d_score,
+                                const float* d_grad_loss, float* d_grad_ent, float* d_grad_ent_im, float* d_grad_rel,
+                                float* d_grad_rel_im, int64_t n_ent, int64_t n_rel, float* d_work,
+                                int64_t work_floats, void* stream) {
+  return mmre_ns_backward_ex(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
+                             phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate, d_score,
+                             d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, n_ent, n_rel, d_work,
+                             work_floats, stream, nullptr);
 }
 
 extern "C" int mmre_score_rows_backward(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2425,21 +2543,30 @@ extern "C" int64_t mmre_ns_fused_workspace(int model, int norm_flag, int64_t bat
   return w.total > 7 * batch ? w.total : 7 * batch;
 }
 
-static bool fused_fast(const NSArgs& A) { return transe_fast_nc(A) != 0 && A.K <= NSW * NSF_MAXJ; }
+// the fused TransE kernel's shapes; it is margin-only (k_ns_transe_fused has no other loss head)
+static bool fused_fast(const NSArgs& A) {
+  return A.loss_kind == MMRE_LOSS_MARGIN && transe_fast_nc(A) != 0 && A.K <= NSW * NSF_MAXJ;
+}
 
 // elements per lane of the row-owner path of the other models (d <= 512)
 static int gen_nc(int dim) { return dim <= 64 ? 1 : dim <= 128 ? 2 : dim <= 256 ? 4 : dim <= 512 ? 8 : 0; }
 
-extern "C" int mmre_ns_fused_forward(int model, int norm_flag, float model_margin, int use_model_margin,
-                                     const float* d_ent, const float* d_ent_im, const float* d_rel,
-                                     const float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim, float phase_denom,
-                                     const int64_t* d_h, const int64_t* d_t, const int64_t* d_r, int64_t batch,
-                                     int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
-                                     float* d_score, float* d_loss, float* d_work, void* stream) {
+extern "C" int mmre_ns_fused_forward_ex(int model, int norm_flag, float model_margin, int use_model_margin,
+                                        const float* d_ent, const float* d_ent_im, const float* d_rel,
+                                        const float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim,
+                                        float phase_denom, const int64_t* d_h, const int64_t* d_t, const int64_t* d_r,
+                                        int64_t batch, int64_t neg, float loss_margin, float adv_temperature,
+                                        float regul_rate, float* d_score, float* d_loss, float* d_work, void* stream,
+                                        const mmre_ns_opts_t* opts) {
   NSArgs A;
-  int rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
-                   phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  int rc = ns_opts_check(opts);
   if (rc) return rc;
+  rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
+               phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  if (rc) return rc;
+  if (opts) A.loss_kind = opts->loss_kind;
+  // TransE under Softplus / Sigmoid is the rows path's (mmre_ns_forward_ex / mmre_ns_backward_ex)
+  if (is_transe(model) && A.loss_kind != MMRE_LOSS_MARGIN) return MMRE_ERR_MODEL;
   if (!d_score || !d_loss || !d_work || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
   if (neg > NS_MAXK) return MMRE_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
@@ -2510,6 +2637,17 @@ extern "C" int mmre_ns_fused_forward(int model, int norm_flag, float model_margi
   return MMRE_OK;
 }
 
+extern "C" int mmre_ns_fused_forward(int model, int norm_flag, float model_margin, int use_model_margin,
+                                     const float* d_ent, const float* d_ent_im, const float* d_rel,
+                                     const float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim, float phase_denom,
+                                     const int64_t* d_h, const int64_t* d_t, const int64_t* d_r, int64_t batch,
+                                     int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
+                                     float* d_score, float* d_loss, float* d_work, void* stream) {
+  return mmre_ns_fused_forward_ex(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im,
+                                  n_ent, n_rel, dim, phase_denom, d_h, d_t, d_r, batch, neg, loss_margin,
+                                  adv_temperature, regul_rate, d_score, d_loss, d_work, stream, nullptr);
+}
+
 static int fused_grad_impl(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
                            const float* d_ent_im, const float* d_rel, const float* d_rel_im, int64_t n_ent,
                            int64_t n_rel, int dim, float phase_denom, const int64_t* d_h, const int64_t* d_t,
@@ -2517,11 +2655,24 @@ static int fused_grad_impl(int model, int norm_flag, float model_margin, int use
                            float regul_rate, const float* d_score, const float* d_grad_loss, float* d_grad_ent,
                            float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work, float lr,
                            float* pe, float* pei, float* pr, float* pri, void* stream, float* d_loss_out = nullptr,
-                           int parity = 0, const NSNext* nxp = nullptr) {
+                           int parity = 0, const NSNext* nxp = nullptr, const mmre_ns_opts_t* opts = nullptr) {
   NSArgs A;
-  int rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
-                   phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  int rc = ns_opts_check(opts);
   if (rc) return rc;
+  rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
+               phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  if (rc) return rc;
+  NSOpt gopt{};
+  if (opts) {
+    A.loss_kind = opts->loss_kind;
+    // TransE under Softplus / Sigmoid is the rows path's (mmre_ns_forward_ex / mmre_ns_backward_ex)
+    if (is_transe(model) && A.loss_kind != MMRE_LOSS_MARGIN) return MMRE_ERR_MODEL;
+    if (opts->optimizer == MMRE_OPT_ADAGRAD && lr != 0.0f) {  // the generic row owner's Adagrad branch
+      if (is_transe(model) || !opts->d_sum_ent || !opts->d_sum_rel) return MMRE_ERR_ARG;
+      if (model == MMRE_COMPLEX && (!opts->d_sum_ent_im || !opts->d_sum_rel_im)) return MMRE_ERR_ARG;
+      gopt = NSOpt{1, opts->eps, opts->d_sum_ent, opts->d_sum_ent_im, opts->d_sum_rel, opts->d_sum_rel_im};
+    }
+  }
   if (!d_score || !d_work || !d_grad_ent || !d_grad_rel || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
   if (model == MMRE_COMPLEX && (!d_grad_ent_im || !d_grad_rel_im)) return MMRE_ERR_ARG;
   if (lr != 0.0f && (!pe || !pr || (model == MMRE_COMPLEX && (!pei || !pri)))) return MMRE_ERR_ARG;
@@ -2562,7 +2713,7 @@ static int fused_grad_impl(int model, int norm_flag, float model_margin, int use
     hipLaunchKernelGGL((k_ns_gen_owner<NC_>), dim3(gen_row0 + ogrid.x), blk, 0, st, A, n_ent, n_rel, reg_ent,        \
                        reg_rel, S.rec, S.counts, S.bucket, S.ovf, S.ovf_n, w.dpad, d_grad_loss, d_grad_ent,          \
                        d_grad_ent_im, d_grad_rel, d_grad_rel_im, lr, pe, pei, pr, pri, gen_row0, NS_HUB_WG, w.slots,  \
-                       d_work + w.part, d_loss_out, gen_reduce, gnx);                                               \
+                       d_work + w.part, d_loss_out, gen_reduce, gnx, gopt);                                         \
   } while (0)
     if (nc == 1) MMRE_NS_GEN(1);
     else if (nc == 2) MMRE_NS_GEN(2);
@@ -2601,6 +2752,20 @@ static int fused_grad_impl(int model, int norm_flag, float model_margin, int use
   return MMRE_OK;
 }
 
+extern "C" int mmre_ns_fused_grad_ex(int model, int norm_flag, float model_margin, int use_model_margin,
+                                     const float* d_ent, const float* d_ent_im, const float* d_rel,
+                                     const float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim, float phase_denom,
+                                     const int64_t* d_h, const int64_t* d_t, const int64_t* d_r, int64_t batch,
+                                     int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
+                                     const float* d_score, const float* d_grad_loss, float* d_grad_ent,
+                                     float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work,
+                                     void* stream, const mmre_ns_opts_t* opts) {
+  return fused_grad_impl(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, n_ent,
+                         n_rel, dim, phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate,
+                         d_score, d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, 0.0f,
+                         nullptr, nullptr, nullptr, nullptr, stream, nullptr, 0, nullptr, opts);
+}
+
 extern "C" int mmre_ns_fused_grad(int model, int norm_flag, float model_margin, int use_model_margin,
                                   const float* d_ent, const float* d_ent_im, const float* d_rel, const float* d_rel_im,
                                   int64_t n_ent, int64_t n_rel, int dim, float phase_denom, const int64_t* d_h,
@@ -2608,10 +2773,25 @@ extern "C" int mmre_ns_fused_grad(int model, int norm_flag, float model_margin, 
                                   float loss_margin, float adv_temperature, float regul_rate, const float* d_score,
                                   const float* d_grad_loss, float* d_grad_ent, float* d_grad_ent_im, float* d_grad_rel,
                                   float* d_grad_rel_im, float* d_work, void* stream) {
+  return mmre_ns_fused_grad_ex(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im,
+                               n_ent, n_rel, dim, phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature,
+                               regul_rate, d_score, d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im,
+                               d_work, stream, nullptr);
+}
+
+extern "C" int mmre_ns_fused_grad_sgd_ex(int model, int norm_flag, float model_margin, int use_model_margin,
+                                         float* d_ent, float* d_ent_im, float* d_rel, float* d_rel_im, int64_t n_ent,
+                                         int64_t n_rel, int dim, float phase_denom, const int64_t* d_h,
+                                         const int64_t* d_t, const int64_t* d_r, int64_t batch, int64_t neg,
+                                         float loss_margin, float adv_temperature, float regul_rate,
+                                         const float* d_score, const float* d_grad_loss, float* d_grad_ent,
+                                         float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work,
+                                         float lr, void* stream, const mmre_ns_opts_t* opts) {
+  if (!(lr != 0.0f)) return MMRE_ERR_ARG;
   return fused_grad_impl(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, n_ent,
                          n_rel, dim, phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate,
-                         d_score, d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, 0.0f,
-                         nullptr, nullptr, nullptr, nullptr, stream);
+                         d_score, d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, lr, d_ent,
+                         d_ent_im, d_rel, d_rel_im, stream, nullptr, 0, nullptr, opts);
 }
 
 extern "C" int mmre_ns_fused_grad_sgd(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2622,11 +2802,10 @@ extern "C" int mmre_ns_fused_grad_sgd(int model, int norm_flag, float model_marg
                                       const float* d_score, const float* d_grad_loss, float* d_grad_ent,
                                       float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work,
                                       float lr, void* stream) {
-  if (!(lr != 0.0f)) return MMRE_ERR_ARG;
-  return fused_grad_impl(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, n_ent,
-                         n_rel, dim, phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate,
-                         d_score, d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, lr, d_ent,
-                         d_ent_im, d_rel, d_rel_im, stream);
+  return mmre_ns_fused_grad_sgd_ex(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im,
+                                   n_ent, n_rel, dim, phase_denom, d_h, d_t, d_r, batch, neg, loss_margin,
+                                   adv_temperature, regul_rate, d_score, d_grad_loss, d_grad_ent, d_grad_ent_im,
+                                   d_grad_rel, d_grad_rel_im, d_work, lr, stream, nullptr);
 }
 
 extern "C" int mmre_ns_forward_backward(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2762,11 +2941,18 @@ static int step_openke_gen_impl(const OpenKESamplerArgs& sa, int64_t n_sampler, 
                                 float loss_margin, float adv_temperature, float regul_rate, float* d_score,
                                 float* d_loss, float* d_grad_ent, float* d_grad_ent_im, float* d_grad_rel,
                                 float* d_grad_rel_im, float* d_work, float lr, hipStream_t st, int64_t prepared,
-                                int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y) {
+                                int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y,
+                                const mmre_ns_opts_t* opts) {
   NSArgs A;
   int rc = ns_args(A, model, 0, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim, phase_denom,
                    sa.bh, sa.bt, sa.br, batch, neg, loss_margin, adv_temperature, regul_rate);
   if (rc) return rc;
+  if (opts) {  // checked by the entry point; the sum tables before the forward is launched
+    A.loss_kind = opts->loss_kind;
+    if (opts->optimizer == MMRE_OPT_ADAGRAD &&
+        (!opts->d_sum_ent || !opts->d_sum_rel || (model == MMRE_COMPLEX && (!opts->d_sum_ent_im || !opts->d_sum_rel_im))))
+      return MMRE_ERR_ARG;
+  }
   const int gnc = gen_nc(dim);
   if (is_transe(model) || gnc == 0 || neg > NS_MAXK) return MMRE_ERR_SHAPE;
   FusedWs w;
@@ -2809,7 +2995,7 @@ static int step_openke_gen_impl(const OpenKESamplerArgs& sa, int64_t n_sampler, 
   return fused_grad_impl(model, 0, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, n_ent, n_rel, dim,
                          phase_denom, sa.bh, sa.bt, sa.br, batch, neg, loss_margin, adv_temperature, regul_rate,
                          d_score, nullptr, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, lr, d_ent,
-                         d_ent_im, d_rel, d_rel_im, st, d_loss, 0, d_next_h ? &nx : nullptr);
+                         d_ent_im, d_rel, d_rel_im, st, d_loss, 0, d_next_h ? &nx : nullptr, opts);
 }
 
 #define MMRE_STEP_OPENKE_PARAMS                                                                                      \
@@ -2840,7 +3026,7 @@ extern "C" int mmre_ns_step_openke_pipe(MMRE_STEP_OPENKE_PARAMS, int64_t prepare
 // The one-call step for DistMult / ComplEx / RotatE (step_openke_gen_impl): the sampler arguments of
 // mmre_ns_step_openke, then the generic model's (ComplEx im tables, RotatE's model margin and phase),
 // then prepared (bit 0: d_batch_* already drawn) and the next batch's buffers (nullable).
-extern "C" int mmre_ns_step_openke_gen_pipe(
+extern "C" int mmre_ns_step_openke_gen_pipe_ex(
     const int64_t* d_train_list, int64_t train_total, const int64_t* d_head_hrt, const int64_t* d_tail_hrt,
     const int64_t* d_rel_hrt, const int64_t* d_lef_head, const int64_t* d_rig_head, const int64_t* d_lef_tail,
     const int64_t* d_rig_tail, const int64_t* d_lef_rel, const int64_t* d_rig_rel, const float* d_left_mean,
@@ -2850,7 +3036,8 @@ extern "C" int mmre_ns_step_openke_gen_pipe(
     int64_t n_ent, int64_t n_rel, int dim, float phase_denom, int64_t batch, int64_t neg, float loss_margin,
     float adv_temperature, float regul_rate, float* d_score, float* d_loss, float* d_grad_ent, float* d_grad_ent_im,
     float* d_grad_rel, float* d_grad_rel_im, float* d_work, float lr, void* stream, int64_t prepared,
-    int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y) {
+    int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y, const mmre_ns_opts_t* opts) {
+  if (ns_opts_check(opts)) return MMRE_ERR_ARG;
   if (!d_train_list || !d_head_hrt || !d_tail_hrt || !d_lef_head || !d_rig_head || !d_lef_tail || !d_rig_tail ||
       !d_seeds || !d_batch_h || !d_batch_t || !d_batch_r || !d_batch_y || !d_ticket)
     return MMRE_ERR_ARG;
@@ -2870,5 +3057,25 @@ extern "C" int mmre_ns_step_openke_gen_pipe(
   return step_openke_gen_impl(sa, n_sampler, model, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im,
                               n_ent, n_rel, dim, phase_denom, batch, neg, loss_margin, adv_temperature, regul_rate,
                               d_score, d_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, lr,
-                              (hipStream_t)stream, prepared, d_next_h, d_next_t, d_next_r, d_next_y);
+                              (hipStream_t)stream, prepared, d_next_h, d_next_t, d_next_r, d_next_y, opts);
+}
+
+extern "C" int mmre_ns_step_openke_gen_pipe(
+    const int64_t* d_train_list, int64_t train_total, const int64_t* d_head_hrt, const int64_t* d_tail_hrt,
+    const int64_t* d_rel_hrt, const int64_t* d_lef_head, const int64_t* d_rig_head, const int64_t* d_lef_tail,
+    const int64_t* d_rig_tail, const int64_t* d_lef_rel, const int64_t* d_rig_rel, const float* d_left_mean,
+    const float* d_right_mean, uint64_t* d_seeds, int64_t work_threads, int64_t mode, const int32_t* d_blocks,
+    int64_t n_blocks, int64_t* d_batch_h, int64_t* d_batch_t, int64_t* d_batch_r, float* d_batch_y, int32_t* d_ticket,
+    int model, float model_margin, int use_model_margin, float* d_ent, float* d_ent_im, float* d_rel, float* d_rel_im,
+    int64_t n_ent, int64_t n_rel, int dim, float phase_denom, int64_t batch, int64_t neg, float loss_margin,
+    float adv_temperature, float regul_rate, float* d_score, float* d_loss, float* d_grad_ent, float* d_grad_ent_im,
+    float* d_grad_rel, float* d_grad_rel_im, float* d_work, float lr, void* stream, int64_t prepared,
+    int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y) {
+  return mmre_ns_step_openke_gen_pipe_ex(
+      d_train_list, train_total, d_head_hrt, d_tail_hrt, d_rel_hrt, d_lef_head, d_rig_head, d_lef_tail, d_rig_tail,
+      d_lef_rel, d_rig_rel, d_left_mean, d_right_mean, d_seeds, work_threads, mode, d_blocks, n_blocks, d_batch_h,
+      d_batch_t, d_batch_r, d_batch_y, d_ticket, model, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im,
+      n_ent, n_rel, dim, phase_denom, batch, neg, loss_margin, adv_temperature, regul_rate, d_score, d_loss, d_grad_ent,
+      d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, lr, stream, prepared, d_next_h, d_next_t, d_next_r, d_next_y,
+      nullptr);
 }

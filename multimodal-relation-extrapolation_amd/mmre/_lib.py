@@ -18,6 +18,17 @@ I64 = ctypes.c_int64
 I32 = ctypes.c_int
 F32 = ctypes.c_float
 
+
+class NSOpts(ctypes.Structure):
+    """mmre_ns_opts_t (include/mmre.h): the loss kind, the fused optimizer and Adagrad's state."""
+    _fields_ = [("loss_kind", I32), ("optimizer", I32), ("eps", F32), ("d_sum_ent", P), ("d_sum_ent_im", P),
+                ("d_sum_rel", P), ("d_sum_rel_im", P)]
+
+
+OPTS = ctypes.POINTER(NSOpts)
+LOSS_KINDS = {"margin": 0, "softplus": 1, "sigmoid": 2}
+OPT_SGD, OPT_ADAGRAD = 0, 1
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "mmre_version": (I32, []),
@@ -61,6 +72,7 @@ SIGNATURES = {
     "mmre_sampler_repo": (I32, [P, P, P, I64, I64, I64, P, I64, P, P, P, I64, P, P, P, I64, ctypes.c_uint64, I32,
                                 P, P, P, P]),
     "mmre_sgd_step": (I32, [P, P, P, I32, F32, P]),
+    "mmre_adagrad_step": (I32, [P, P, P, P, I32, F32, F32, P]),
     "mmre_ns_workspace": (I64, [I64, I64]),
     "mmre_ns_forward": (I32, [I32, I32, F32, I32, P, P, P, P, I32, F32, P, P, P, I64, I64, F32, F32, F32, P, P, P,
                               P]),
@@ -86,6 +98,19 @@ SIGNATURES = {
                                        F32, P, P, P, P, P, P, P, P]),
     "mmre_score_rows_backward": (I32, [I32, I32, F32, I32, P, P, P, P, I32, F32, P, P, P, I64, P, P, P, P, P, I64, I64,
                                        P, I64, P]),
+    "mmre_ns_forward_ex": (I32, [I32, I32, F32, I32, P, P, P, P, I32, F32, P, P, P, I64, I64, F32, F32, F32, P, P, P,
+                                 P, OPTS]),
+    "mmre_ns_backward_ex": (I32, [I32, I32, F32, I32, P, P, P, P, I32, F32, P, P, P, I64, I64, F32, F32, F32, P, P, P,
+                                  P, P, P, I64, I64, P, I64, P, OPTS]),
+    "mmre_ns_fused_forward_ex": (I32, [I32, I32, F32, I32, P, P, P, P, I64, I64, I32, F32, P, P, P, I64, I64, F32, F32,
+                                       F32, P, P, P, P, OPTS]),
+    "mmre_ns_fused_grad_ex": (I32, [I32, I32, F32, I32, P, P, P, P, I64, I64, I32, F32, P, P, P, I64, I64, F32, F32,
+                                    F32, P, P, P, P, P, P, P, P, OPTS]),
+    "mmre_ns_fused_grad_sgd_ex": (I32, [I32, I32, F32, I32, P, P, P, P, I64, I64, I32, F32, P, P, P, I64, I64, F32,
+                                        F32, F32, P, P, P, P, P, P, P, F32, P, OPTS]),
+    "mmre_ns_step_openke_gen_pipe_ex": (I32, [P, I64, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, P, I64, P, P, P, P,
+                                              P, I32, F32, I32, P, P, P, P, I64, I64, I32, F32, I64, I64, F32, F32, F32,
+                                              P, P, P, P, P, P, P, F32, P, I64, P, P, P, P, OPTS]),
     "mmre_generator_workspace": (I64, [I64, I32, I32, I32, I32]),
     "mmre_generator_forward": (I32, [P, I32, P, I32, I64, P, P, P, P, I32, P, P, P, P, I32, P, P, P, P, I32, P, P,
                                      F32, I32, F32, P, P, P]),

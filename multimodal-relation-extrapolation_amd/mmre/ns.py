@@ -1,4 +1,7 @@
-"""Fused negative-sampling margin loss (csrc/ns.hip) as a torch.autograd.Function.
+"""Fused negative-sampling loss (csrc/ns.hip) as a torch.autograd.Function: MarginLoss, and with
+loss="softplus" / "sigmoid" OpenKE's SoftplusLoss / SigmoidLoss (SoftplusLoss.py:19-26,
+SigmoidLoss.py:19-26) through the same kernels' shared loss head; with an mmre.optim.Adagrad the
+backward's row owner applies Adagrad's step as it applies SGD's.
 
 forward  = model(data) in 'normal' mode for B*(1+k) rows -> MarginLoss (optionally
            self-adversarial) + regul_rate * regularization, one launch + one fixed-order
@@ -16,7 +19,9 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import call, lib, mark_written, ptr, require_cuda, stream_ptr
+import ctypes
+
+from ._lib import LOSS_KINDS, OPT_ADAGRAD, OPT_SGD, NSOpts, call, lib, mark_written, ptr, require_cuda, stream_ptr
 
 MODEL_IDS = {"transe": 0, "transe_l2": 1, "distmult": 2, "complex": 3, "rotate": 4}
 
@@ -39,6 +44,28 @@ def _scalar_args(spec, batch, neg, loss_margin, adv_t, regul_rate):
     return (spec.model_id, int(spec.norm_flag), spec.model_margin, int(spec.use_model_margin))
 
 
+def _ns_opts(kind: int, adagrad=None):
+    """mmre_ns_opts_t for a loss kind and, optionally, Adagrad's (eps, sums of ent, rel[, ent_im,
+    rel_im]); None for the margin loss without Adagrad (the entry points without _ex)."""
+    if kind == 0 and adagrad is None:
+        return None
+    o = NSOpts(loss_kind=int(kind), optimizer=OPT_SGD)
+    if adagrad is not None:
+        eps, sums = adagrad
+        o.optimizer, o.eps = OPT_ADAGRAD, float(eps)
+        o.d_sum_ent, o.d_sum_rel = sums[0].data_ptr(), sums[1].data_ptr()
+        if len(sums) == 4:
+            o.d_sum_ent_im, o.d_sum_rel_im = sums[2].data_ptr(), sums[3].data_ptr()
+    return o
+
+
+def _call_ex(name, opts, *args):
+    """`name` (opts None: exactly the call made before the options existed) or its _ex twin."""
+    if opts is None:
+        return call(name, *args)
+    return call(name + "_ex", *args, ctypes.byref(opts))
+
+
 class _FusedNS(torch.autograd.Function):
     """Training (the tables need gradients): mmre_ns_fused_forward in the forward (loss,
     scores, and the gradient's slot contributions kept in the workspace), mmre_ns_fused_grad
@@ -48,37 +75,41 @@ class _FusedNS(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ent, rel, ent_im, rel_im, h, t, r, spec, batch, neg, loss_margin, adv_t, regul_rate, events,
-                sgd):
+                sgd, kind=0):
         dev = ent.device
         N = batch * (1 + neg)
         score = torch.empty(N, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         ctx.mark_non_differentiable(score)
         ctx.set_materialize_grads(False)  # no zero-filled gradient for the (non-differentiable) scores
-        ctx.fused = any(ctx.needs_input_grad[:4])
+        # TransE under Softplus / Sigmoid: the rows path (mmre_ns_forward_ex / mmre_ns_backward_ex; the
+        # fused TransE kernel is margin-only), its optimizer step left to optimizer.step()
+        ctx.fused = any(ctx.needs_input_grad[:4]) and not (kind != 0 and spec.model in ("transe", "transe_l2"))
         ctx.has_im = ent_im is not None
         ctx.cfg = (spec, batch, neg, loss_margin, adv_t, regul_rate)
         ctx.sgd = sgd if ctx.fused else None
+        ctx.kind = kind
+        opts = _ns_opts(kind)
         if ctx.fused:
             E, R = int(ent.shape[0]), int(rel.shape[0])
             work = torch.empty(int(lib().mmre_ns_fused_workspace(spec.model_id, int(spec.norm_flag), batch, neg, E, R,
                                                                  spec.dim)), dtype=torch.float32, device=dev)
             if events is not None:
                 events[0].record()
-            call("mmre_ns_fused_forward", spec.model_id, int(spec.norm_flag), spec.model_margin,
-                 int(spec.use_model_margin), ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), E, R, spec.dim,
-                 spec.phase_denom, ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t),
-                 float(regul_rate), ptr(score), ptr(loss), ptr(work), stream_ptr(dev))
+            _call_ex("mmre_ns_fused_forward", opts, spec.model_id, int(spec.norm_flag), spec.model_margin,
+                     int(spec.use_model_margin), ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), E, R, spec.dim,
+                     spec.phase_denom, ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t),
+                     float(regul_rate), ptr(score), ptr(loss), ptr(work), stream_ptr(dev))
             if events is not None:
                 events[1].record()
             ctx.work = work
             ctx.events = events
         else:
             work = torch.empty(int(lib().mmre_ns_workspace(batch, neg)), dtype=torch.float32, device=dev)
-            call("mmre_ns_forward", spec.model_id, int(spec.norm_flag), spec.model_margin,
-                 int(spec.use_model_margin), ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), spec.dim,
-                 spec.phase_denom, ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t),
-                 float(regul_rate), ptr(score), ptr(loss), ptr(work), stream_ptr(dev))
+            _call_ex("mmre_ns_forward", opts, spec.model_id, int(spec.norm_flag), spec.model_margin,
+                     int(spec.use_model_margin), ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), spec.dim,
+                     spec.phase_denom, ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t),
+                     float(regul_rate), ptr(score), ptr(loss), ptr(work), stream_ptr(dev))
         ctx.save_for_backward(ent, rel, ent_im if ent_im is not None else ent, rel_im if rel_im is not None else rel,
                               h, t, r, score)
         return loss[0], score
@@ -86,7 +117,7 @@ class _FusedNS(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_score):
         if g_loss is None:
-            return (None,) * 15
+            return (None,) * 16
         ent, rel, ent_im, rel_im, h, t, r, score = ctx.saved_tensors
         spec, batch, neg, loss_margin, adv_t, regul_rate = ctx.cfg
         if not ctx.has_im:
@@ -104,17 +135,20 @@ class _FusedNS(torch.autograd.Function):
                     ptr(ent_im), ptr(rel), ptr(rel_im), int(ent.shape[0]), int(rel.shape[0]), spec.dim,
                     spec.phase_denom, ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t),
                     float(regul_rate), ptr(score), ptr(gl), ptr(ge), ptr(gei), ptr(gr), ptr(gri), ptr(ctx.work))
-            if ctx.sgd is not None:  # the optimizer's plain SGD step in the same pass (step() skips these tables)
+            if ctx.sgd is not None:  # the optimizer's plain step in the same pass (step() skips these tables)
                 opt, lr, tables = ctx.sgd
-                call("mmre_ns_fused_grad_sgd", *args, float(lr), stream_ptr(dev))
-                mark_written(*tables)  # the SGD update rewrote the parameters in place
+                adagrad = opt.fused_state(tables) if hasattr(opt, "fused_state") else None
+                _call_ex("mmre_ns_fused_grad_sgd", _ns_opts(ctx.kind, adagrad), *args, float(lr), stream_ptr(dev))
+                mark_written(*tables)  # the update rewrote the parameters in place
+                if adagrad is not None:
+                    mark_written(*adagrad[1])
                 opt._fused_applied(tables)
             else:
-                call("mmre_ns_fused_grad", *args, stream_ptr(dev))
+                _call_ex("mmre_ns_fused_grad", _ns_opts(ctx.kind), *args, stream_ptr(dev))
             if ev is not None and len(ev) > 2:
                 ev[3].record()
             ctx.work = ctx.events = ctx.sgd = None
-            return ge, gr, gei, gri, None, None, None, None, None, None, None, None, None, None, None
+            return ge, gr, gei, gri, None, None, None, None, None, None, None, None, None, None, None, None
         # deterministic rows backward (slots + row owner): writes every row, no fills
         E, R = int(ent.shape[0]), int(rel.shape[0])
         ge, gr = torch.empty_like(ent), torch.empty_like(rel)
@@ -122,17 +156,21 @@ class _FusedNS(torch.autograd.Function):
         gri = torch.empty_like(rel_im) if rel_im is not None else None
         nw = int(lib().mmre_rows_backward_workspace(spec.model_id, batch * (1 + neg), E, R, spec.dim))
         work = torch.empty(nw, dtype=torch.float32, device=dev)
-        call("mmre_ns_backward", spec.model_id, int(spec.norm_flag), spec.model_margin, int(spec.use_model_margin),
-             ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), spec.dim, spec.phase_denom, ptr(h), ptr(t), ptr(r),
-             batch, neg, float(loss_margin), float(adv_t), float(regul_rate), ptr(score), ptr(gl), ptr(ge), ptr(gei),
-             ptr(gr), ptr(gri), E, R, ptr(work), nw, stream_ptr(dev))
-        return ge, gr, gei, gri, None, None, None, None, None, None, None, None, None, None, None
+        _call_ex("mmre_ns_backward", _ns_opts(ctx.kind), spec.model_id, int(spec.norm_flag), spec.model_margin,
+                 int(spec.use_model_margin), ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), spec.dim, spec.phase_denom,
+                 ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t), float(regul_rate), ptr(score),
+                 ptr(gl), ptr(ge), ptr(gei), ptr(gr), ptr(gri), E, R, ptr(work), nw, stream_ptr(dev))
+        return ge, gr, gei, gri, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def fused_ns_loss(spec: NSSpec, ent, rel, h, t, r, batch: int, neg: int, loss_margin: float,
                   adv_temperature: float | None = None, regul_rate: float = 0.0, ent_im=None, rel_im=None,
-                  events=None, optimizer=None):
+                  events=None, optimizer=None, loss: str = "margin"):
     """Returns (loss scalar tensor, scores (B*(1+k),)). Differentiable w.r.t. the tables.
+    loss: "margin" (MarginLoss), "softplus" (SoftplusLoss) or "sigmoid" (SigmoidLoss); the latter
+    two ignore loss_margin and weight the negatives by softmax(+T n) under adv_temperature.
+    DistMult / ComplEx / RotatE take the fused kernels for every loss; TransE under softplus /
+    sigmoid takes the rows kernels (no float atomics either; the optimizer's step is then its own).
     events: optional torch.cuda.Events recorded around the C-ABI calls alone (training mode), for
     kernel timing: (start, end) of mmre_ns_fused_forward, and with four, (start, end) of the
     backward's mmre_ns_fused_grad.
@@ -140,20 +178,26 @@ def fused_ns_loss(spec: NSSpec, ent, rel, h, t, r, batch: int, neg: int, loss_ma
     no gradient yet (zero_grad(set_to_none=True): autograd will assign, not accumulate), the
     backward applies the step as well (mmre_ns_fused_grad_sgd) and optimizer.step() skips the
     tables. The parameters afterwards are bit-identical to backward() + step(); p.grad is still
-    written. Otherwise the optimizer is ignored here."""
+    written. Otherwise the optimizer is ignored here. An mmre.optim.Adagrad is taken the same way
+    (DistMult / ComplEx / RotatE): parameters and state["sum"] afterwards are torch's."""
+    if loss not in LOSS_KINDS:
+        raise ValueError(f"fused_ns_loss: loss {loss!r} (one of {sorted(LOSS_KINDS)})")
+    kind = LOSS_KINDS[loss]
     require_cuda(ent, rel, h, t, r, ent_im, rel_im)
     h, t, r = (x.to(torch.int64).contiguous() for x in (h, t, r))
     if ent.dtype != torch.float32 or rel.dtype != torch.float32:
         raise TypeError("fused_ns_loss: float32 tables")
     tables = [x for x in (ent, rel, ent_im, rel_im) if x is not None]
     sgd = None
+    if optimizer is not None and hasattr(optimizer, "fused_state") and spec.model not in OpenKETrainStep.GENERIC:
+        optimizer = None  # Adagrad rides in the generic row owner only; TransE: optimizer.step()
     if optimizer is not None and hasattr(optimizer, "fusable_lr"):
         lr = optimizer.fusable_lr(tables)
         if lr is not None:
             sgd = (optimizer, lr, tables)
     return _FusedNS.apply(ent.contiguous(), rel.contiguous(), None if ent_im is None else ent_im.contiguous(),
                           None if rel_im is None else rel_im.contiguous(), h, t, r, spec, int(batch), int(neg),
-                          float(loss_margin), float(adv_temperature or 0.0), float(regul_rate), events, sgd)
+                          float(loss_margin), float(adv_temperature or 0.0), float(regul_rate), events, sgd, kind)
 
 
 class _ScoreRows(torch.autograd.Function):
@@ -225,14 +269,23 @@ class OpenKETrainStep:
     spec's model margin and phase for RotatE): the generic fused path's kernels -- forward,
     slot records, row owner with SGD -- with the loss reduction and (pipeline=True) the next
     batch's sampler in the row owner's grid: three launches a step instead of the drop-in
-    path's five (sampler, forward, loss reduction, slots, row owner), the same values."""
+    path's five (sampler, forward, loss reduction, slots, row owner), the same values. For these models, loss="softplus" / "sigmoid" is SoftplusLoss /
+    SigmoidLoss (loss_margin ignored) and adagrad=<mmre.optim.Adagrad over the tables> makes the row
+    owner apply Adagrad's step with that optimizer's state (eps, state["sum"]; state["step"]
+    advances per call) instead of SGD's (mmre_ns_step_openke_gen_pipe_ex): the values of
+    fused_ns_loss(..., loss=, optimizer=).backward() + step(), bit for bit."""
 
     GENERIC = ("distmult", "complex", "rotate")
 
     def __init__(self, sampler, spec: NSSpec, ent, rel, batch: int, neg: int, loss_margin: float, lr: float,
                  adv_temperature: float | None = None, regul_rate: float = 0.0, mode: int = 0,
-                 pipeline: bool = True, ent_im=None, rel_im=None):
+                 pipeline: bool = True, ent_im=None, rel_im=None, loss: str = "margin", adagrad=None):
         self.generic = spec.model in self.GENERIC
+        if loss not in LOSS_KINDS:
+            raise ValueError(f"OpenKETrainStep: loss {loss!r} (one of {sorted(LOSS_KINDS)})")
+        if not self.generic and (loss != "margin" or adagrad is not None):
+            raise ValueError("OpenKETrainStep: TransE takes the margin loss and SGD (its fused kernel is margin-only)")
+        self.kind, self.adagrad = LOSS_KINDS[loss], adagrad
         if not self.generic and (spec.model not in ("transe", "transe_l2") or spec.use_model_margin):
             raise ValueError("OpenKETrainStep: TransE without a model margin, DistMult, ComplEx or RotatE")
         if (spec.model == "complex") != (ent_im is not None and rel_im is not None):
@@ -281,13 +334,17 @@ class OpenKETrainStep:
         st = self._state()
         prepared = 1 if (self.pipeline and self._ready is not None and self._ready[0] == st[0]) else 0
         args = self.sampler.step_args(self.B, self.K, self.mode, cur, advance=not prepared)
-        call("mmre_ns_step_openke_gen_pipe", *args, s.model_id, s.model_margin, int(s.use_model_margin), ptr(self.ent),
-             ptr(self.ent_im), ptr(self.rel), ptr(self.rel_im), E, R, s.dim, s.phase_denom, self.B, self.K,
-             self.margin, self.adv, self.regul, ptr(self.score), ptr(self.loss), ptr(self.ge), ptr(self.gei),
-             ptr(self.gr), ptr(self.gri), ptr(self.work), self.lr, stream_ptr(self.ent.device), prepared,
-             ptr(nxt["batch_h"]) if nxt else None, ptr(nxt["batch_t"]) if nxt else None,
-             ptr(nxt["batch_r"]) if nxt else None, ptr(nxt["batch_y"]) if nxt else None)
+        tables = [x for x in (self.ent, self.rel, self.ent_im, self.rel_im) if x is not None]
+        opts = _ns_opts(self.kind, self.adagrad.fused_state(tables) if self.adagrad is not None else None)
+        _call_ex("mmre_ns_step_openke_gen_pipe", opts, *args, s.model_id, s.model_margin, int(s.use_model_margin),
+                 ptr(self.ent), ptr(self.ent_im), ptr(self.rel), ptr(self.rel_im), E, R, s.dim, s.phase_denom, self.B,
+                 self.K, self.margin, self.adv, self.regul, ptr(self.score), ptr(self.loss), ptr(self.ge),
+                 ptr(self.gei), ptr(self.gr), ptr(self.gri), ptr(self.work), self.lr, stream_ptr(self.ent.device),
+                 prepared, ptr(nxt["batch_h"]) if nxt else None, ptr(nxt["batch_t"]) if nxt else None,
+                 ptr(nxt["batch_r"]) if nxt else None, ptr(nxt["batch_y"]) if nxt else None)
         mark_written(self.ent, self.rel, self.ent_im, self.rel_im)
+        if self.adagrad is not None:
+            self.adagrad.count_fused_step(tables)
         self.batch = cur
         if nxt is not None:
             self.sampler.advance(self.B, self.K, self.mode)

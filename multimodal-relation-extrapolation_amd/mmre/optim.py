@@ -3,7 +3,13 @@ HIP launch over every parameter tensor (mmre_sgd_step, csrc/optim.hip) -- the Op
 default optimizer (Trainer.py:82-86, optim.SGD(parameters, lr, weight_decay)) after the fused
 negative-sampling gradient. Any other configuration is torch.optim.SGD's own step; such steps
 are counted in SGD.fallback_steps (reason in SGD.fallback_reason), so a run can show that the
-HIP step was the one that ran."""
+HIP step was the one that ran.
+
+Adagrad: the same contract for torch.optim.Adagrad's plain step (lr_decay 0, weight_decay 0, no
+maximize) -- the optimizer of the reference's DistMult / ComplEx recipes (OpenKE
+examples/train_distmult_WN18RR.py, train_complex_WN18RR.py; Trainer.py:66-72): mmre_adagrad_step,
+or the fused backward's row owner (mmre_ns_fused_grad_sgd_ex). Its state is torch's own
+(state[p]["sum"], state[p]["step"]), so state_dict() stays torch-compatible."""
 from __future__ import annotations
 
 import ctypes
@@ -15,17 +21,8 @@ from ._lib import call, mark_written, stream_ptr
 _MAX_T = 8
 
 
-class SGD(torch.optim.SGD):
-    def _plain(self, group) -> bool:
-        return (group["momentum"] == 0 and group["weight_decay"] == 0 and not group["nesterov"]
-                and not group["maximize"])
-
-    def _eligible(self, group, ps) -> bool:
-        return self._why_not(group, ps) is None
-
-    # steps that took torch's own SGD path instead of mmre_sgd_step, and why (last reason)
-    fallback_steps = 0
-    fallback_reason = None
+class _FusedTables:
+    """What SGD and Adagrad share: the bookkeeping of tables whose step the fused backward applied."""
 
     # ---- fused mode: the fused negative-sampling backward applies this optimizer's step to the
     # embedding tables in its row-owner pass (mmre.ns.fused_ns_loss(..., optimizer=opt)); step()
@@ -81,6 +78,19 @@ class SGD(torch.optim.SGD):
     def zero_grad(self, set_to_none: bool = True):
         self._fused_done = {}
         super().zero_grad(set_to_none=set_to_none)
+
+
+class SGD(_FusedTables, torch.optim.SGD):
+    def _plain(self, group) -> bool:
+        return (group["momentum"] == 0 and group["weight_decay"] == 0 and not group["nesterov"]
+                and not group["maximize"])
+
+    def _eligible(self, group, ps) -> bool:
+        return self._why_not(group, ps) is None
+
+    # steps that took torch's own SGD path instead of mmre_sgd_step, and why (last reason)
+    fallback_steps = 0
+    fallback_reason = None
 
     def _why_not(self, group, ps):
         if not self._plain(group):
@@ -140,4 +150,105 @@ class SGD(torch.optim.SGD):
                 call("mmre_sgd_step", ctypes.cast(params, ctypes.c_void_p), ctypes.cast(grads, ctypes.c_void_p),
                      ctypes.cast(numel, ctypes.c_void_p), n, lr, stream_ptr(chunk[0].device))
                 mark_written(*chunk)  # as torch's in-place SGD update would
+        return loss
+
+
+class Adagrad(_FusedTables, torch.optim.Adagrad):
+    """torch.optim.Adagrad whose plain step is mmre_adagrad_step (one launch, one pass over
+    parameter, gradient and sum instead of the foreach step's five), bit-identical to torch's."""
+
+    # steps that took torch's own Adagrad path instead of mmre_adagrad_step, and why (last reason)
+    fallback_steps = 0
+    fallback_reason = None
+
+    def _plain(self, group) -> bool:
+        # foreach=False (torch's single-tensor step) scales the quotient, not the gradient: other roundings
+        return (group["lr_decay"] == 0 and group["weight_decay"] == 0 and not group["maximize"]
+                and not group.get("differentiable", False) and group.get("foreach") is not False)
+
+    def fusable_lr(self, tables):
+        """As SGD.fusable_lr, and the tables' sums must be float32 device tensors laid out like them."""
+        for t in tables:
+            s = self.state.get(t, {}).get("sum")
+            if s is None or not s.is_cuda or s.dtype != torch.float32 or not s.is_contiguous() or s.shape != t.shape:
+                return None
+        return super().fusable_lr(tables)
+
+    def fused_state(self, tables):
+        """(eps, the tables' sum tensors): what the fused row owner's Adagrad branch needs."""
+        group = next(g for g in self.param_groups if any(p is tables[0] for p in g["params"]))
+        return float(group["eps"]), [self.state[t]["sum"] for t in tables]
+
+    def count_fused_step(self, tables):
+        """A fused step of `tables` outside step() (the one-call training step): sum and the parameters
+        were written by the kernel; state["step"] advances as torch's step would have advanced it."""
+        for t in tables:
+            self.state[t]["step"] += 1
+            mark_written(self.state[t]["sum"])
+
+    def _why_not(self, group, ps):
+        if not self._plain(group):
+            return "lr_decay / weight_decay / maximize / differentiable / foreach=False"
+        for p in ps:
+            if not p.is_cuda or p.dtype != torch.float32 or p.grad.dtype != torch.float32:
+                return "not a float32 device tensor"
+            if p.grad.is_sparse:
+                return "sparse gradient"
+            s = self.state[p]["sum"]
+            if not s.is_cuda or s.dtype != torch.float32 or not s.is_contiguous():
+                return "state sum is not a contiguous float32 device tensor"
+            if not p.is_contiguous() or not p.grad.is_contiguous():
+                return "non-contiguous parameter or gradient"
+            if p.data_ptr() % 16 or p.grad.data_ptr() % 16 or s.data_ptr() % 16:
+                return "parameter, gradient or sum not 16-B aligned (float4 streams)"
+        return None
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        done = getattr(self, "_fused_done", {})
+        self._fused_done = {}
+        late = [k for k, c in done.items() if c > 1]  # the fused backward's own assignment counts once
+        if late:
+            raise RuntimeError("mmre.optim.Adagrad: a table whose Adagrad step the fused backward already applied "
+                               "received more gradient before step() (e.g. gradient accumulation); call zero_grad() "
+                               "between backward passes or build the loss without optimizer= (mmre.ns.fused_ns_loss)")
+        fused = [p for g in self.param_groups for p in g["params"] if id(p) in done]
+        self.count_fused_step(fused)  # their sum and parameters: written by the fused backward
+        work = []
+        for group in self.param_groups:
+            ps = [p for p in group["params"] if p.grad is not None and id(p) not in done]
+            why = self._why_not(group, ps) if ps else None
+            if why is not None:  # torch's own Adagrad step -- counted, not silent -- over what was not fused
+                type(self).fallback_steps += 1
+                type(self).fallback_reason = why
+                saved = [p.grad for p in fused]
+                for p in fused:
+                    p.grad = None  # torch's step skips parameters without a gradient
+                try:
+                    super().step()
+                finally:
+                    for p, g in zip(fused, saved):
+                        p.grad = g
+                return loss
+            work.append((group, ps))
+        for group, ps in work:
+            lr, eps = float(group["lr"]), float(group["eps"])
+            for i in range(0, len(ps), _MAX_T):
+                chunk = ps[i:i + _MAX_T]
+                n = len(chunk)
+                sums = [self.state[p]["sum"] for p in chunk]
+                params = (ctypes.c_void_p * n)(*[p.data_ptr() for p in chunk])
+                grads = (ctypes.c_void_p * n)(*[p.grad.data_ptr() for p in chunk])
+                sumv = (ctypes.c_void_p * n)(*[t.data_ptr() for t in sums])
+                numel = (ctypes.c_int64 * n)(*[p.numel() for p in chunk])
+                call("mmre_adagrad_step", ctypes.cast(params, ctypes.c_void_p), ctypes.cast(grads, ctypes.c_void_p),
+                     ctypes.cast(sumv, ctypes.c_void_p), ctypes.cast(numel, ctypes.c_void_p), n, lr, eps,
+                     stream_ptr(chunk[0].device))
+                mark_written(*chunk, *sums)  # as torch's in-place update would
+                for p in chunk:
+                    self.state[p]["step"] += 1
         return loss

@@ -1,9 +1,11 @@
 """Trainer (OpenKE/openke/config/Trainer.py:16-134): same constructor, setters and run() loop.
 Batches arrive from the GPU sampler already on the device; the strategy's forward/backward is
-the fused HIP loss; plain SGD runs inside the fused backward (mmre.optim.SGD). For TransE +
-MarginLoss + SGD with 'normal' sampling (TransE, DistMult, ComplEx, RotatE), run() takes the
+the fused HIP loss; plain SGD and plain Adagrad run inside the fused backward (mmre.optim.SGD,
+mmre.optim.Adagrad). For MarginLoss + SGD with 'normal' sampling (TransE, DistMult, ComplEx,
+RotatE), and for SoftplusLoss / SigmoidLoss with SGD or Adagrad on DistMult, ComplEx and RotatE
+(the reference's examples/train_distmult_WN18RR.py and train_complex_WN18RR.py), run() takes the
 whole step as one C-ABI call (mmre.ns.OpenKETrainStep: same batches, losses and parameters, bit
-for bit)."""
+for bit). TransE under SoftplusLoss / SigmoidLoss trains per batch through the fused rows path."""
 import os
 
 import numpy as np
@@ -55,7 +57,8 @@ class Trainer(object):
         p = self.model.parameters()
         m = (self.opt_method or "sgd").lower()
         if m == "adagrad":
-            return optim.Adagrad(p, lr=self.alpha, lr_decay=self.lr_decay, weight_decay=self.weight_decay)
+            from mmre.optim import Adagrad  # plain Adagrad: one HIP launch / the fused backward (torch's step otherwise)
+            return Adagrad(p, lr=self.alpha, lr_decay=self.lr_decay, weight_decay=self.weight_decay)
         if m == "adadelta":
             return optim.Adadelta(p, lr=self.alpha, weight_decay=self.weight_decay)
         if m == "adam":
@@ -102,18 +105,24 @@ class Trainer(object):
     def _one_call_step(self):
         """(mmre.ns.OpenKETrainStep, its optimizer group) when the whole step -- the loader's
         Base.cpp sampling, NegativeSampling + MarginLoss on TransE, DistMult, ComplEx or RotatE,
-        plain SGD -- can run as one C-ABI call (mmre_ns_step_openke_pipe for TransE,
-        mmre_ns_step_openke_gen_pipe for the others); else None (train_one_step)."""
+        plain SGD; or SoftplusLoss / SigmoidLoss with plain SGD or Adagrad on DistMult, ComplEx or
+        RotatE -- can run as one C-ABI call (mmre_ns_step_openke_pipe for TransE,
+        mmre_ns_step_openke_gen_pipe[_ex] for the others); else None (train_one_step)."""
         try:
             from ..data.TrainDataLoader import TrainDataLoader
             from ..module.loss.MarginLoss import MarginLoss
+            from ..module.loss.SigmoidLoss import SigmoidLoss
+            from ..module.loss.SoftplusLoss import SoftplusLoss
             from ..module.strategy.NegativeSampling import NegativeSampling
             from mmre.ns import OpenKETrainStep
         except ImportError:
             return None
         m, dl = self.model, self.data_loader
-        if not (isinstance(m, NegativeSampling) and isinstance(m.loss, MarginLoss) and isinstance(dl, TrainDataLoader)):
+        if not (isinstance(m, NegativeSampling) and isinstance(m.loss, (MarginLoss, SoftplusLoss, SigmoidLoss))
+                and isinstance(dl, TrainDataLoader)):
             return None
+        hinge = isinstance(m.loss, MarginLoss)
+        adagrad = self.optimizer if hasattr(self.optimizer, "fused_state") else None
         if m.l3_regul_rate != 0 or dl.sampling_mode != "normal" or dl.negative_rel != 0 or m.batch_size != dl.batch_size:
             return None
         if not (hasattr(m.model, "ns_spec") and hasattr(m.model, "_tables")):
@@ -121,6 +130,8 @@ class Trainer(object):
         spec = m.model.ns_spec()
         ent, rel, ent_im, rel_im = m.model._tables()
         generic = spec.model in OpenKETrainStep.GENERIC
+        if not generic and (not hinge or adagrad is not None):
+            return None  # TransE's fused kernel: margin loss and SGD only (train_one_step: the rows path)
         if generic:
             # DistMult / ComplEx / RotatE: mmre_ns_step_openke_gen_pipe (the generic kernels' shapes)
             if (spec.model == "complex") != (ent_im is not None and rel_im is not None):
@@ -137,8 +148,15 @@ class Trainer(object):
             return None
         group = next(g for g in self.optimizer.param_groups if any(p is ent for p in g["params"]))
         margin, adv = m.loss.fused_args()
-        step = OpenKETrainStep(dl.sampler, spec, ent, rel, dl.batch_size, dl.negative_ent, margin, float(group["lr"]),
-                               adv_temperature=adv, regul_rate=m.regul_rate, ent_im=ent_im, rel_im=rel_im)
+        if hinge and adagrad is None:
+            step = OpenKETrainStep(dl.sampler, spec, ent, rel, dl.batch_size, dl.negative_ent, margin,
+                                   float(group["lr"]), adv_temperature=adv, regul_rate=m.regul_rate, ent_im=ent_im,
+                                   rel_im=rel_im)
+        else:
+            kind, margin = ("margin", margin) if hinge else (margin, 0.0)  # (kind, adv): no margin
+            step = OpenKETrainStep(dl.sampler, spec, ent, rel, dl.batch_size, dl.negative_ent, margin,
+                                   float(group["lr"]), adv_temperature=adv, regul_rate=m.regul_rate, ent_im=ent_im,
+                                   rel_im=rel_im, loss=kind, adagrad=adagrad)
         return step, group
 
     def set_model(self, model):

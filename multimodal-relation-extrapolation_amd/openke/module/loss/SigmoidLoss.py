@@ -27,3 +27,8 @@ class SigmoidLoss(Loss):
 
     def predict(self, p_score, n_score):
         return self.forward(p_score, n_score).cpu().data.numpy()
+
+    # fused-kernel parameters (strategy.NegativeSampling: mmre.ns.fused_ns_loss(..., loss=kind)); unlike
+    # MarginLoss.fused_args there is no margin, so the first entry is the loss kind
+    def fused_args(self):
+        return "sigmoid", (float(self.adv_temperature.item()) if self.adv_flag else None)
