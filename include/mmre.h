@@ -193,7 +193,21 @@ int mmre_link_sweep_l1q(int pred_kind, float margin, const float* d_ent_km, cons
  * for an entity slice). d_work: mmre_link_evaluate_l1q_workspace(dim, e_pad, q_pad) bytes,
  * ZEROED before the first call (it holds grid tickets; every call leaves them zero).
  * d_undecided_q (NULL or n_query uint32): per query, the pairs the filter left undecided and
- * rescored with the canonical chain (the relation-sharded partition's cost calibration). */
+ * rescored with the canonical chain (the relation-sharded partition's cost calibration).
+ * The group partition also shapes the sweep: the integer filter's code sweep runs once per
+ * SWEEP ROW -- a group, cut into runs of at most 8 members -- and ranks every (row, entity) score
+ * against each member's own threshold. Contract: d_grp_qoff (n_groups + 1 ascending offsets,
+ * 0 .. n_query) and d_grp_q (a permutation of 0 .. n_query - 1) partition the queries, and the
+ * members of a group share (mode, r, anchor), hence a bit-identical query vector. Results --
+ * counts, the undecided record, d_undecided_q -- are the same for every such partition: any
+ * group order, any group sizes (one query per group; one group holding every query of a key;
+ * groups beyond 8 members). Speed is not: a 128-row tile costs its largest row's members, so
+ * groups sorted by descending size and capped at 8 (FilterIndex.groups(order="size",
+ * max_group=8)) sweep fastest. Where grouping would not pay -- the rows' upper bound
+ * n_groups + n_query / 8 leaves resident workgroups without a unit, or exceeds 0.6 n_query
+ * (little duplication, or one query per group) -- the call sweeps once per query, with the
+ * launches of mmre_link_sweep_l1q. Queries whose
+ * vectors differ must not share a group (their counts would be the first member's). */
 int64_t mmre_link_evaluate_l1q_workspace(int dim, int64_t e_pad, int64_t q_pad);
 int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t n_ent, const float* d_rel, int64_t n_rel,
                            int dim, const int64_t* d_qh, const int64_t* d_qr, const int64_t* d_qt,

@@ -18,6 +18,9 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <tuple>
 #include <type_traits>
 
 #include "mmre_common.h"
@@ -485,6 +488,14 @@ struct L1Q {
   int64_t fin_n;           // on it -- every workgroup's slice when the gate is shut, the last workgroup's
   uint32_t* fin_ticket;    // pass after the sweep when it is open (fin_counts nullptr: a separate launch)
   uint32_t* wq;            // dynamic unit scheduling: one zeroed work counter per XCD group (nullptr: static ranges)
+  // grouped sweep (the fused evaluation; k_eval_prep's row map): sweep row -> its first member's
+  // position in grp_q and its member count; per row tile the largest count; [0] rows, [1] rows
+  // padded to whole tiles. q_l1c is then per ROW, and the code planes hold one column per row.
+  const int32_t* row_off;
+  const int32_t* row_cnt;
+  const int32_t* grp_q;
+  const int32_t* tile_m;
+  const int32_t* n_rows;
 };
 // The sweeps' dynamic-scheduling work counters (L1Q::wq): one per XCD group, each on a 128-B
 // line of its own -- the second half of an undecided-pair counter slot (L1Q_SLOT_STRIDE bytes
@@ -525,11 +536,14 @@ __device__ __forceinline__ void l1_int_thresholds(float th, float l1c, float l1d
   t_span = to > ts ? to - ts : 0u;
 }
 
+// (U float4 pairs in flight per round: 5, or 3 inside the grouped sweep's slot loop, where the
+// tile's 64 accumulators stay live across the rescoring: 4 and 5 spilled 16 VGPRs there)
+template <int U = 5>
 __device__ __forceinline__ float l1_exact_rows(const float* __restrict__ q, const float* __restrict__ e, int kt) {
   const float4* q4 = reinterpret_cast<const float4*>(q);
   const float4* e4 = reinterpret_cast<const float4*>(e);
   float acc = 0.0f;
-#pragma unroll 5
+#pragma unroll U
   for (int k = 0; k < kt / 4; ++k) {
     const float4 a = q4[k], b = e4[k];
     acc = acc + fabsf(a.x - b.x);
@@ -961,21 +975,42 @@ struct BlockMap {
 // counts stay in registers until the workgroup moves to the next query tile.
 // LDS of one VALU-sweep workgroup. A struct declared once in the kernel, so that the L1
 // filter's kernel and its f32 fallback path (the same kernel, one uniform branch) share it.
-template <int NPL, bool TC, bool LIST>
-struct ValuSmem {
+// Grouped sweep (the fused evaluation, GS > 0): a sweep row is one query VECTOR shared by up to GS
+// member queries; per member slot and row of the tile, the member's integer thresholds, its query
+// id (-1: no member) and its count accumulator (flushed when the workgroup leaves the row tile).
+// Single-buffered: the flush / reload sits between two workgroup barriers. An empty base for
+// GS = 0, so the ungrouped instantiations keep their LDS to the byte.
+template <int GS>
+struct ValuSmemGrp {
+  uint32_t g_ts[GS][TQ];
+  uint32_t g_tw[GS][TQ];
+  int32_t g_mq[GS][TQ];
+  uint32_t g_acc[GS][TQ];
+};
+template <>
+struct ValuSmemGrp<0> {};
+constexpr int L1Q_GS = 8;  // member slots per sweep row: 8 KB + 2 KB per slot = 36 KB, four workgroups per CU
+// The grouped sweep runs when the host's bound on the sweep rows is at most this share of the
+// queries (mmre_link_evaluate_l1q). C2, 1-unit claims: rows at 0.373 / 0.448 / 0.620 / 1.0 of the
+// queries (caps 8 / 4 / 2 / 1) 0.709 / 0.807 / 0.915 / 1.268 ms against the ungrouped 0.980: the
+// break-even is near 0.69 of the true rows, which the bound overstates by up to 1/8.
+constexpr double L1Q_GROUP_FRAC = 0.6;
+
+template <int NPL, bool TC, bool LIST, int GS = 0>
+struct ValuSmem : ValuSmemGrp<GS> {
   float4 sq[2][NPL][KC][TQ / 4];
   float4 se[2][NPL][KC][TE / 4];
-  float s_thr[2][TQ];
-  int32_t s_true[2][TQ];
+  float s_thr[2][GS ? 1 : TQ];
+  int32_t s_true[2][GS ? 1 : TQ];
   int32_t s_rel[2][TC ? TQ : 1];
   int8_t s_mode[2][TC ? TQ : 1];
   // per-thread counters (off the VGPR budget); 16-bit with type constraints, so that the wave
   // lists fit beside them at four workgroups per CU (a thread adds <= 8 per unit and row; the
   // sweep flushes every unit where a query tile could hold more than 8,190 of a workgroup's units)
-  std::conditional_t<TC, uint16_t, int32_t> s_cnt[TC ? 2 : 1][8][NT];
+  std::conditional_t<TC, uint16_t, int32_t> s_cnt[TC ? 2 : 1][GS ? 1 : 8][GS ? 1 : NT];
   uint32_t s_unc[NT / 64];           // undecided pairs per wave (the L1 filter's counter)
-  uint32_t s_ts[2][TQ];              // L1 filter, prediction = score: per query row, the integer
-  uint32_t s_tw[2][TQ];              // thresholds t_sure and t_out - t_sure (load_meta)
+  uint32_t s_ts[2][GS ? 1 : TQ];     // L1 filter, prediction = score: per query row, the integer
+  uint32_t s_tw[2][GS ? 1 : TQ];     // thresholds t_sure and t_out - t_sure (load_meta)
   int s_unit;                        // dynamic scheduling: the unit after the one being swept
   // type constraints: per unit (two in flight, by unit parity), the type words of its 128 query
   // rows over its 128 entity columns -- words 0, 2, 1, 3 of the tile, so a thread's two words
@@ -987,9 +1022,9 @@ struct ValuSmem {
 // The sweep body. Counts go to the raw columns only (counts[0][q], counts[2][q]); the filtered
 // columns (initialised to minus the listed entities that beat the truth by the truth pass)
 // receive them in k_counts_finalize, one coalesced pass after the sweep (half the atomics).
-template <int OP, bool TC, bool STORE, int PK, int NPL, int DYNC>
+template <int OP, bool TC, bool STORE, int PK, int NPL, int DYNC, int GS = 0>
 __device__ __forceinline__ void sweep_valu_body(
-    ValuSmem<NPL, TC, (OP == 5 || OP == 6)>& sm, const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent,
+    ValuSmem<NPL, TC, (OP == 5 || OP == 6), GS>& sm, const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent,
     const float* __restrict__ q_km, int64_t q_pad, int64_t n_query, int kp, int n_et, int e_base, int n_groups,
     int pred_kind, float margin, const float* __restrict__ thr, const int32_t* __restrict__ qtrue,
     const int64_t* __restrict__ qr, const int8_t* __restrict__ qmode, const uint32_t* __restrict__ type_head,
@@ -1000,6 +1035,10 @@ __device__ __forceinline__ void sweep_valu_body(
   constexpr bool L1F = OP == 5 || OP == 6;  // TransE L1's integer filter (16- / 8-bit codes)
   constexpr bool w8 = OP == 6;
   constexpr bool FAST = (OP == 2 || L1F) && !STORE;
+  // grouped sweep: one SAD chain per sweep row (a query vector), ranked against each member's
+  // thresholds in turn (the slot loop of the epilogue); see ValuSmemGrp and k_eval_prep's row map
+  constexpr bool GRP = GS > 0;
+  static_assert(!GRP || (L1F && PK == 0 && !TC && !STORE), "the grouped sweep is the plain integer filter's");
   auto& sq = sm.sq;
   auto& se = sm.se;
   auto& s_thr = sm.s_thr;
@@ -1022,7 +1061,9 @@ __device__ __forceinline__ void sweep_valu_body(
   // rescoring of undecided pairs) balance themselves instead of leaving a tail of workgroups.
   const int grp = blockIdx.x % n_groups, gmem = blockIdx.x / n_groups;
   const int per_grp = gridDim.x / n_groups;
-  const UnitMap um(grp, n_groups, (int)(q_pad / TQ), n_et);
+  // (grouped: the row tiles, known on the device only)
+  const int n_qt = GRP ? __builtin_amdgcn_readfirstlane(l1.n_rows[GRP ? 1 : 0]) / TQ : (int)(q_pad / TQ);
+  const UnitMap um(grp, n_groups, n_qt, n_et);
   const int nkc = kp / KC;
   // (compiled per mode and chunk: a runtime choice between the modes, or a runtime chunk size,
   // kept values of both live across the loop -- 160-168 B of scratch per lane; the host passes
@@ -1081,6 +1122,57 @@ __device__ __forceinline__ void sweep_valu_body(
         s_mode[slot][tid] = v ? qmode[q] : 0;
       }
     }
+  };
+
+  // Grouped: the row tile's member slots. Entry idx = slot * TQ + row is always thread idx % NT's
+  // (here and in the flush), so reload and flush need no barrier between them. A slot without a
+  // member (or a padding row) gets t_sure = t_span = 0: it neither counts nor lists a pair.
+  // Returns the tile's slot count (uniform).
+  auto load_meta_grp = [&](int qtile) -> int {
+    int m = 0;
+    if constexpr (GRP) {
+      const int tid = vgpr_opaque(threadIdx.x);
+      m = min(__builtin_amdgcn_readfirstlane(l1.tile_m[qtile]), GS);
+      const bool tight = w8 && l1.q_l1c != nullptr;
+      const int ktm = sgpr_opaque(l1.kt);
+      const float md = __uint_as_float(sgpr_opaque(__float_as_uint(l1d)));
+      const float mf = (float)(ktm + 4) * 0x1p-23f * (1.0f + 0x1p-8f);  // = l1f
+      const float mc = __builtin_fmaf((float)ktm * 1.03f, md, 0x1p-120f);  // = l1c
+      const uint32_t om2 = tight ? 2u * l1.hdr[3] : 0u;
+      // thread t: row t % TQ, slots t / TQ + 2 u -- entry t + u NT. Three dependent rounds of
+      // loads for all of them at once (the row's map entry and error sum; its members' ids; their
+      // thresholds), not a chain per entry: the workgroup waits here once per row tile.
+      static_assert(NT == 2 * TQ && GS % 2 == 0, "two slots' rows per pass");
+      const int r = tid % TQ, s0 = tid / TQ;
+      const int64_t row = (int64_t)qtile * TQ + r;
+      const int cnt = l1.row_cnt[row];
+      const int64_t off = l1.row_off[row];
+      const float rc = tight ? l1.q_l1c[row] : 0.0f;
+      int q[GS / 2];
+      float th[GS / 2];
+#pragma unroll
+      for (int u = 0; u < GS / 2; ++u) {
+        q[u] = -1;
+        if (s0 + 2 * u < cnt) {
+          const int qq = l1.grp_q[off + s0 + 2 * u];
+          q[u] = (uint32_t)qq < (uint32_t)n_query ? qq : -1;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < GS / 2; ++u) th[u] = q[u] >= 0 ? thr[q[u]] : -INFINITY;
+#pragma unroll
+      for (int u = 0; u < GS / 2; ++u) {
+        const int sl = s0 + 2 * u;
+        if (sl < m) {
+          uint32_t t_sure, t_span;
+          l1_int_thresholds(th[u], tight ? (q[u] >= 0 ? rc : 0.0f) + 0x1p-120f : mc, md, mf, om2, t_sure, t_span);
+          sm.g_ts[GRP ? sl : 0][r] = t_sure;
+          sm.g_tw[GRP ? sl : 0][r] = t_span;
+          sm.g_mq[GRP ? sl : 0][r] = q[u];
+        }
+      }
+    }
+    return m;
   };
 
   const int srow = tid >> 5, sc4 = tid & 31;
@@ -1160,10 +1252,14 @@ __device__ __forceinline__ void sweep_valu_body(
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) accp[i][j] = f32x2{0.0f, 0.0f};
+  if constexpr (GRP) {
+    for (int idx = tid; idx < GS * TQ; idx += NT) (&sm.g_acc[0][0])[idx] = 0u;
+  } else {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    s_cnt[0][i][tid] = 0;
-    if constexpr (TC) s_cnt[TC ? 1 : 0][i][tid] = 0;
+    for (int i = 0; i < 8; ++i) {
+      s_cnt[0][i][tid] = 0;
+      if constexpr (TC) s_cnt[TC ? 1 : 0][i][tid] = 0;
+    }
   }
   if (L1F && tid < NT / 64) sm.s_unc[tid] = 0u;
   // L1 filter: the wave's undecided pairs are appended to its LDS list (ballot order, no
@@ -1194,11 +1290,18 @@ __device__ __forceinline__ void sweep_valu_body(
       if (l1.guard) atomicAdd(l1.guard, 1u);
       ok = false;
     }
+    if constexpr (GRP) {
+      // grouped: a member's own truth is skipped here (the slot loop keeps no truth ids in LDS),
+      // and the pairs are counted here, after the skip
+      if (ok && e + e_base == qtrue[q]) ok = false;
+      n_listed += (uint32_t)__builtin_popcountll(__ballot(ok));
+    }
     bool beat = false;
     if (ok) {
       if (l1.und_q) atomicAdd(&l1.und_q[q], 1u);
       const float th = thr[q];
-      const float sx = l1_exact_rows(l1.q_rows + q * (int64_t)l1.kt, l1.ent_rows + (int64_t)(e + e_base) * l1.kt, l1.kt);
+      const float sx = l1_exact_rows<GRP ? 3 : 5>(l1.q_rows + q * (int64_t)l1.kt,
+                                                  l1.ent_rows + (int64_t)(e + e_base) * l1.kt, l1.kt);
       beat = pred(sx) < th;
       if constexpr (TC) {
         const uint32_t* tm = qmode[q] == MMRE_HEAD_BATCH ? type_head : type_tail;
@@ -1230,7 +1333,9 @@ __device__ __forceinline__ void sweep_valu_body(
   // the L1 filter's code-width word (L1Q_CODES8 / _CODES16 / _F32: which of the gated sweeps
   // counts), in flight with the stage
   const uint32_t fb_flag = L1F ? l1.hdr[1] : 0u;
-  load_meta(cur_qt, 0);
+  int cur_m = 0;  // grouped: the row tile's member slots (uniform)
+  if constexpr (GRP) cur_m = load_meta_grp(cur_qt);
+  else load_meta(cur_qt, 0);
   gload();
   swrite(0);
   __syncthreads();
@@ -1335,7 +1440,99 @@ __device__ __forceinline__ void sweep_valu_body(
           const int sh = (te & 7) * 4;
           return ((w.x >> sh) & 15u) | (((w.y >> sh) & 15u) << 4);
         };
-        if constexpr (FAST) {
+        if constexpr (GRP) {
+          // Grouped: the tile's integer scores are ranked once per member slot -- the whole-tile
+          // pass below (four VALU per pair) against that slot's thresholds; the last entity tile
+          // adds its column test. No truth test in either: no pair below t_sure is a truth
+          // (S_int < t_sure proves S < th), and the rescoring skips a member's own truth. Per slot
+          // the thread's 8 row counts (<= 8 each) are packed four to a dword, summed over the 16
+          // te lanes of the row (one DPP row: 16 x 8 <= 128 fits a byte; 8 cross-lane adds), and
+          // lane te < 8 adds row te's sum into the slot's LDS accumulator -- one owner per (slot,
+          // row) in the workgroup, so a plain read-modify-write (the flush to counts[], shared with
+          // the other workgroups, is one global atomic per non-zero (slot, row) and row tile).
+          const bool whole = ebase + TE <= n_ent;  // uniform
+          int2* wl = sm.s_pairs[tid >> 6];
+          const int lane = tid & 63;
+          for (int s = 0; s < cur_m; ++s) {  // uniform bound
+            uint32_t unc[2] = {0u, 0u}, pk[2] = {0u, 0u};
+            if (whole) {
+#pragma unroll
+              for (int i = 0; i < 8; ++i) {
+                const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
+                const uint32_t t_sure = sm.g_ts[GRP ? s : 0][ql], t_span = sm.g_tw[GRP ? s : 0][ql];
+                int c = 0;
+                uint32_t u = unc[i >> 2];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                  const uint32_t si = __float_as_uint(acc[i][j]);
+                  const uint32_t d = si - t_sure;
+                  c += si < t_sure;
+                  u = u + u + (uint32_t)(d < t_span);
+                }
+                unc[i >> 2] = u;
+                pk[i >> 2] |= (uint32_t)c << (8 * (i & 3));
+              }
+            } else {
+#pragma unroll
+              for (int i = 0; i < 8; ++i) {
+                const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
+                const uint32_t t_sure = sm.g_ts[GRP ? s : 0][ql], t_span = sm.g_tw[GRP ? s : 0][ql];
+                int c = 0;
+                uint32_t u = unc[i >> 2];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                  const int e = (int)ebase + ((j < 4) ? te * 4 + j : 64 + te * 4 + (j - 4));
+                  const bool valid = e < n_ent;
+                  const uint32_t si = __float_as_uint(acc[i][j]);
+                  c += (si < t_sure) & valid;
+                  u = u + u + (uint32_t)((si - t_sure < t_span) & valid);
+                }
+                unc[i >> 2] = u;
+                pk[i >> 2] |= (uint32_t)c << (8 * (i & 3));
+              }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {  // sum over the row's 16 lanes: xor 1, xor 2, half mirror, mirror
+              uint32_t v = pk[h];
+              v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
+              v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);
+              v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);
+              v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);
+              pk[h] = v;
+            }
+            if (te < 8) {
+              const uint32_t cnt = ((te < 4 ? pk[0] : pk[1]) >> (8 * (te & 3))) & 255u;
+              const int ql = (te < 4) ? tq * 4 + te : 64 + tq * 4 + (te - 4);
+              if (cnt) sm.g_acc[GRP ? s : 0][ql] += cnt;
+            }
+            for (;;) {  // uniform: one undecided pair per lane and round into the wave's list
+              const bool has = (unc[0] | unc[1]) != 0u;
+              const uint64_t bal = __ballot(has);
+              if (bal == 0) break;
+              if (has) {
+                const int h = unc[0] ? 0 : 1;
+                const int p = __builtin_clz(unc[h]);  // pair p = (i & 3) * 8 + j sits at bit 31 - p
+                unc[h] &= ~(0x80000000u >> p);
+                const int i = h * 4 + (p >> 3), j = p & 7;
+                const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
+                const int e = (int)ebase + ((j < 4) ? te * 4 + j : 64 + te * 4 + (j - 4));
+                // list_n < 64 at the top of every round and a round appends <= 64: pos < 128
+                const int pos = list_n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
+                                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                wl[pos] = make_int2(sm.g_mq[GRP ? s : 0][ql], e);
+              }
+              list_n += __builtin_popcountll(bal);
+              if (list_n >= 64) {  // a full batch
+                list_n -= 64;
+                rescore(wl[list_n + lane], true);
+              }
+            }
+          }
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[i][j] = 0.0f;
+        } else if constexpr (FAST) {
           if constexpr (OP == 2) {  // unpack the pair layout (register renames) and restart it
 #pragma unroll
             for (int i = 0; i < 8; ++i)
@@ -1565,6 +1762,21 @@ __device__ __forceinline__ void sweep_valu_body(
         int next_qt = cur_qt, next_et = cur_et;
         if (!last) um.at(unit_next, next_qt, next_et);
         // (TC: 16-bit counters -- flush every unit where a group's query tile could exceed them)
+        if constexpr (GRP) {
+          if (last || next_qt != cur_qt) {  // uniform: flush this row tile's member counts
+            __syncthreads();  // every wave's adds of this unit are in, and its threshold reads done
+            const int tid = vgpr_opaque(threadIdx.x);
+            for (int idx = tid; idx < cur_m * TQ; idx += NT) {
+              const uint32_t c = (&sm.g_acc[0][0])[idx];
+              if (c) {
+                const int q = (&sm.g_mq[0][0])[idx];
+                if (q >= 0) atomicAdd(&counts[q], (int)c);
+                (&sm.g_acc[0][0])[idx] = 0u;
+              }
+            }
+            if (!last) cur_m = load_meta_grp(next_qt);  // visible after the stage's barrier below
+          }
+        } else
         if (last || next_qt != cur_qt || (TC && n_et > 8 * 8190)) {  // uniform: flush this query tile's counts
           const int tid = vgpr_opaque(threadIdx.x);  // (see load_meta)
           const int tq = tid >> 4, te = tid & 15;
@@ -1625,7 +1837,7 @@ __device__ __forceinline__ void sweep_valu_body(
   }
 }
 
-template <int OP, bool TC, bool STORE, int PK, int DYNC = 0>
+template <int OP, bool TC, bool STORE, int PK, int DYNC = 0, int GS = 0>
 __global__ __launch_bounds__(NT, (OP == 2) ? 3 : 4) void k_sweep_valu(
     const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent, const float* __restrict__ q_km,
     int64_t q_pad, int64_t n_query, int kp, int n_et, int e_base, int n_groups, int pred_kind, float margin,
@@ -1634,7 +1846,7 @@ __global__ __launch_bounds__(NT, (OP == 2) ? 3 : 4) void k_sweep_valu(
     const uint32_t* __restrict__ type_tail, int64_t type_words, int32_t* __restrict__ counts,
     float* __restrict__ scores, L1Q l1) {
   constexpr int NPL = (OP == 2) ? 2 : 1;
-  __shared__ ValuSmem<NPL, TC, (OP == 5 || OP == 6)> sm;
+  __shared__ ValuSmem<NPL, TC, (OP == 5 || OP == 6), GS> sm;
   // the L1 filter's fallback (k_l1q_quant decided that the codes are too coarse for these
   // planes -- one outlier value sets the code step for everything): the filter launch does
   // nothing (sweep_valu_body tests the flag once its first stage is loaded, so the flag's load
@@ -1653,7 +1865,7 @@ __global__ __launch_bounds__(NT, (OP == 2) ? 3 : 4) void k_sweep_valu(
       return;
     }
   }
-  sweep_valu_body<OP, TC, STORE, PK, NPL, DYNC>(sm, ent_km, e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base,
+  sweep_valu_body<OP, TC, STORE, PK, NPL, DYNC, GS>(sm, ent_km, e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base,
                                           n_groups, pred_kind, margin, thr, qtrue, qr, qmode, type_head, type_tail,
                                           type_words, counts, scores, l1);
   if (l1.gate != nullptr && l1.fin_counts != nullptr) {
@@ -3193,7 +3405,7 @@ __global__ void k_bf3_stats(const uint32_t* __restrict__ hdr, unsigned long long
 // ---------------------------------------------------------------- launch ---
 // Resident workgroups of a persistent sweep: the occupancy API's blocks per CU (capped at 4,
 // the VGPR-limited residency of a 256-thread group at <= 128 VGPRs) x the device's CUs.
-static int resident_groups(const void* kernel, int threads) {
+static int resident_groups_query(const void* kernel, int threads) {
   int dev = 0, cus = 256, per = 0;
   if (hipGetDevice(&dev) == hipSuccess) {
     int v = 0;
@@ -3202,6 +3414,18 @@ static int resident_groups(const void* kernel, int threads) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, threads, 0) != hipSuccess || per <= 0) per = 1;
   if (per > 4) per = 4;
   return cus * per;
+}
+// (queried once per kernel and device: the fused evaluation asks on every call)
+static int resident_groups(const void* kernel, int threads) {
+  static std::mutex mu;
+  static std::map<std::tuple<const void*, int, int>, int> cache;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  std::lock_guard<std::mutex> lock(mu);
+  const auto key = std::make_tuple(kernel, threads, dev);
+  auto it = cache.find(key);
+  if (it == cache.end()) it = cache.emplace(key, resident_groups_query(kernel, threads)).first;
+  return it->second;
 }
 
 static int launch_finalize(hipStream_t st, int32_t* counts, int64_t n_query, bool tc) {
@@ -3310,6 +3534,45 @@ static int launch_valu(bool tc, bool store, hipStream_t st, const float* ent_km,
   return finalize ? launch_finalize(st, counts, n_query, tc) : MMRE_OK;
 }
 
+// The grouped integer-filter sweep of the fused evaluation (k_sweep_valu<.., GS = L1Q_GS>): work
+// units are (row tile) x (entity tile), the row tiles known on the device only -- the host sizes
+// the grid from rows_max, an upper bound (workgroups past the last unit leave at once).
+// Units per claim, C2 N = 1 (103 row tiles x 111 entity tiles over 1,024 workgroups, ~11 units
+// each, heavy tiles first), per evaluation: chunks of 1 / 2 / 4 units (MMRE_SWEEP_CHUNK) 0.705 /
+// 0.733 / 0.969 ms -- with so few units per workgroup a 4-unit claim is a third of its share, and
+// the last claims leave a long tail (the ungrouped sweep's ~30 units each favoured 4: see
+// sweep_valu_body). The host picks 1 below 16 units per workgroup, as launch_valu_one does.
+template <int OP>
+static int launch_valu_grp(hipStream_t st, const float* ent_km, int64_t e_pad, int64_t n_ent, int n_et, int e_base,
+                           const float* q_km, int64_t q_pad, int64_t n_query, int kp, const float* thr,
+                           const int32_t* qtrue, int32_t* counts, L1Q l1, int64_t rows_max) {
+  const bool dyn = l1.wq != nullptr && kp / KC >= 2;
+  if (!dyn) l1.wq = nullptr;
+  int g = resident_groups((const void*)k_sweep_valu<OP, false, false, 0, 1, L1Q_GS>, NT);
+  if (!dyn) g *= 16;  // static ranges: short ones (launch_valu_one)
+  const int64_t q_tiles = (rows_max + TQ - 1) / TQ;
+  const int64_t units = (n_et >= 8) ? 8 * q_tiles * ((n_et + 7) / 8) : q_tiles * n_et;
+  if (units < g) g = (int)(units > 0 ? units : 1);
+  int chunk = 0;
+  if (dyn) {
+    static const char* ch_env = getenv("MMRE_SWEEP_CHUNK");  /* A/B: 1, 2 or 4 units per claim */
+    const int64_t per_wg = q_tiles * n_et / (g > 0 ? g : 1);
+    chunk = ch_env ? (atoi(ch_env) >= 4 ? 4 : atoi(ch_env) >= 2 ? 2 : 1) : (per_wg >= 16 ? 4 : 1);
+  }
+  const int ng = (g % 8 == 0 && n_et >= 8) ? 8 : 1;
+#define MMRE_LVG(DYNCV)                                                                                             \
+  hipLaunchKernelGGL((k_sweep_valu<OP, false, false, 0, DYNCV, L1Q_GS>), dim3((unsigned)g), dim3(NT), 0, st, ent_km,  \
+                     e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base, ng, 0, 0.0f, thr, qtrue, nullptr, nullptr, \
+                     nullptr, nullptr, (int64_t)0, counts, nullptr, l1)
+  if (chunk == 4) MMRE_LVG(4);
+  else if (chunk == 2) MMRE_LVG(2);
+  else if (chunk == 1) MMRE_LVG(1);
+  else MMRE_LVG(0);
+#undef MMRE_LVG
+  MMRE_CHECK_LAUNCH();
+  return MMRE_OK;
+}
+
 // ------------------------------------------ fused TransE L1 evaluation (round 5) ---
 // mmre_link_evaluate_l1q: the whole count-only TransE L1 evaluation of a query set -- entity
 // prep, query prep, truth scores, filter-list scores and counts, the L1 filter's quantization
@@ -3327,9 +3590,30 @@ static int launch_valu(bool tc, bool store, hipStream_t st, const float* ent_km,
 //   K3 k_eval_count_probe filter counts, a wave per group | the code-width probe, a wave per
 //                         sampled query (the last of its 128 blocks decides 8 vs 16 bits)
 //   K4-K6                 the three gated sweeps (8-bit, 16-bit, f32; the code-width word
-//                         names the one that counts); the f32 launch also carries the
+//                         names the one that counts); the two code sweeps are GROUPED (below);
+//                         the f32 launch also carries the
 //                         finalize (filtered += raw): each workgroup's slice when its gate is
 //                         shut, the last workgroup's pass (ticket) when it is open
+// Grouped code sweeps: a TransE query vector depends on (mode, r, anchor) alone, the filter
+// groups' key, so every member of a group would sweep a bit-identical row of codes; only its
+// threshold (its own truth's score) differs. The code sweeps therefore run one SAD chain per
+// SWEEP ROW -- a group, cut into runs of <= L1Q_GS members -- and the rank epilogue compares each
+// (row, entity) integer score against every member's thresholds (sweep_valu_body, GS > 0):
+//   K1 block 0            the row map from the group offsets (rows per group, a block scan):
+//                         row -> first member's position in grp_q, member count; the row totals
+//                         (device words: the host never knows them)
+//   K2                    quantizes ONE column per row (the first member's vector, read from its
+//                         row-major copy) into the query-side code planes; the tight bound's
+//                         q_l1c is per row; a block range writes the query -> row map and, per
+//                         128-row tile, the largest member count (the slot loop's bound)
+//   K3                    the probe samples the same queries as before and reads their codes
+//                         through that map: the same decision
+//   sweeps                work unit = (row tile) x (entity tile); per-query outputs unchanged.
+// The member thresholds are computed by the sweep when it enters a row tile (load_meta_grp), not
+// in K3 as per-tile tables: the code width -- which of the two threshold sets applies -- is only
+// known when K3 ends. K1 still prepares and measures every query (q_km, q_rows, q_true, truth
+// are outputs; M, the f32 decision and the code step stay what the separate path computes), and
+// the f32 fallback sweeps per query.
 // No cross-workgroup hand-off inside K1 / K2: grid-wide results pass at kernel boundaries.
 // Measured on the way (MI355X, C2, per evaluation): a __threadfence() per K1 block (L2
 // write-back of each block's freshly written rows) 163 us for K1; per-block partials read back by
@@ -3363,6 +3647,16 @@ struct EvalL1 {
   uint32_t* hdr;            // the L1 filter header
   double n_elem;
   float ratio;
+  // the grouped sweep's row map (block 0 of K1): each filter group, cut into runs of <= row_cap
+  // members, gives the sweep rows -- row_off the run's first position in grp_q, row_cnt its
+  // members; n_rows = {rows, rows padded to tiles} (tile_m, the largest count per 128-row tile, is K2's)
+  const int64_t* grp_qoff;
+  int64_t n_groups;
+  int row_cap;   // 0: no row map (the ungrouped sweeps follow), the grid has no row-map block
+  int32_t* row_off;
+  int32_t* row_cnt;
+  int32_t* tile_m;
+  int32_t* n_rows;
 };
 
 // canonical sum of squares over x[0..dim) (k ascending, LDS reads batched 16 per round) and
@@ -3399,8 +3693,51 @@ __global__ __launch_bounds__(256, 7) void k_eval_prep(EvalL1 P) {
   const int kp = P.kp, kt = kp, ls = kt + 1, rb = P.rb, rbq = P.rbq, dim = P.dim;
   const int tid = threadIdx.x, lane = tid & 31, slot = tid >> 5;
   float mx = 0.0f, sa = 0.0f;
-  if ((int)blockIdx.x < P.n_eblk) {  // ---- entity rows (k_prep_rows for TransE)
-    const int64_t e0 = (int64_t)blockIdx.x * rb;
+  if (P.row_cap > 0 && blockIdx.x == 0) {
+    // ---- the row map, from the group offsets alone (first in dispatch order: it overlaps the
+    // prep blocks). Thread t takes a contiguous run of groups: rows per run, a block scan, then
+    // the rows written in group order -- any partition, any order; a group of n members gives
+    // ceil(n / row_cap) rows, so rows <= queries.
+    __shared__ int s_scan[256];
+    const int cap = P.row_cap;
+    const int64_t per = (P.n_groups + 255) / 256;
+    const int64_t g0 = (int64_t)tid * per, g1 = g0 + per < P.n_groups ? g0 + per : P.n_groups;
+    int nr = 0;
+#pragma unroll 8
+    for (int64_t g = g0; g < g1; ++g) {
+      const int64_t n = P.grp_qoff[g + 1] - P.grp_qoff[g];
+      nr += n > 0 ? (int)((n + cap - 1) / cap) : 0;
+    }
+    s_scan[tid] = nr;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+      const int v = tid >= o ? s_scan[tid - o] : 0;
+      __syncthreads();
+      s_scan[tid] += v;
+      __syncthreads();
+    }
+    int64_t row = s_scan[tid] - nr;
+    const int64_t total = s_scan[255], rows_pad = total > 0 ? (total + TQ - 1) / TQ * TQ : TQ;
+    for (int64_t g = g0; g < g1; ++g) {
+      const int64_t a = P.grp_qoff[g], n = P.grp_qoff[g + 1] - a;
+      for (int64_t j = 0; j < n && row < P.q_pad; j += cap, ++row) {
+        P.row_off[row] = (int32_t)(a + j);
+        P.row_cnt[row] = (int32_t)(n - j < cap ? n - j : cap);
+      }
+    }
+    for (int64_t r = total + tid; r < rows_pad && r < P.q_pad; r += 256) {
+      P.row_off[r] = 0;
+      P.row_cnt[r] = 0;
+    }
+    if (tid == 0) {
+      P.n_rows[0] = (int32_t)(total < P.q_pad ? total : P.q_pad);
+      P.n_rows[1] = (int32_t)(rows_pad < P.q_pad ? rows_pad : P.q_pad);
+    }
+    return;
+  }
+  const int bx = (int)blockIdx.x - (P.row_cap > 0 ? 1 : 0);  // the prep blocks
+  if (bx < P.n_eblk) {  // ---- entity rows (k_prep_rows for TransE)
+    const int64_t e0 = (int64_t)bx * rb;
     for (int i = slot; i < rb; i += 8) {
       const int64_t e = e0 + i;
       float* x = lds + i * ls;
@@ -3435,7 +3772,7 @@ __global__ __launch_bounds__(256, 7) void k_eval_prep(EvalL1 P) {
     // query at once (into LDS); the norms and the combine work from LDS. (Reading the relation
     // row for its norm and again for the combine, each in its own dependent rounds, made a
     // block's latency ~27 us: K1 31.7 us for an 8-way share of C2.)
-    const int64_t q0 = (int64_t)(blockIdx.x - P.n_eblk) * rbq;
+    const int64_t q0 = (int64_t)(bx - P.n_eblk) * rbq;
     float* y0 = lds + rbq * ls;      // the truth rows
     float* z0 = lds + 2 * rbq * ls;  // the relation rows
     if (tid < rbq) {
@@ -3540,10 +3877,10 @@ __global__ __launch_bounds__(256, 7) void k_eval_prep(EvalL1 P) {
   }
   __syncthreads();
   if (tid == 0) {
-    P.pstat[2 * blockIdx.x] = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-    P.pstat[2 * blockIdx.x + 1] = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
+    P.pstat[2 * bx] = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+    P.pstat[2 * bx + 1] = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
   }
-  if (blockIdx.x == 0)
+  if (bx == 0)
     for (int i = 2 + tid; i < L1Q_PART / 4; i += 256) P.hdr[i] = 0u;
 }
 
@@ -3592,6 +3929,15 @@ struct EvalQuant {  // K2's quantization operands (k_l1q_quant8<TIGHT> + the 16-
   int kw, k2, kt, n_blk;  // 8-bit word rows, 16-bit word rows, floats per row, blocks per plane
   int tight;
   float* q_l1c;
+  // grouped sweep: the query-side planes hold one column per sweep ROW (its first member's
+  // vector: every member's is bit-identical), q_l1c is per row, and the blocks after the
+  // quantization blocks write the query -> row map (the probe's)
+  const int32_t* row_off;
+  const int32_t* row_cnt;
+  const int32_t* grp_q;
+  const int32_t* n_rows;
+  int32_t* row_of_q;
+  int32_t* tile_m;
 };
 
 __global__ __launch_bounds__(256, 4) void k_eval_quant_list(EvalL1 P, EvalQuant Q, const int32_t* __restrict__ ids,
@@ -3606,6 +3952,27 @@ __global__ __launch_bounds__(256, 4) void k_eval_quant_list(EvalL1 P, EvalQuant 
       return;
     }
     list_v[p] = l1_row_score64(P.q_rows + vq * P.kp, P.ent_rows + j * P.kp, P.kp);
+    return;
+  }
+  if ((int)blockIdx.x >= n_lblk + 2 * Q.n_blk) {  // ---- query -> sweep row, a thread per row
+    // (+ the block's two row tiles' largest member counts, the sweep's slot-loop bounds)
+    __shared__ int s_tm[2];
+    if (threadIdx.x < 2) s_tm[threadIdx.x] = 0;
+    __syncthreads();
+    const int mb = (int)blockIdx.x - n_lblk - 2 * Q.n_blk;
+    const int64_t row = (int64_t)mb * 256 + threadIdx.x;
+    int n = 0;
+    if (row < Q.n_rows[0]) {
+      const int64_t a = Q.row_off[row];
+      n = Q.row_cnt[row];
+      for (int s = 0; s < n; ++s) {
+        const int64_t q = Q.grp_q[a + s];
+        if (q >= 0 && q < P.n_query) Q.row_of_q[q] = (int32_t)row;
+      }
+    }
+    if (n > 0) atomicMax(&s_tm[threadIdx.x >> 7], n);
+    __syncthreads();
+    if (threadIdx.x < 2 && (int64_t)(2 * mb + threadIdx.x + 1) * TQ <= P.q_pad) Q.tile_m[2 * mb + threadIdx.x] = s_tm[threadIdx.x];
     return;
   }
   // ---- M and the codes / f32 decision from K1's per-block statistics: every quantization block
@@ -3647,7 +4014,8 @@ __global__ __launch_bounds__(256, 4) void k_eval_quant_list(EvalL1 P, EvalQuant 
   const int bx = ent ? b - Q.n_blk : b;
   const L1QPlane& pl = ent ? Q.pe : Q.pq;
   const float* __restrict__ km = pl.km;
-  const int64_t pad = pl.pad, c0 = pl.c0, n = pl.n;
+  const bool rows = !ent && Q.n_rows != nullptr;  // grouped: a column per sweep row
+  const int64_t pad = pl.pad, c0 = pl.c0, n = rows ? (int64_t)Q.n_rows[1] : pl.n;
   uint32_t* __restrict__ out = pl.out;
   uint32_t* __restrict__ out16 = ent ? Q.out16e : Q.out16q;
   const int kp = P.kp, kw = Q.kw, k2 = Q.k2, kt = Q.kt;
@@ -3662,6 +4030,10 @@ __global__ __launch_bounds__(256, 4) void k_eval_quant_list(EvalL1 P, EvalQuant 
   for (int64_t cb = (int64_t)bx * 32; cb < n; cb += (int64_t)Q.n_blk * 32) {  // uniform
     const bool live = cb + cl < n;
     const int64_t c = c0 + cb + cl;
+    // the source column: the entity's own, or the row's first member (a padding row: zeros)
+    int64_t cs = c;
+    if (rows) cs = (live && c < Q.n_rows[0]) ? (int64_t)Q.grp_q[Q.row_off[c]] : -1;
+    if (rows && cs >= P.n_query) cs = -1;
     float err = 0.0f;
     // four word rows of a thread in flight together (kw <= 64 word rows -- d <= 256 -- is two
     // load rounds instead of four; eight took 167 VGPRs), then coded in the same order as before
@@ -3672,8 +4044,22 @@ __global__ __launch_bounds__(256, 4) void k_eval_quant_list(EvalL1 P, EvalQuant 
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
           const int k = 4 * (r0 + 8 * j) + h;
-          xv[j][h] = (live && r0 + 8 * j < kw && k < kp) ? km[(int64_t)k * pad + c] : 0.0f;
+          xv[j][h] = (!rows && live && r0 + 8 * j < kw && k < kp) ? km[(int64_t)k * pad + c] : 0.0f;
         }
+      if (rows) {  // a row's vector from its member's row-major copy (the same floats as the k-major
+                   // plane's; 16 B per word row instead of four scattered dwords)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = 4 * (r0 + 8 * j);
+          if (live && cs >= 0 && r0 + 8 * j < kw && k + 3 < kp) {
+            const float4 v = *reinterpret_cast<const float4*>(P.q_rows + cs * kp + k);
+            xv[j][0] = v.x;
+            xv[j][1] = v.y;
+            xv[j][2] = v.z;
+            xv[j][3] = v.w;
+          }
+        }
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int r = r0 + 8 * j;
@@ -3750,7 +4136,7 @@ __global__ __launch_bounds__(256) void k_eval_count_probe(
     const int32_t* __restrict__ qtrue, const float* __restrict__ thr, int64_t n_query, int64_t n_ent,
     int32_t* __restrict__ counts, const uint32_t* __restrict__ uq, int64_t q_pad, const uint32_t* __restrict__ ue,
     int64_t e_pad, int64_t n_slice, int kw, int kt, const float* __restrict__ q_l1c, uint32_t* __restrict__ hdr,
-    uint32_t* __restrict__ ticket, uint32_t probe_max, int force_bits) {
+    uint32_t* __restrict__ ticket, uint32_t probe_max, int force_bits, const int32_t* __restrict__ row_of_q) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if ((int)blockIdx.x < n_cblk) {
     // the wave's own LDS slices: written and read by the same wave (wave barriers, no block sync)
@@ -3811,6 +4197,9 @@ __global__ __launch_bounds__(256) void k_eval_count_probe(
   if (w != L1Q_CODES8) return;  // the f32 fallback: no codes to probe
   const int pb = ((int)blockIdx.x - n_cblk) * 4 + wv, n_pb = ((int)gridDim.x - n_cblk) * 4;
   const int64_t q = (int64_t)pb * n_query / n_pb;
+  // the same sampled queries as the separate path's probe; their codes and error sums sit in
+  // their sweep row's column (row_of_q: the grouped planes)
+  const int64_t qc = row_of_q ? (int64_t)row_of_q[q] : q;
   const int64_t span = n_slice > L1Q_PROBE_E ? n_slice - L1Q_PROBE_E : 0;
   const int64_t c = (((int64_t)pb * span / n_pb) & ~(int64_t)3) + 4 * lane;
   const float l1d = l1q_delta(hdr, 255.0f);
@@ -3820,7 +4209,7 @@ __global__ __launch_bounds__(256) void k_eval_count_probe(
   if (c < n_slice) {
 #pragma unroll 8
     for (int r = 0; r < kw; ++r) {
-      const uint32_t a = uq[(int64_t)r * q_pad + q];
+      const uint32_t a = uq[(int64_t)r * q_pad + qc];
       const uint4 e = *reinterpret_cast<const uint4*>(ue + (int64_t)r * e_pad + c);
       acc[0] = __builtin_amdgcn_sad_u8(a, e.x, acc[0]);
       acc[1] = __builtin_amdgcn_sad_u8(a, e.y, acc[1]);
@@ -3829,7 +4218,7 @@ __global__ __launch_bounds__(256) void k_eval_count_probe(
     }
   }
   uint32_t t_sure, t_span;
-  l1_int_thresholds(thr[q], (q_l1c ? q_l1c[q] : l1c) + (q_l1c ? 0x1p-120f : 0.0f), l1d, l1f, q_l1c ? 2u * hdr[3] : 0u,
+  l1_int_thresholds(thr[q], (q_l1c ? q_l1c[qc] : l1c) + (q_l1c ? 0x1p-120f : 0.0f), l1d, l1f, q_l1c ? 2u * hdr[3] : 0u,
                     t_sure, t_span);
   uint32_t und = 0u;
 #pragma unroll
@@ -4468,8 +4857,12 @@ static int64_t eval_blocks(int dim, int64_t e_pad, int64_t q_pad) {
   const int kp = plane_rows(MMRE_TRANSE_L1, dim);
   return (e_pad + eval_rb(kp) - 1) / eval_rb(kp) + (q_pad + eval_rbq(kp) - 1) / eval_rbq(kp);
 }
+static int64_t eval_stat_bytes(int dim, int64_t e_pad, int64_t q_pad) {
+  return 256 + round_up(8 * eval_blocks(dim, e_pad, q_pad), 256);  // tickets (+ the row counts), K1's per-block statistics
+}
 static int64_t eval_extra_bytes(int dim, int64_t e_pad, int64_t q_pad) {
-  return 256 + round_up(8 * eval_blocks(dim, e_pad, q_pad), 256);  // tickets, K1's per-block statistics
+  // + the grouped sweep's row map: row_off, row_cnt, row_of_q (q_pad each: rows <= queries), tile_m
+  return eval_stat_bytes(dim, e_pad, q_pad) + 3 * 4 * q_pad + round_up(4 * (q_pad / TQ), 256);
 }
 
 extern "C" int64_t mmre_link_evaluate_l1q_workspace(int dim, int64_t e_pad, int64_t q_pad) {
@@ -4511,6 +4904,29 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   char* extra = w + mmre_link_l1q_workspace(dim, e_pad, q_pad);
   uint32_t* ticket = (uint32_t*)extra;  // zero before the first call (the caller zeroes the workspace once)
   float* pstat = (float*)(extra + 256);
+  int32_t* n_rows = (int32_t*)extra + 8;  // {rows, rows padded to tiles}: written by K1's block 0
+  int32_t* row_off = (int32_t*)(extra + eval_stat_bytes(dim, e_pad, q_pad));
+  int32_t* row_cnt = row_off + q_pad;
+  int32_t* row_of_q = row_cnt + q_pad;
+  int32_t* tile_m = row_of_q + q_pad;
+  // Grouped or not. The grouped sweep shares a SAD chain among a row's members but pays for it:
+  // K1's row-map block and K2's map blocks on every call, a longer unit per row, fewer units.
+  // It runs when the rows (bounded from the group count: a group of n members is ceil(n / 8)
+  // rows) (a) give every resident workgroup a unit -- a small evaluation is bound by its longest
+  // workgroup and by launch latencies, C1 -- and (b) are few enough against the queries
+  // (L1Q_GROUP_FRAC, measured: DESIGN.md 4d). Otherwise the call is the ungrouped one: no row
+  // map, a column per query, the per-query sweeps. MMRE_GROUP_CAP=1..8 (A/B, tests) forces the
+  // grouped sweep with that many members per row at most.
+  const char* cap_env = getenv("MMRE_GROUP_CAP");
+  int row_cap = cap_env ? std::min(L1Q_GS, std::max(1, atoi(cap_env))) : L1Q_GS;
+  if (!cap_env) {
+    const int64_t res = resident_groups((const void*)k_sweep_valu<6, false, false, 0, 1, L1Q_GS>, NT);
+    const int64_t n_et0 = (e_end - e_begin + TE - 1) / TE;
+    const int64_t rows8 = std::min<int64_t>(n_query, n_groups + n_query / L1Q_GS);
+    if ((rows8 + TQ - 1) / TQ * n_et0 < res || (double)rows8 > L1Q_GROUP_FRAC * (double)n_query) row_cap = 0;
+  }
+  const bool grouped = row_cap > 0;
+  const int64_t rows_max = grouped ? std::min<int64_t>(n_query, n_groups + n_query / row_cap) : n_query;
   const int64_t e_cols = round_up(e_end, TE) - e_begin;
   const int64_t n_slice = e_end - e_begin;
   const int n_et = (int)((n_slice + TE - 1) / TE);
@@ -4551,8 +4967,15 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   P.hdr = hdr;
   P.n_elem = (double)kp * (double)(q_pad + e_cols);
   P.ratio = ratio_env ? (float)atof(ratio_env) : 128.0f;
-  // K1: prep + truths + |x| statistics (the last block decides codes vs f32 and resets the header)
-  hipLaunchKernelGGL(k_eval_prep, dim3((unsigned)(P.n_eblk + P.n_qblk)), dim3(256), lds1, st, P);
+  P.grp_qoff = d_grp_qoff;
+  P.n_groups = n_groups;
+  P.row_cap = row_cap;
+  P.row_off = row_off;
+  P.row_cnt = row_cnt;
+  P.tile_m = tile_m;
+  P.n_rows = n_rows;
+  // K1: the row map (block 0, grouped) | prep + truths + |x| statistics
+  hipLaunchKernelGGL(k_eval_prep, dim3((unsigned)((grouped ? 1 : 0) + P.n_eblk + P.n_qblk)), dim3(256), lds1, st, P);
   MMRE_CHECK_LAUNCH();
   // K2: list scores | codes (8-bit words + error row, 16-bit words)
   EvalQuant Q{};
@@ -4569,8 +4992,15 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   Q.n_blk = (int)std::min<int64_t>(512, std::max<int64_t>(64, (resident_groups((const void*)k_eval_quant_list, 256) -
                                                               n_lblk) / 2));
   Q.tight = tight ? 1 : 0;
-  Q.q_l1c = q_l1c;
-  hipLaunchKernelGGL(k_eval_quant_list, dim3((unsigned)(n_lblk + 2 * Q.n_blk)), dim3(256), 0, st, P, Q, d_filt_ids,
+  Q.q_l1c = q_l1c;  // per sweep row (grouped), per query
+  Q.row_off = row_off;
+  Q.row_cnt = row_cnt;
+  Q.grp_q = d_grp_q;
+  Q.n_rows = grouped ? n_rows : nullptr;
+  Q.row_of_q = row_of_q;
+  Q.tile_m = tile_m;
+  const int n_mblk = grouped ? (int)((rows_max + 255) / 256) : 0;  // the query -> row map, tile_m: a thread per row
+  hipLaunchKernelGGL(k_eval_quant_list, dim3((unsigned)(n_lblk + 2 * Q.n_blk + n_mblk)), dim3(256), 0, st, P, Q, d_filt_ids,
                      d_entry_q, n_entries, d_list_scores, n_lblk);
   MMRE_CHECK_LAUNCH();
   // K3: filter counts | the code-width probe
@@ -4579,26 +5009,42 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   hipLaunchKernelGGL(k_eval_count_probe, dim3((unsigned)(n_cblk + L1Q_PROBE_Q / 4)), dim3(256), 0, st, d_grp_qoff, d_grp_q,
                      n_groups, n_cblk, d_filt_off, d_filt_ids, d_list_scores, d_q_true, d_truth, n_query, n_ent,
                      d_counts, vq, q_pad, ve + e_begin, e_pad, n_slice, k4, kt, tight ? q_l1c : nullptr, hdr,
-                     ticket, probe_max, bits == 8 || bits == 16 ? bits : 0);
+                     ticket, probe_max, bits == 8 || bits == 16 ? bits : 0, grouped ? row_of_q : nullptr);
   MMRE_CHECK_LAUNCH();
   // the sweeps: the one the code-width word names counts, the others' workgroups leave
   const int64_t tw = (n_ent + 31) / 32;
   L1Q l1{d_q_rows, d_ent_rows, hdr, (unsigned long long*)((char*)d_work + 256), d_q_km, d_ent_km + e_begin, kp,
          kt, nullptr, tight ? q_l1c : nullptr, hdr + 4, d_undecided_q};
   l1.wq = l1q_work_counters(hdr);
+  if (!grouped) {  // a sweep per query: the separate path's launches
+    int rc = launch_valu<6>(false, false, st, (const float*)(ve + e_begin), e_pad, n_slice, n_et, (int)e_begin,
+                            (const float*)vq, q_pad, n_query, k4, 0, 0.0f, d_truth, d_q_true, d_qr, d_qmode, nullptr,
+                            nullptr, tw, d_counts, nullptr, l1, false);
+    if (rc) return rc;
+    L1Q l16 = l1;
+    l16.gate = hdr + 1;
+    rc = launch_valu<5>(false, false, st, (const float*)(ue + e_begin), e_pad, n_slice, n_et, (int)e_begin,
+                        (const float*)uq, q_pad, n_query, k2, 0, 0.0f, d_truth, d_q_true, d_qr, d_qmode, nullptr,
+                        nullptr, tw, d_counts, nullptr, l16, false);
+    if (rc) return rc;
+  } else {
+  l1.row_off = row_off;
+  l1.row_cnt = row_cnt;
+  l1.grp_q = d_grp_q;
+  l1.tile_m = tile_m;
+  l1.n_rows = n_rows;
   // the 8-bit sweep (it leaves unless the word names the 8-bit codes) and the gated 16-bit one
   // (one launch for both widths was tried: with both SAD loops in one kernel the allocator
-  // spilled 58-81 VGPRs)
-  int rc = launch_valu<6>(false, false, st, (const float*)(ve + e_begin), e_pad, n_slice, n_et, (int)e_begin,
-                          (const float*)vq, q_pad, n_query, k4, 0, 0.0f, d_truth, d_q_true, d_qr, d_qmode, nullptr,
-                          nullptr, tw, d_counts, nullptr, l1, false);
+  // spilled 58-81 VGPRs): grouped, a SAD chain per sweep row, ranked against each member
+  int rc = launch_valu_grp<6>(st, (const float*)(ve + e_begin), e_pad, n_slice, n_et, (int)e_begin, (const float*)vq,
+                              q_pad, n_query, k4, d_truth, d_q_true, d_counts, l1, rows_max);
   if (rc) return rc;
   L1Q l16 = l1;
   l16.gate = hdr + 1;
-  rc = launch_valu<5>(false, false, st, (const float*)(ue + e_begin), e_pad, n_slice, n_et, (int)e_begin,
-                      (const float*)uq, q_pad, n_query, k2, 0, 0.0f, d_truth, d_q_true, d_qr, d_qmode, nullptr, nullptr,
-                      tw, d_counts, nullptr, l16, false);
+  rc = launch_valu_grp<5>(st, (const float*)(ue + e_begin), e_pad, n_slice, n_et, (int)e_begin, (const float*)uq,
+                          q_pad, n_query, k2, d_truth, d_q_true, d_counts, l16, rows_max);
   if (rc) return rc;
+  }
   // the f32 fallback, gated on the word; it also carries the finalize (filtered += raw)
   L1Q gate{};
   gate.gate = hdr + 1;

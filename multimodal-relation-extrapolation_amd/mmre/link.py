@@ -101,7 +101,7 @@ class FilterIndex:
             ids[dst] = gids
         return off, ids
 
-    def groups(self, qh, qr, qt, qmode, max_group: int = 64, entity_range=None):
+    def groups(self, qh, qr, qt, qmode, max_group: int = 64, entity_range=None, order: str = "key"):
         """Filter groups: queries with the same (mode, r, anchor) share their known-entity
         list (Test.h:85 `_find` looks up (r, t) for head_batch, (h, r) for tail_batch).
         Groups larger than `max_group` queries are split (one wave of the count kernel per
@@ -109,7 +109,10 @@ class FilterIndex:
         entry_q int32): the query partition, one CSR list per group and, per listed entity,
         the group member whose query vector scores it -- for mmre_link_truth_grouped.
         entity_range (e0, e1): keep only listed entities in [e0, e1) -- the filter correction of
-        a rank that sweeps that slice of the table (entity-sharded evaluation)."""
+        a rank that sweeps that slice of the table (entity-sharded evaluation).
+        order: "key" (ascending key, the default) or "size" -- groups by descending member
+        count (stable), the order the fused TransE evaluation sweeps best: a group is one sweep
+        row there, and a 128-row tile costs its largest group's members."""
         qh, qr, qt, qmode = (np.asarray(x, np.int64) for x in (qh, qr, qt, qmode))
         anchor = np.where(qmode == HEAD, qt, qh)
         key = (qmode * self.n_rel + qr) * self.n_ent + anchor
@@ -124,6 +127,15 @@ class FilterIndex:
         grp_qoff = np.empty(len(piece_key) + 1, np.int64)
         grp_qoff[:-1] = starts[piece_key] + piece_idx * max_group
         grp_qoff[-1] = len(grp_q)
+        if order == "size":
+            sizes = np.diff(grp_qoff)
+            perm = np.argsort(-sizes, kind="stable")
+            new_off = np.zeros(len(sizes) + 1, np.int64)
+            np.cumsum(sizes[perm], out=new_off[1:])
+            src = np.repeat(grp_qoff[:-1][perm] - new_off[:-1], sizes[perm]) + np.arange(len(grp_q))
+            grp_q, grp_qoff = grp_q[src], new_off
+        elif order != "key":
+            raise ValueError(f"groups: unknown order {order!r}")
         first = grp_q[grp_qoff[:-1]]
         off, ids = self.filters(qh[first], qr[first], qt[first], qmode[first])
         entry_q = np.repeat(first, np.diff(off)).astype(np.int32)
@@ -148,6 +160,24 @@ class FilterIndex:
             w = (m.reshape(self.n_rel, words, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(-1)
             out.append(np.ascontiguousarray(w.astype(np.uint32)))
         return out
+
+
+# Members per filter group on the fused TransE path: the grouped sweep's slot capacity (a group
+# is then exactly one sweep row; larger groups are cut by the native side anyway, and the filter
+# counts take one wave per group either way). MMRE_MAX_GROUP: A/B.
+FUSED_MAX_GROUP = 8
+
+
+def group_args(spec, type_constrain: bool = False) -> dict:
+    """FilterIndex.groups keywords for an evaluation of `spec`: on the fused TransE path
+    (mmre_link_evaluate_l1q sweeps one row per group) groups by descending size, capped at the
+    sweep's slot capacity; the defaults everywhere else."""
+    if spec is None or spec.model != "transe" or type_constrain or int(spec.pred_kind) != 0:
+        return {}
+    # (as LinkSweep._fusable: the separate path gains nothing from small size-ordered groups)
+    if os.environ.get("MMRE_L1_FILTER", "1") == "0" or os.environ.get("MMRE_FUSED_EVAL", "1") == "0":
+        return {}
+    return dict(order="size", max_group=int(os.environ.get("MMRE_MAX_GROUP", FUSED_MAX_GROUP)))
 
 
 class LinkSweep:
@@ -430,7 +460,8 @@ def evaluate_link_prediction(spec: ScoreSpec, test_h, test_r, test_t, index: Fil
     filt = None
     masks = None
     if index is not None:
-        filt = tuple(torch.from_numpy(a).to(dev) for a in index.groups(qh, qr, qt, qm))
+        filt = tuple(torch.from_numpy(a).to(dev) for a in index.groups(qh, qr, qt, qm,
+                                                                                  **group_args(spec, type_constrain)))
         if type_constrain:
             tm = index.type_masks()
             masks = tuple(torch.from_numpy(m).to(dev) for m in tm)

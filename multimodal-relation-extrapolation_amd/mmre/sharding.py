@@ -89,7 +89,7 @@ def calibrate_weights(spec, qh, qr, qt, qm, index, device, group=None):
     whole evaluation has 0.2 %), and each costs ~140 swept pairs. Rank 0's counts are broadcast
     so every rank packs the same partition. None (count-based packing) for other models."""
     import torch.distributed as dist
-    from .link import LinkSweep
+    from .link import LinkSweep, group_args
     if spec is None or index is None or spec.model != "transe":
         return None
     if len(qh) == 0:
@@ -100,7 +100,7 @@ def calibrate_weights(spec, qh, qr, qt, qm, index, device, group=None):
     multi = dist.is_initialized() and dist.get_world_size(group) > 1
     if not multi or dist.get_rank(group) == 0:  # the calibration runs on rank 0 only
         to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        filt = tuple(to(a) for a in index.groups(qh, qr, qt, qm))
+        filt = tuple(to(a) for a in index.groups(qh, qr, qt, qm, **group_args(spec)))
         und = torch.zeros(len(qh), dtype=torch.int32, device=device)
         sw.run(to(qh), to(qr), to(qt), to(qm), filt=filt, undecided_q=und)
         w = torch.from_numpy(cost_weights(und.cpu().numpy(), sw.n_ent))
@@ -244,7 +244,9 @@ class ShardedLinkEvaluation:
         self.filt = None
         self.masks_tc = None
         if index is not None:
-            self.filt = tuple(to(a) for a in index.groups(qh[mine], qr[mine], qt[mine], qm[mine]))
+            from .link import group_args
+            self.filt = tuple(to(a) for a in index.groups(qh[mine], qr[mine], qt[mine], qm[mine],
+                                                          **group_args(spec, type_constrain)))
             if type_constrain:
                 tm = index.type_masks()
                 if tm is None:
@@ -456,7 +458,9 @@ class EntityShardedLinkEvaluation(ShardedLinkEvaluation):
         self.filt = None
         self.masks_tc = None
         if index is not None:
-            self.filt = tuple(to(a) for a in index.groups(qh, qr, qt, qm, entity_range=self.entity_range))
+            from .link import group_args
+            self.filt = tuple(to(a) for a in index.groups(qh, qr, qt, qm, entity_range=self.entity_range,
+                                                          **group_args(spec, type_constrain)))
             if type_constrain:
                 tm = index.type_masks()
                 if tm is None:
