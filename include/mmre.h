@@ -266,6 +266,55 @@ int mmre_link_metrics(const int32_t* h_head_counts, const int32_t* h_tail_counts
                       float* h_out);
 
 /* ====================================================================== *
+ *  Relation prediction: every test pair (h, t) against every relation.   *
+ *  Replaces, per evaluation, the loop getRelBatch (Test.h:55-62) +        *
+ *  model.predict on R rows (h, j, t), mode 'normal' + testRel             *
+ *  (Test.h:194-228, _find Corrupt.h:166-177) per test triple, and         *
+ *  test_relation_prediction (Test.h:329-354).                             *
+ * ====================================================================== */
+
+/* Bytes of d_work for mmre_rel_evaluate: the per-relation values that do not depend on the
+ * pair, written once per call by a prologue -- TransE: the F.normalize'd relation rows
+ * (n_rel x dim floats, used with norm_flag); RotatE: sin and cos of every phase (2 x n_rel x
+ * dim floats); DistMult / ComplEx: 0. Negative for an unknown model or a bad shape. */
+int64_t mmre_rel_workspace(int model, int64_t n_rel, int dim);
+
+/* For test triple i = (d_qh[i], d_qr[i], d_qt[i]): pred(j) = what model.predict returns for the
+ * row (h, j, t) in 'normal' mode, j = 0..n_rel-1 (Test.h:55-62) -- bit for bit the score
+ * chain of mmre_ns_forward for that row (lane-strided partials, butterfly wave sum, TransE's
+ * three norms and divisions, RotatE's canonical sincos) followed by the pred_kind / margin
+ * transform of mmre_link_truth (for TransE with a model margin and RotatE, mmre_ns_forward's
+ * m - s IS that transform's inner step: pred_kind 1 / 3). Then, Test.h:200-213:
+ *   d_counts[0][i] = #{ j != r : pred(j) < pred(r) }   strict: ties favour the truth, and a NaN
+ *                                                      on either side never counts;
+ *   d_counts[1][i] = the same without the relations listed for query i (the known relations
+ *                    of (h, t) in train + valid + test; a list may hold r itself, relations that
+ *                    do not beat the truth and ids outside [0, n_rel), which are ignored; no
+ *                    relation twice);
+ *   d_truth[i]     = pred(r);  d_scores[i * n_rel + j] = pred(j) when d_scores is given.
+ * d_filt_off[n_query + 1] (int64) / d_filt_ids (int32): per-query CSR; NULL/NULL = no filter
+ * (both columns equal). Tables as mmre_ns_forward takes them (RotatE entities (E, 2 dim)).
+ * A query whose h, t or r is out of range reads nothing: counts 0, truth NaN, scores NaN.
+ * Enqueues a prologue (TransE with norm_flag, RotatE) and one sweep launch; any n_rel >= 1.
+ * Checked before any launch: MMRE_ERR_MODEL for an unknown model, MMRE_ERR_SHAPE for dim > 512,
+ * MMRE_ERR_ARG for a null table / output, sizes < 1, n_query < 0, pred_kind outside 0..4, one
+ * of the two filter arrays without the other, MMRE_ERR_WORKSPACE for a d_work smaller than
+ * mmre_rel_workspace. n_query == 0 is a successful no-op. */
+int mmre_rel_evaluate(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                      const float* d_ent_im, const float* d_rel, const float* d_rel_im, int64_t n_ent,
+                      int64_t n_rel, int dim, float phase_denom, const int64_t* d_qh, const int64_t* d_qr,
+                      const int64_t* d_qt, int64_t n_query, const int64_t* d_filt_off, const int32_t* d_filt_ids,
+                      int32_t* d_counts, float* d_truth, float* d_scores, void* d_work, int64_t work_bytes,
+                      void* stream);
+
+/* testRel's accumulation + test_relation_prediction (Test.h:215-225, :329-344), host side, in
+ * query order with the reference's widths (float accumulators; `+= 1.0 / (count + 1)` a double
+ * quotient added to a float; then / (float)n). Counts: int32, raw count of query i at
+ * h_counts[i], filtered at h_counts[stride + i].
+ * h_out[10] = {mrr, mr, hit10, hit3, hit1} x {filter, raw}. */
+int mmre_rel_metrics(const int32_t* h_counts, int64_t n, int64_t stride, float* h_out);
+
+/* ====================================================================== *
  *  OpenKE negative sampler (Base.cpp:78-197 sampling/getBatch,           *
  *  Corrupt.h:7-163 corrupt_head/tail/rel, Random.h:11-29).               *
  *  Bit-exact: each positive's LCG state is reached by affine jump-ahead  *

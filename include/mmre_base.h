@@ -4,11 +4,16 @@
  * absent openke.data loaders call `sampling`). libmmre_base.so exports the same names,
  * argument types (INT = int64 `long`, REAL = float, Setting.h:3-4) and global-state
  * semantics, so a caller switches by loading this library instead of release/Base.so.
- * `sampling` runs the bit-exact GPU sampler (mmre_sampler_openke) and testHead/testTail
+ * `sampling` runs the bit-exact GPU sampler (mmre_sampler_openke) and testHead/testTail/testRel
  * rank the caller's score vector on the GPU; everything else is host bookkeeping.
  * Errors the reference would crash on (missing files, out-of-range index) print a message
- * to stderr and abort. Not exported (outside the link-prediction path): triple
- * classification (getNegTest/getTestBatch), relation prediction (getRelBatch/testRel).
+ * to stderr and abort. Not exported (outside the evaluation path): triple
+ * classification (getNegTest/getTestBatch).
+ *
+ * Deviation from Base.so, on purpose: initTest here ALSO resets the relation-prediction
+ * accumulators (with lastRel). The reference's initTest declares shadowing locals for them (Test.h:29), so its
+ * rel_* globals are never reset and a second relation-prediction evaluation in one process adds
+ * to the first one's sums (and test_relation_prediction divides them in place each time).
  */
 #ifndef MMRE_BASE_H
 #define MMRE_BASE_H
@@ -77,14 +82,30 @@ float getTestLinkHit1(bool type_constrain);
 float getTestLinkMR(bool type_constrain);
 float getTestLinkMRR(bool type_constrain);
 
+/* Relation prediction. Test.h:55-62 -- the relationTotal rows (h, j, t), j = 0..R-1, of test
+ * triple lastRel into caller arrays of length relationTotal; lastRel is NOT advanced. */
+void getRelBatch(int64_t* ph, int64_t* pt, int64_t* pr);
+/* Test.h:194-228 -- con: host float32[R] predictions of those rows (lower = better), ranked on
+ * the GPU against the true relation (raw, and filtered by the known relations of (h, t));
+ * advances lastRel. One call past the last test triple is an out-of-range index: latched (or
+ * fatal) before any GPU work, like testHead's. */
+void testRel(float* con);
+/* Test.h:329-354 -- the float accumulation of the testRel calls since initTest, in call order,
+ * divided by testTotal; prints the reference's raw / filtered lines. */
+void test_relation_prediction(void);
+/* Not in Base.so (its callers read the rel_* globals): the last test_relation_prediction's
+ * {mrr, mr, hit10, hit3, hit1} x {filter, raw}, the layout of mmre_rel_metrics (mmre.h); NaN
+ * while an error is latched. */
+void mmre_base_get_rel_metrics(float* out10);
+
 /* Not in Base.so, whose void API crashes on bad input (Reader.h:59-90 ignores fopen
  * failures; OpenKE/README.md:129). Here a failure -- a file that cannot be opened, a test
  * index out of range, type_constrain without importTypeFiles, a HIP error -- prints its
  * message and, by default, abort()s: an unmodified OpenKE caller never checks for errors.
  * mmre_base_set_error_mode(1) (or MMRE_BASE_LATCH_ERRORS=1 in the environment) latches it
  * instead: the failing call returns, every entry point above returns at once while the latch
- * is set, and their outputs are poisoned (sampling / getHeadBatch / getTailBatch ids -1,
- * batch_y NaN, getTestLink* NaN). mmre_base_last_error returns the code (0: none; mmre.h
+ * is set, and their outputs are poisoned (sampling / getHeadBatch / getTailBatch / getRelBatch
+ * ids -1, batch_y NaN, getTestLink* and mmre_base_get_rel_metrics NaN). mmre_base_last_error returns the code (0: none; mmre.h
  * MMRE_ERR_*, HIP errors as MMRE_ERR_HIP_BASE + hipError_t) and copies the message into
  * msg[cap]; mmre_base_clear_error resets the latch. */
 void mmre_base_set_error_mode(int latch);

@@ -15,13 +15,21 @@
 //                                                              counts stay on the device
 //   Test.h:232-390     test_link_prediction, getTestLink*      one D2H of all counts, then the P14
 //                                                              float accumulation in call order
+//   Test.h:55-62       getRelBatch                             host index fill (lastRel not advanced)
+//   Test.h:194-228     testRel                                 GPU: the caller's R predictions staged and
+//                                                              ranked by the same kernel against the known
+//                                                              relations of (h, t); advances lastRel
+//   Test.h:329-354     test_relation_prediction                one D2H of the counts, the float accumulation
+//                                                              in call order, the reference's printout
 //
 // The per-query rank of Test.h walks all E scores and binary-searches the known-triple
 // list for every better entity (~0.55 ms per query on the host); here it is one small
 // kernel per call whose launch overlaps the caller's next predict. State is global, as in
 // the reference (the ctypes caller owns nothing but its arrays). Triple classification
-// (getNegTest/getTestBatch) and relation prediction are not part of the link-prediction
-// path and are not exported.
+// (getNegTest/getTestBatch) is not part of the evaluation path and is not exported.
+// One deliberate deviation: initTest resets lastRel AND the relation-prediction accumulators
+// (Test.h:29 declares shadowing locals instead, so the reference's rel_* sums survive initTest
+// and a second evaluation in one process adds to stale sums).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -68,7 +76,7 @@ struct State {
   std::vector<REAL> left_mean, right_mean;
   // importTestFiles
   std::vector<Trip> test_list, valid_list, known;  // known = train + valid + test, by (h, r, t)
-  std::vector<int64_t> hoff, toff;                 // per test query: CSR offsets of its known lists
+  std::vector<int64_t> hoff, toff, roff;           // per test query: CSR offsets of its known lists
   // importTypeFiles: per relation sorted allowed heads / tails
   std::vector<std::vector<INT>> head_type, tail_type;
   bool have_types = false;
@@ -79,6 +87,11 @@ struct State {
     bool tc;
   };
   std::vector<Call> calls;
+  int64_t ring_seq = 0;  // staging-ring position, shared by testHead / testTail / testRel
+  // relation prediction: lastRel, testRel calls since initTest, {mrr, mr, hit10, hit3, hit1} x {filter, raw}
+  INT last_rel = 0;
+  int64_t rel_calls = 0;
+  REAL rel_metrics[10] = {};
   REAL hit10 = 0, hit3 = 0, hit1 = 0, mr = 0, mrr = 0;
   REAL hit10_tc = 0, hit3_tc = 0, hit1_tc = 0, mr_tc = 0, mrr_tc = 0;
 };
@@ -101,6 +114,9 @@ struct Device {
   // ranking
   bool test_ready = false;
   int32_t *d_hids = nullptr, *d_tids = nullptr;  // per test query: known heads of (r, t) / tails of (h, r)
+  int32_t* d_rids = nullptr;                     // ... and known relations of (h, t)
+  int32_t* d_rel_counts = nullptr;               // [testRel call][4]
+  int64_t rel_slot_cap = 0;
   uint32_t *d_th = nullptr, *d_tt = nullptr;  // type bitsets [rel][words]
   static constexpr int kRing = 4;
   float* h_stage[kRing] = {};
@@ -235,10 +251,12 @@ void test_device() {
   device_init();
   if (D.test_ready) return;
   HIP_OR_DIE(hipStreamSynchronize(D.st));
-  for (void* p : {(void*)D.d_hids, (void*)D.d_tids, (void*)D.d_th, (void*)D.d_tt, (void*)D.d_counts}) release(p);
+  for (void* p : {(void*)D.d_hids, (void*)D.d_tids, (void*)D.d_rids, (void*)D.d_th, (void*)D.d_tt,
+                  (void*)D.d_counts, (void*)D.d_rel_counts})
+    release(p);
   D.d_th = D.d_tt = nullptr;
-  D.d_counts = nullptr;
-  D.slot_cap = 0;
+  D.d_counts = D.d_rel_counts = nullptr;
+  D.slot_cap = D.rel_slot_cap = 0;
   for (int i = 0; i < Device::kRing; ++i) {
     if (D.h_stage[i]) HIP_OR_DIE(hipHostFree(D.h_stage[i]));
     release(D.d_con[i]);
@@ -249,8 +267,10 @@ void test_device() {
   }
   std::vector<Trip> by_t(S.known);
   std::sort(by_t.begin(), by_t.end(), by_trh);
-  std::vector<int64_t> hoff(1, 0), toff(1, 0);
-  std::vector<int32_t> hids, tids;
+  std::vector<Trip> by_p(S.known);  // by (h, t, r): the relations of a pair are one run
+  std::sort(by_p.begin(), by_p.end(), by_htr);
+  std::vector<int64_t> hoff(1, 0), toff(1, 0), roff(1, 0);
+  std::vector<int32_t> hids, tids, rids;
   for (const Trip& q : S.test_list) {
     // heads j with (j, r, t) known: rows of by_t with t = q.t, r = q.r (sorted by h)
     auto a = std::lower_bound(by_t.begin(), by_t.end(), Trip{kLowest, q.r, q.t}, by_trh);
@@ -263,15 +283,25 @@ void test_device() {
       if (tids.empty() || toff.back() == (int64_t)tids.size() || tids.back() != (int32_t)it->t)
         tids.push_back((int32_t)it->t);
     toff.push_back((int64_t)tids.size());
+    // relations j with (h, j, t) known (Test.h:209 `_find(h, t, j)`)
+    auto c = std::lower_bound(by_p.begin(), by_p.end(), Trip{q.h, kLowest, q.t}, by_htr);
+    for (auto it = c; it != by_p.end() && it->h == q.h && it->t == q.t; ++it)
+      if (roff.back() == (int64_t)rids.size() || rids.back() != (int32_t)it->r) rids.push_back((int32_t)it->r);
+    roff.push_back((int64_t)rids.size());
   }
   S.hoff = hoff;
   S.toff = toff;
+  S.roff = roff;
   D.d_hids = upload(hids);
   D.d_tids = upload(tids);
+  D.d_rids = upload(rids);
   if (S.have_types) {
     const INT words = (S.ent_total + 31) / 32;
     std::vector<uint32_t> th((size_t)(S.rel_total * words), 0u), tt((size_t)(S.rel_total * words), 0u);
-    for (INT r = 0; r < S.rel_total; ++r) {
+    // the type lists are those of the LAST importTypeFiles: after a dataset with more relations was
+    // imported without its own type file they cover fewer relations than rel_total (the rest: none)
+    const INT typed = std::min<INT>(S.rel_total, (INT)std::min(S.head_type.size(), S.tail_type.size()));
+    for (INT r = 0; r < typed; ++r) {
       for (INT e : S.head_type[r])
         if (e >= 0 && e < S.ent_total) th[r * words + (e >> 5)] |= 1u << (e & 31);
       for (INT e : S.tail_type[r])
@@ -280,9 +310,10 @@ void test_device() {
     D.d_th = upload(th);
     D.d_tt = upload(tt);
   }
+  const INT stage_n = std::max<INT>(std::max(S.ent_total, S.rel_total), 1);  // a score vector: E or R floats
   for (int i = 0; i < Device::kRing; ++i) {
-    HIP_OR_DIE(hipHostMalloc(&D.h_stage[i], sizeof(float) * std::max<INT>(S.ent_total, 1), hipHostMallocDefault));
-    HIP_OR_DIE(hipMalloc(&D.d_con[i], sizeof(float) * std::max<INT>(S.ent_total, 1)));
+    HIP_OR_DIE(hipHostMalloc(&D.h_stage[i], sizeof(float) * stage_n, hipHostMallocDefault));
+    HIP_OR_DIE(hipMalloc(&D.d_con[i], sizeof(float) * stage_n));
     HIP_OR_DIE(hipEventCreateWithFlags(&D.ev[i], hipEventDisableTiming));
   }
   HIP_OR_DIE(hipStreamSynchronize(D.st));
@@ -330,6 +361,30 @@ __global__ __launch_bounds__(1024) void k_rank_scores(const float* __restrict__ 
   if (threadIdx.x < 4) out[threadIdx.x] = s[threadIdx.x];
 }
 
+// the caller's n scores into the next staging slot and on to the device; returns the slot
+int stage_scores(const REAL* con, INT n) {
+  const int ring = (int)(S.ring_seq++ % Device::kRing);
+  HIP_OR_DIE(hipEventSynchronize(D.ev[ring]));  // staging slot free again
+  memcpy(D.h_stage[ring], con, sizeof(float) * n);
+  HIP_OR_DIE(hipMemcpyAsync(D.d_con[ring], D.h_stage[ring], sizeof(float) * n, hipMemcpyHostToDevice, D.st));
+  return ring;
+}
+
+// grow a [slot][4] count array to hold `slot` (rare: sized for one evaluation)
+void reserve_slots(int32_t*& counts, int64_t& cap, int64_t slot, int64_t per_eval) {
+  if (slot < cap) return;
+  HIP_OR_DIE(hipStreamSynchronize(D.st));
+  const int64_t ncap = std::max<int64_t>(per_eval, 2 * cap) + 16;
+  int32_t* n = nullptr;
+  HIP_OR_DIE(hipMalloc(&n, sizeof(int32_t) * 4 * ncap));
+  if (counts) {
+    HIP_OR_DIE(hipMemcpy(n, counts, sizeof(int32_t) * 4 * cap, hipMemcpyDeviceToDevice));
+    HIP_OR_DIE(hipFree(counts));
+  }
+  counts = n;
+  cap = ncap;
+}
+
 void rank_call(const REAL* con, INT idx, bool tc, int side) {
   if (idx < 0 || idx >= S.test_total)
     fail(MMRE_ERR_ARG, "test index " + std::to_string((long)idx) + " out of range [0, " +
@@ -337,23 +392,8 @@ void rank_call(const REAL* con, INT idx, bool tc, int side) {
   if (tc && !S.have_types) fail(MMRE_ERR_ARG, "type_constrain requires importTypeFiles()");
   test_device();
   const int64_t slot = (int64_t)S.calls.size();
-  if (slot >= D.slot_cap) {  // grow the count array (rare: sized for one evaluation)
-    HIP_OR_DIE(hipStreamSynchronize(D.st));
-    const int64_t cap = std::max<int64_t>(2 * S.test_total, 2 * D.slot_cap) + 16;
-    int32_t* n = nullptr;
-    HIP_OR_DIE(hipMalloc(&n, sizeof(int32_t) * 4 * cap));
-    if (D.d_counts) {
-      HIP_OR_DIE(hipMemcpy(n, D.d_counts, sizeof(int32_t) * 4 * D.slot_cap, hipMemcpyDeviceToDevice));
-      HIP_OR_DIE(hipFree(D.d_counts));
-    }
-    D.d_counts = n;
-    D.slot_cap = cap;
-  }
-  const int ring = (int)(slot % Device::kRing);
-  HIP_OR_DIE(hipEventSynchronize(D.ev[ring]));  // staging slot free again
-  memcpy(D.h_stage[ring], con, sizeof(float) * S.ent_total);
-  HIP_OR_DIE(hipMemcpyAsync(D.d_con[ring], D.h_stage[ring], sizeof(float) * S.ent_total, hipMemcpyHostToDevice,
-                            D.st));
+  reserve_slots(D.d_counts, D.slot_cap, slot, 2 * S.test_total);
+  const int ring = stage_scores(con, S.ent_total);
   const Trip& q = S.test_list[idx];
   const int32_t* ids = side == 0 ? D.d_hids : D.d_tids;
   const std::vector<int64_t>& oh = side == 0 ? S.hoff : S.toff;
@@ -365,6 +405,28 @@ void rank_call(const REAL* con, INT idx, bool tc, int side) {
   HIP_OR_DIE(hipGetLastError());
   HIP_OR_DIE(hipEventRecord(D.ev[ring], D.st));
   S.calls.push_back({side, tc});
+}
+
+// testRel (Test.h:194-228): the R predictions of test triple lastRel ranked against its true
+// relation; the known relations of (h, t) are the filter list. Same kernel as testHead /
+// testTail (the candidates are relations, no type rows); columns 0, 1 = raw, filtered.
+void rel_rank_call(const REAL* con) {
+  const INT idx = S.last_rel;
+  if (idx < 0 || idx >= S.test_total)
+    fail(MMRE_ERR_ARG, "test index " + std::to_string((long)idx) + " out of range [0, " +
+                           std::to_string((long)S.test_total) + ")");
+  test_device();
+  const int64_t slot = S.rel_calls;
+  reserve_slots(D.d_rel_counts, D.rel_slot_cap, slot, S.test_total);
+  const int ring = stage_scores(con, S.rel_total);
+  const Trip& q = S.test_list[idx];
+  hipLaunchKernelGGL(k_rank_scores, dim3(1), dim3(1024), 0, D.st, D.d_con[ring], S.rel_total, q.r,
+                     D.d_rids + S.roff[idx], S.roff[idx + 1] - S.roff[idx], (const uint32_t*)nullptr,
+                     D.d_rel_counts + 4 * slot);
+  HIP_OR_DIE(hipGetLastError());
+  HIP_OR_DIE(hipEventRecord(D.ev[ring], D.st));
+  S.rel_calls++;
+  S.last_rel++;
 }
 
 // --------------------------------------------------------------- readers ----
@@ -587,9 +649,61 @@ static void sampling_impl(INT* batch_h, INT* batch_t, INT* batch_r, REAL* batch_
 
 // ---------------------------------------------------------------- Test.h ----
 static void initTest_impl() {
-  S.last_head = S.last_tail = 0;
+  S.last_head = S.last_tail = S.last_rel = 0;
   if (D.test_ready) HIP_OR_DIE(hipStreamSynchronize(D.st));
   S.calls.clear();
+  // unlike Test.h:29 (shadowing locals): the relation-prediction sums start over as well
+  S.rel_calls = 0;
+  for (REAL& v : S.rel_metrics) v = 0;
+}
+
+// Test.h:55-62: the R rows (h, j, t) of test triple lastRel; lastRel is NOT advanced (testRel does)
+static void getRelBatch_impl(INT* ph, INT* pt, INT* pr) {
+  if (S.last_rel < 0 || S.last_rel >= S.test_total)
+    fail(MMRE_ERR_ARG, "test index " + std::to_string((long)S.last_rel) + " out of range [0, " +
+                           std::to_string((long)S.test_total) + ")");
+  const Trip& q = S.test_list[(size_t)S.last_rel];
+  for (INT i = 0; i < S.rel_total; ++i) {
+    ph[i] = q.h;
+    pt[i] = q.t;
+    pr[i] = i;
+  }
+}
+
+// Test.h:329-354: testRel's float accumulation (Test.h:215-225) over the calls since initTest, in
+// call order, / testTotal, and the reference's printout
+static void test_relation_prediction_impl() {
+  const int64_t n = S.rel_calls;
+  if (n > D.rel_slot_cap)  // the test files were imported again after those calls: their counts are gone
+    fail(MMRE_ERR_ARG, "test_relation_prediction: call initTest() after importTestFiles()");
+  std::vector<int32_t> c((size_t)(4 * n + 4));
+  if (n) {
+    HIP_OR_DIE(hipStreamSynchronize(D.st));
+    HIP_OR_DIE(hipMemcpy(c.data(), D.d_rel_counts, sizeof(int32_t) * 4 * n, hipMemcpyDeviceToHost));
+  }
+  REAL acc[2][5] = {};  // [raw, filter][tot10, tot3, tot1, rank, reci]
+  for (int64_t i = 0; i < n; ++i)
+    for (int v = 0; v < 2; ++v) {
+      const INT s = c[4 * i + v];
+      REAL* a = acc[v];
+      if (s < 10) a[0] += 1;
+      if (s < 3) a[1] += 1;
+      if (s < 1) a[2] += 1;
+      a[3] += (REAL)(s + 1);
+      a[4] = (REAL)((double)a[4] + 1.0 / (double)(s + 1));
+    }
+  const REAL tot = (REAL)S.test_total;
+  for (int v = 0; v < 2; ++v)
+    for (int f = 0; f < 5; ++f) acc[v][f] /= tot;
+  printf("no type constraint results:\n");
+  printf("metric:\t\t\t MRR \t\t MR \t\t hit@10 \t hit@3  \t hit@1 \n");
+  printf("averaged(raw):\t\t %f \t %f \t %f \t %f \t %f \n", acc[0][4], acc[0][3], acc[0][0], acc[0][1], acc[0][2]);
+  printf("\n");
+  printf("averaged(filter):\t %f \t %f \t %f \t %f \t %f \n", acc[1][4], acc[1][3], acc[1][0], acc[1][1],
+         acc[1][2]);
+  const int f_of[5] = {4, 3, 0, 1, 2};  // mrr, mr, hit10, hit3, hit1
+  for (int g = 0; g < 2; ++g)            // filter, raw
+    for (int m = 0; m < 5; ++m) S.rel_metrics[5 * g + m] = acc[1 - g][f_of[m]];
 }
 
 static void getHeadBatch_impl(INT* ph, INT* pt, INT* pr) {
@@ -755,6 +869,27 @@ extern "C" void getTailBatch(INT* ph, INT* pt, INT* pr) {
 
 extern "C" void test_link_prediction(bool type_constrain) {
   guarded([&] { test_link_prediction_impl(type_constrain); });
+}
+
+extern "C" void getRelBatch(INT* ph, INT* pt, INT* pr) {
+  if (!guarded([&] { getRelBatch_impl(ph, pt, pr); })) {
+    poison<INT>(ph, S.rel_total, -1);
+    poison<INT>(pt, S.rel_total, -1);
+    poison<INT>(pr, S.rel_total, -1);
+  }
+}
+
+extern "C" void testRel(REAL* con) {
+  guarded([&] { rel_rank_call(con); });
+}
+
+extern "C" void test_relation_prediction() {
+  guarded([&] { test_relation_prediction_impl(); });
+}
+
+extern "C" void mmre_base_get_rel_metrics(float* out10) {
+  if (!out10) return;
+  for (int i = 0; i < 10; ++i) out10[i] = g_err_code ? NAN : S.rel_metrics[i];
 }
 
 // ------------------------------------------------------------ error latch ----

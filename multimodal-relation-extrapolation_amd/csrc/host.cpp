@@ -83,6 +83,36 @@ extern "C" int mmre_link_metrics(const int32_t* h_head_counts, const int32_t* h_
   return MMRE_OK;
 }
 
+// testRel's accumulation and test_relation_prediction (Test.h:215-225, :329-344): two serial
+// chains (raw, filtered) of float globals in query order -- `+= 1` on a float, `+= (count + 1)`
+// long -> float, `+= 1.0 / (count + 1)` a double quotient added to the float and stored as
+// float -- then each `/= testTotal` in float. The hit@k sums are small integers, exact in float.
+extern "C" int mmre_rel_metrics(const int32_t* h_counts, int64_t n, int64_t stride, float* h_out) {
+  if (!h_counts || !h_out || n <= 0 || stride < n) return MMRE_ERR_ARG;
+  if (n >= (int64_t)1 << 24) return MMRE_ERR_SHAPE;
+  const float tot = (float)n;
+  for (int g = 0; g < 2; ++g) {  // h_out: filter, raw; counts columns: raw, filter
+    const int32_t* c = h_counts + (int64_t)(1 - g) * stride;
+    float reci = 0.0f, rank = 0.0f;
+    int32_t c10 = 0, c3 = 0, c1 = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t s = c[i];
+      c10 += s < 10;
+      c3 += s < 3;
+      c1 += s < 1;
+      rank += (float)(s + 1);
+      reci = (float)((double)reci + 1.0 / (double)(s + 1));
+    }
+    float* o = h_out + 5 * g;
+    o[0] = reci / tot;
+    o[1] = rank / tot;
+    o[2] = (float)c10 / tot;
+    o[3] = (float)c3 / tot;
+    o[4] = (float)c1 / tot;
+  }
+  return MMRE_OK;
+}
+
 // glibc random() TYPE_3 after srand(1): r[i] = r[i-31] + r[i-3], output r[i+344] >> 1.
 // randReset (Random.h:11-15) seeds thread i with the next rand() of the process.
 extern "C" int mmre_glibc_rand(int64_t skip, int64_t n, int64_t* h_out) {

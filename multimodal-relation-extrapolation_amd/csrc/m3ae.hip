@@ -50,12 +50,6 @@ constexpr int M3_AQ = 16;       // query rows per attention workgroup
 constexpr int M3_AKC = 64;      // most keys per staged K / V chunk
 constexpr int M3_MAXR = 336;    // 1 + M3_MAXLEN
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int sh = 32; sh >= 1; sh >>= 1) v += __shfl_xor(v, sh);
-  return v;
-}
-
 // Plan buffer (int32), n = n_seq:
 //   uniq[n]    unique-sequence index of each input row
 //   src[n]     first input row of each unique sequence

@@ -24,6 +24,15 @@ constexpr int kWave = 64;
 
 __host__ __device__ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// Sum over the wave by the xor butterfly: a + b and b + a agree, so every lane ends with the same
+// total, the same every run. The reduction of every row-wise score chain (ns.hip row_score,
+// relpred.hip): two kernels that feed it the same lane partials get the same bits.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+  return v;
+}
+
 // Small split-K fp32 GEMM (gemm.hip): C = A B / (*div if div) + bias, strided operands;
 // tile_dot[t] = sum over output tile t of C * Wd when both are given. One launch.
 int gemm_launch(hipStream_t st, const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn,

@@ -24,12 +24,6 @@ namespace mmre {
 constexpr int NS_WAVES = 4;  // positives per 256-thread workgroup
 constexpr int NS_MAXK = 512;  // negatives per positive kept in LDS
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
-
 struct NSArgs {
   int model, norm_flag, use_model_margin, dim;
   float model_margin, phase_denom;

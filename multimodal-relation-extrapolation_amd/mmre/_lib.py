@@ -55,6 +55,10 @@ SIGNATURES = {
     "mmre_link_sweep_bf3_rows": (I32, [I32, I32, F32, P, I64, I64, I64, I64, P, P, P, P, P, P, I64, I64, I32, P, P,
                                        P, I64, P]),
     "mmre_link_metrics": (I32, [P, P, I64, I64, P]),
+    "mmre_rel_workspace": (I64, [I32, I64, I32]),
+    "mmre_rel_evaluate": (I32, [I32, I32, I32, F32, P, P, P, P, I64, I64, I32, F32, P, P, P, I64, P, P, P, P, P, P,
+                                I64, P]),
+    "mmre_rel_metrics": (I32, [P, I64, I64, P]),
     "mmre_glibc_rand": (I32, [I64, I64, P]),
     "mmre_sampler_advance": (I32, [P, I64, I64, I64, I64, I64]),
     "mmre_sampler_advance_device": (I32, [P, I64, I64, I64, I64, I64, P]),

@@ -101,6 +101,19 @@ class FilterIndex:
             ids[dst] = gids
         return off, ids
 
+    def relation_filters(self, qh, qt):
+        """Known relations of each pair (qh[i], qt[i]) -- Test.h:209 `_find(h, t, j)` over train +
+        valid + test -- as a per-query CSR (off int64 [Q+1], ids int32, ascending per query) for
+        mmre_rel_evaluate. The (h, t) -> relations order is built from the stored triples on the
+        first call."""
+        if getattr(self, "_ht_key", None) is None:
+            h, r = self._hr_key // self.n_rel, self._hr_key % self.n_rel
+            key = h * self.n_ent + self._hr_val
+            o = np.lexsort((r, key))
+            self._ht_key, self._ht_val = key[o], r[o]
+        qh, qt = (np.asarray(x, np.int64) for x in (qh, qt))
+        return self._gather(self._ht_key, self._ht_val, qh * self.n_ent + qt)
+
     def groups(self, qh, qr, qt, qmode, max_group: int = 64, entity_range=None, order: str = "key"):
         """Filter groups: queries with the same (mode, r, anchor) share their known-entity
         list (Test.h:85 `_find` looks up (r, t) for head_batch, (h, r) for tail_batch).
@@ -471,3 +484,72 @@ def evaluate_link_prediction(spec: ScoreSpec, test_h, test_r, test_t, index: Fil
     counts = res["counts"].cpu().numpy()
     head, tail = counts[:, :n], counts[:, n:]
     return link_metrics(head, tail), (head, tail)
+
+
+# ---------------------------------------------------------------------------------------
+# Relation prediction (Test.h:55-62, :194-228, :329-354): which relation holds between h and t
+# ---------------------------------------------------------------------------------------
+REL_GROUPS = ["filter", "raw"]
+
+
+def relation_sweep(spec: ScoreSpec, qh, qr, qt, filt=None, return_scores=False, buffers=None):
+    """One fused relation-prediction evaluation (mmre_rel_evaluate): for every test triple
+    (qh[i], qr[i], qt[i]) the predictions of (h, j, t) for all relations j -- bit for bit what
+    model.predict returns for those rows -- and the Test.h:200-213 counts. qh/qr/qt int64 device
+    tensors; filt: per-query CSR (off int64, ids int32) device tensors of the known relations of
+    each pair (FilterIndex.relation_filters) or None. buffers: a dict kept between calls (outputs
+    and the workspace are reused). Enqueues only.
+    Returns dict(counts=(2, Q) int32 [raw, filt], truth=(Q,), scores=(Q, R) | None)."""
+    _lib.require_cuda(spec.ent, spec.rel, spec.ent_im, spec.rel_im, qh, qr, qt)
+    dev = spec.ent.device
+    model_id = MODEL_IDS[spec.model]
+    n, n_ent, n_rel = int(qh.shape[0]), int(spec.ent.shape[0]), int(spec.rel.shape[0])
+    c = lambda x: None if x is None else x.detach().contiguous().float()
+    ent, rel, ent_im, rel_im = c(spec.ent), c(spec.rel), c(spec.ent_im), c(spec.rel_im)
+    qh, qr, qt = (x.to(torch.int64).contiguous() for x in (qh, qr, qt))
+    b = buffers if buffers is not None else {}
+    if b.get("rel_n") != n:
+        b["rel_counts"] = torch.empty((2, n), dtype=torch.int32, device=dev)
+        b["rel_truth"] = torch.empty(n, dtype=torch.float32, device=dev)
+        b["rel_n"] = n
+    need = int(_lib.lib().mmre_rel_workspace(model_id, n_rel, int(spec.dim)))
+    wk = b.get("rel_work")
+    if need > 0 and (wk is None or wk.numel() < need):
+        wk = b["rel_work"] = torch.empty(need, dtype=torch.uint8, device=dev)
+    scores = torch.empty((n, n_rel), dtype=torch.float32, device=dev) if return_scores else None
+    off, ids = (None, None) if filt is None else filt
+    call("mmre_rel_evaluate", model_id, int(bool(spec.norm_flag)), int(spec.pred_kind), float(spec.margin), ptr(ent),
+         ptr(ent_im), ptr(rel), ptr(rel_im), n_ent, n_rel, int(spec.dim), float(spec.phase_denom), ptr(qh), ptr(qr),
+         ptr(qt), n, ptr(off), ptr(ids), ptr(b["rel_counts"]), ptr(b["rel_truth"]), ptr(scores),
+         ptr(wk) if need > 0 else None, int(wk.numel()) if need > 0 else 0, stream_ptr(dev))
+    return dict(counts=b["rel_counts"], truth=b["rel_truth"], scores=scores)
+
+
+def rel_metrics(counts: np.ndarray):
+    """testRel's accumulation + test_relation_prediction (Test.h:215-225, :329-344; host C++ in
+    libmmre, the reference's float order and widths). counts: (2, n) int32 = raw, filt."""
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.shape[0] != 2:
+        raise ValueError("counts must be (2, n)")
+    if c.dtype != np.int32 or c.strides[1] != 4 or c.strides[0] % 4:
+        c = np.ascontiguousarray(c, np.int32)
+    out = np.zeros(10, np.float32)
+    call("mmre_rel_metrics", c.ctypes.data, c.shape[1], c.strides[0] // 4, out.ctypes.data)
+    return {g: {m: float(out[5 * gi + mi]) for mi, m in enumerate(METRIC_NAMES)} for gi, g in enumerate(REL_GROUPS)}
+
+
+def evaluate_relation_prediction(spec: ScoreSpec, test_h, test_r, test_t, index: FilterIndex | None = None,
+                                 return_scores: bool = False):
+    """Full OpenKE relation-prediction evaluation in test order (testList sorted by (r, h, t),
+    Reader.h:227): the reference's loop getRelBatch -> predict -> testRel per test triple and
+    test_relation_prediction, as one fused evaluation. Without an index the filtered column
+    equals the raw one. Returns (metrics {"filter": {...}, "raw": {...}}, counts (2, n) numpy
+    [raw, filt][, scores (n, R) numpy])."""
+    test_h, test_r, test_t = (np.asarray(x, np.int64) for x in (test_h, test_r, test_t))
+    dev = spec.ent.device
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    filt = None if index is None else tuple(to(a) for a in index.relation_filters(test_h, test_t))
+    res = relation_sweep(spec, to(test_h), to(test_r), to(test_t), filt=filt, return_scores=return_scores)
+    counts = res["counts"].cpu().numpy()
+    out = (rel_metrics(counts), counts)
+    return out + (res["scores"].cpu().numpy(),) if return_scores else out

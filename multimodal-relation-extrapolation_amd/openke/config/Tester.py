@@ -5,11 +5,12 @@ testHead, per test triple) with ONE fused evaluation on the GPU (mmre.link): eve
 tail-batch sweep of the test set against every entity, filtered and type-constrained ranks
 counted in the sweep's epilogue, then the Test.h metric reduction (test_link_prediction,
 Test.h:232-327) with the reference's float order. Returns (mrr, mr, hit10, hit3, hit1) like
-the reference."""
+the reference. run_relation_prediction does the same for the reference's relation-prediction
+loop (getRelBatch -> predict -> testRel, Test.h:55-62, :194-228, :329-354)."""
 import numpy as np
 import torch
 
-from mmre.link import evaluate_link_prediction
+from mmre.link import evaluate_link_prediction, evaluate_relation_prediction
 
 
 class Tester(object):
@@ -65,6 +66,22 @@ class Tester(object):
             print("type constraint results:")
             print(line("averaged(raw):\t\t", m["raw_tc"]))
             print(line("averaged(filter):\t", m["filter_tc"]))
+
+    def run_relation_prediction(self):
+        """Which relation holds between h and t: the reference's loop getRelBatch -> predict ->
+        testRel per test triple and test_relation_prediction (Test.h:55-62, :194-228, :329-354) as
+        ONE fused evaluation (mmre.link.evaluate_relation_prediction). Prints the lines
+        Test.h:346-353 prints; returns the filtered (mrr, mr, hit10, hit3, hit1)."""
+        dl = self.data_loader
+        metrics, counts = evaluate_relation_prediction(self.model.score_spec(), dl.test_h, dl.test_r, dl.test_t,
+                                                       index=dl.filter_index())
+        self.last = {"metrics": metrics, "counts": counts}
+        print("no type constraint results:")
+        print("metric:\t\t\t MRR \t\t MR \t\t hit@10 \t hit@3  \t hit@1 ")
+        for name, g in (("averaged(raw):\t\t", metrics["raw"]), ("\naveraged(filter):\t", metrics["filter"])):
+            print(f"{name} {g['mrr']:f} \t {g['mr']:f} \t {g['hit10']:f} \t {g['hit3']:f} \t {g['hit1']:f} ")
+        grp = metrics["filter"]
+        return grp["mrr"], grp["mr"], grp["hit10"], grp["hit3"], grp["hit1"]
 
     def run_triple_classification(self, threshlod=None):
         raise NotImplementedError("triple classification is outside the MI355X hot path (SURVEY.md §2 row 7)")
