@@ -448,7 +448,8 @@ int mmre_ns_forward(int model, int norm_flag, float model_margin, int use_model_
  * atomics: each scored row files its h / r / t gradient rows as slot records in its table
  * rows' buckets and one wave per table row sums them in batch order (bit-identical run to
  * run). d_work: >= mmre_rows_backward_workspace(model, batch * (1 + neg), n_ent, n_rel, dim)
- * floats. dim <= 512. */
+ * floats. dim <= 2048 and neg <= 512 (mmre_ns_rows_supported), MMRE_ERR_SHAPE otherwise, before
+ * anything is launched. */
 int64_t mmre_rows_backward_workspace(int model, int64_t n_rows, int64_t n_ent, int64_t n_rel, int dim);
 int mmre_ns_backward(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
                      const float* d_ent_im, const float* d_rel, const float* d_rel_im, int dim,
@@ -473,7 +474,18 @@ int mmre_ns_backward(int model, int norm_flag, float model_margin, int use_model
  *   gradient is a slot pass (one wave per positive) + the row-owner pass.
  * Replaces strategy NegativeSampling.forward + loss.backward() (NegativeSampling.py:23-32,
  * Trainer.py:43-54) for one batch. d_work: >= mmre_ns_fused_workspace(model, norm_flag, B, k,
- * n_ent, n_rel, dim) floats, kept between the two calls. */
+ * n_ent, n_rel, dim) floats, kept between the two calls.
+ * The fused entry points (and the one-call steps below) serve exactly the shapes for which
+ * mmre_ns_fused_supported returns 1, and return MMRE_ERR_SHAPE for any other before anything is
+ * launched -- the forward too: no loss is returned whose gradient call would then fail. */
+/* Host-only, no device needed. 1 when the fused entry points have kernels for (model, dim, neg,
+ * loss_kind = MMRE_LOSS_*), else 0 (an unknown model or loss kind, dim <= 0 or neg < 0 included):
+ *   TransE L1 / L2: the margin loss, dim <= 512, neg <= 32;
+ *   DistMult / ComplEx / RotatE: any of the three losses, dim <= 512, neg <= 512.
+ * Every other training shape is the rows path's (mmre_ns_forward[_ex] + mmre_ns_backward[_ex]):
+ * mmre_ns_rows_supported is 1 for 0 < dim <= 2048 and 0 <= neg <= 512, any model, any loss. */
+int mmre_ns_fused_supported(int model, int dim, int64_t neg, int loss_kind);
+int mmre_ns_rows_supported(int dim, int64_t neg);
 int64_t mmre_ns_fused_workspace(int model, int norm_flag, int64_t batch, int64_t neg, int64_t n_ent, int64_t n_rel,
                                 int dim);
 int mmre_ns_fused_forward(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,

@@ -2432,6 +2432,7 @@ extern "C" int mmre_ns_backward_ex(int model, int norm_flag, float model_margin,
   if (opts) A.loss_kind = opts->loss_kind;
   if (!d_score || !d_grad_ent || !d_grad_rel || !d_work || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
   if (model == MMRE_COMPLEX && (!d_grad_ent_im || !d_grad_rel_im)) return MMRE_ERR_ARG;
+  if (gen_nc_rows(dim) == 0 || neg > NS_MAXK) return MMRE_ERR_SHAPE;  // mmre_ns_rows_supported: before any launch
   const int64_t n_rows = batch * (1 + neg);
   RowsWs w;
   rows_ws(model, n_rows, n_ent, n_rel, dim, w);
@@ -2545,6 +2546,27 @@ static bool fused_fast(const NSArgs& A) {
 // elements per lane of the row-owner path of the other models (d <= 512)
 static int gen_nc(int dim) { return dim <= 64 ? 1 : dim <= 128 ? 2 : dim <= 256 ? 4 : dim <= 512 ? 8 : 0; }
 
+// the shapes the fused entry points and the one-call steps have kernels for (model, dim, K and
+// loss_kind of A): TransE the fused margin kernel's, the other models the generic kernels'
+static bool fused_supported(const NSArgs& A) {
+  if (A.dim <= 0 || A.K < 0) return false;
+  if (is_transe(A.model)) return fused_fast(A);
+  if (A.model != MMRE_DISTMULT && A.model != MMRE_COMPLEX && A.model != MMRE_ROTATE) return false;
+  if (A.loss_kind != MMRE_LOSS_MARGIN && A.loss_kind != MMRE_LOSS_SOFTPLUS && A.loss_kind != MMRE_LOSS_SIGMOID)
+    return false;
+  return gen_nc(A.dim) != 0 && A.K <= NS_MAXK;
+}
+
+extern "C" int mmre_ns_fused_supported(int model, int dim, int64_t neg, int loss_kind) {
+  NSArgs A{};
+  A.model = model; A.dim = dim; A.K = neg; A.loss_kind = loss_kind;
+  return fused_supported(A) ? 1 : 0;
+}
+
+extern "C" int mmre_ns_rows_supported(int dim, int64_t neg) {
+  return dim > 0 && gen_nc_rows(dim) != 0 && neg >= 0 && neg <= NS_MAXK ? 1 : 0;
+}
+
 extern "C" int mmre_ns_fused_forward_ex(int model, int norm_flag, float model_margin, int use_model_margin,
                                         const float* d_ent, const float* d_ent_im, const float* d_rel,
                                         const float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim,
@@ -2562,21 +2584,18 @@ extern "C" int mmre_ns_fused_forward_ex(int model, int norm_flag, float model_ma
   // TransE under Softplus / Sigmoid is the rows path's (mmre_ns_forward_ex / mmre_ns_backward_ex)
   if (is_transe(model) && A.loss_kind != MMRE_LOSS_MARGIN) return MMRE_ERR_MODEL;
   if (!d_score || !d_loss || !d_work || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
-  if (neg > NS_MAXK) return MMRE_ERR_SHAPE;
+  // the gradient call has no kernel for any other shape (those are the rows path's): refused here,
+  // not after a loss was returned
+  if (!fused_supported(A)) return MMRE_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   FusedWs w;
   fused_ws(model, norm_flag, batch, neg, n_ent, n_rel, dim, w);
   float* part = d_work + w.part;
   NSSlots S = ws_slots(d_work, w, n_ent, n_rel);
-  if (!fused_fast(A)) {  // other models: scores + partials (zeroing the bucket counts), then the loss
+  if (!is_transe(model)) {  // other models: scores + partials (zeroing the bucket counts), then the loss
     const int gnc = gen_nc(dim);
-    if (!is_transe(model) && gnc == 0) return MMRE_ERR_SHAPE;
-    const dim3 fgrid((unsigned)((batch + NS_WAVES - 1) / NS_WAVES));
-    if (is_transe(model)) {
-      hipLaunchKernelGGL(k_ns_forward, fgrid, dim3(256), 0, st, A, d_score, part, S.counts, n_ent + n_rel + 1);
-    } else {
-      // k_ns_gen_forward: DistMult a workgroup per positive, the two-half models a wave per positive
-      const dim3 fgrid((unsigned)(model == MMRE_DISTMULT ? batch : (batch + NS_WAVES - 1) / NS_WAVES));
+    // k_ns_gen_forward: DistMult a workgroup per positive, the two-half models a wave per positive
+    const dim3 fgrid((unsigned)(model == MMRE_DISTMULT ? batch : (batch + NS_WAVES - 1) / NS_WAVES));
 #define MMRE_NS_GF(NC_, M_)                                                                                        \
   hipLaunchKernelGGL((k_ns_gen_forward<NC_, M_>), fgrid, dim3(256), 0, st, A, d_score, part, S.counts,             \
                      n_ent + n_rel + 1)
@@ -2586,13 +2605,12 @@ extern "C" int mmre_ns_fused_forward_ex(int model, int norm_flag, float model_ma
     else if (model == MMRE_COMPLEX) MMRE_NS_GF(NC_, MMRE_COMPLEX);                                                 \
     else MMRE_NS_GF(NC_, MMRE_ROTATE);                                                                             \
   } while (0)
-      if (gnc == 1) MMRE_NS_GF_M(1);
-      else if (gnc == 2) MMRE_NS_GF_M(2);
-      else if (gnc == 4) MMRE_NS_GF_M(4);
-      else MMRE_NS_GF_M(8);
+    if (gnc == 1) MMRE_NS_GF_M(1);
+    else if (gnc == 2) MMRE_NS_GF_M(2);
+    else if (gnc == 4) MMRE_NS_GF_M(4);
+    else MMRE_NS_GF_M(8);
 #undef MMRE_NS_GF_M
 #undef MMRE_NS_GF
-    }
     MMRE_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_ns_reduce, dim3(1), dim3(256), 0, st, A, part, d_loss);
     MMRE_CHECK_LAUNCH();
@@ -2670,16 +2688,15 @@ static int fused_grad_impl(int model, int norm_flag, float model_margin, int use
   if (!d_score || !d_work || !d_grad_ent || !d_grad_rel || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
   if (model == MMRE_COMPLEX && (!d_grad_ent_im || !d_grad_rel_im)) return MMRE_ERR_ARG;
   if (lr != 0.0f && (!pe || !pr || (model == MMRE_COMPLEX && (!pei || !pri)))) return MMRE_ERR_ARG;
-  if (neg > NS_MAXK) return MMRE_ERR_SHAPE;
+  if (!fused_supported(A)) return MMRE_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   FusedWs w;
   fused_ws(model, norm_flag, batch, neg, n_ent, n_rel, dim, w);
   NSSlots S = ws_slots(d_work, w, n_ent, n_rel, parity);
   const double N = (double)batch * (1.0 + (double)neg);
   const dim3 ogrid((unsigned)((n_ent + n_rel + 3) / 4)), blk(256);
-  if (!fused_fast(A)) {
+  if (!is_transe(model)) {
     const int nc = gen_nc(dim);
-    if (is_transe(model) || nc == 0) return MMRE_ERR_SHAPE;
     const double nterms = model == MMRE_COMPLEX ? 6.0 : 3.0;
     const double ew = model == MMRE_ROTATE ? 2.0 * dim : (double)dim;
     const float reg_ent = regul_rate != 0.0f ? (float)(regul_rate * 2.0 / (nterms * N * ew)) : 0.0f;
@@ -2859,7 +2876,7 @@ static int step_openke_impl(const int64_t* d_train_list, int64_t train_total, co
   int rc = ns_args(A, model, norm_flag, 0.0f, 0, d_ent, nullptr, d_rel, nullptr, dim, 0.0f, d_batch_h, d_batch_t,
                    d_batch_r, batch, neg, loss_margin, adv_temperature, regul_rate);
   if (rc) return rc;
-  if (!is_transe(model) || !fused_fast(A)) return MMRE_ERR_SHAPE;  // the fused TransE path's shapes only
+  if (!is_transe(model) || !fused_supported(A)) return MMRE_ERR_SHAPE;  // the fused TransE path's shapes only
   hipStream_t st = (hipStream_t)stream;
   FusedWs w;
   fused_ws(model, norm_flag, batch, neg, n_ent, n_rel, dim, w);
@@ -2948,7 +2965,7 @@ static int step_openke_gen_impl(const OpenKESamplerArgs& sa, int64_t n_sampler, 
       return MMRE_ERR_ARG;
   }
   const int gnc = gen_nc(dim);
-  if (is_transe(model) || gnc == 0 || neg > NS_MAXK) return MMRE_ERR_SHAPE;
+  if (is_transe(model) || !fused_supported(A)) return MMRE_ERR_SHAPE;
   FusedWs w;
   fused_ws(model, 0, batch, neg, n_ent, n_rel, dim, w);
   NSSlots S = ws_slots(d_work, w, n_ent, n_rel);

@@ -83,6 +83,8 @@ SIGNATURES = {
     "mmre_ns_backward": (I32, [I32, I32, F32, I32, P, P, P, P, I32, F32, P, P, P, I64, I64, F32, F32, F32, P, P, P,
                                P, P, P, I64, I64, P, I64, P]),
     "mmre_rows_backward_workspace": (I64, [I32, I64, I64, I64, I32]),
+    "mmre_ns_fused_supported": (I32, [I32, I32, I64, I32]),
+    "mmre_ns_rows_supported": (I32, [I32, I64]),
     "mmre_ns_fused_workspace": (I64, [I32, I32, I64, I64, I64, I64, I32]),
     "mmre_ns_fused_forward": (I32, [I32, I32, F32, I32, P, P, P, P, I64, I64, I32, F32, P, P, P, I64, I64, F32, F32,
                                     F32, P, P, P, P]),

@@ -21,7 +21,8 @@ import torch
 
 import ctypes
 
-from ._lib import LOSS_KINDS, OPT_ADAGRAD, OPT_SGD, NSOpts, call, lib, mark_written, ptr, require_cuda, stream_ptr
+from ._lib import (LIB_PATH, LOSS_KINDS, OPT_ADAGRAD, OPT_SGD, MMREError, NSOpts, call, lib, mark_written, ptr,
+                   require_cuda, stream_ptr)
 
 MODEL_IDS = {"transe": 0, "transe_l2": 1, "distmult": 2, "complex": 3, "rotate": 4}
 
@@ -38,6 +39,26 @@ class NSSpec:
         self.use_model_margin = model_margin is not None
         self.model_margin = float(model_margin or 0.0)
         self.phase_denom = float(phase_denom)
+
+
+def _query(name, *args) -> bool:
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise MMREError(f"{LIB_PATH} does not export {name}: rebuild it")
+    return bool(fn(*args))
+
+
+def fused_supported(spec: NSSpec, neg: int, kind: int = 0) -> bool:
+    """Whether the fused kernels (mmre_ns_fused_*, the one-call steps) exist for the shape: TransE
+    under the margin loss with dim <= 512 and neg <= 32; DistMult / ComplEx / RotatE under any loss
+    with dim <= 512 and neg <= 512 (mmre_ns_fused_supported, the library's own dispatch rule)."""
+    return _query("mmre_ns_fused_supported", spec.model_id, spec.dim, int(neg), int(kind))
+
+
+def rows_supported(spec: NSSpec, neg: int) -> bool:
+    """Whether the rows path (mmre_ns_forward[_ex] + mmre_ns_backward[_ex]) serves the shape: dim <=
+    2048 and neg <= 512, every model and loss (mmre_ns_rows_supported)."""
+    return _query("mmre_ns_rows_supported", spec.dim, int(neg))
 
 
 def _scalar_args(spec, batch, neg, loss_margin, adv_t, regul_rate):
@@ -67,11 +88,13 @@ def _call_ex(name, opts, *args):
 
 
 class _FusedNS(torch.autograd.Function):
-    """Training (the tables need gradients): mmre_ns_fused_forward in the forward (loss,
-    scores, and the gradient's slot contributions kept in the workspace), mmre_ns_fused_grad
-    in the backward (every row of the gradient tables written, scaled by the upstream
-    gradient; a row-owner pass with no float atomics). Otherwise mmre_ns_forward, with
-    mmre_ns_backward (slots + row owner, no float atomics either) as the backward."""
+    """Training (the tables need gradients) at a shape the fused kernels have (fused_supported):
+    mmre_ns_fused_forward in the forward (loss, scores, and the gradient's slot contributions kept
+    in the workspace), mmre_ns_fused_grad in the backward (every row of the gradient tables
+    written, scaled by the upstream gradient; a row-owner pass with no float atomics). Otherwise
+    -- no gradient wanted, or TransE under softplus / sigmoid, with neg > 32 or any model with dim
+    > 512 -- mmre_ns_forward, with mmre_ns_backward (slots + row owner, no float atomics either)
+    as the backward."""
 
     @staticmethod
     def forward(ctx, ent, rel, ent_im, rel_im, h, t, r, spec, batch, neg, loss_margin, adv_t, regul_rate, events,
@@ -82,9 +105,9 @@ class _FusedNS(torch.autograd.Function):
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         ctx.mark_non_differentiable(score)
         ctx.set_materialize_grads(False)  # no zero-filled gradient for the (non-differentiable) scores
-        # TransE under Softplus / Sigmoid: the rows path (mmre_ns_forward_ex / mmre_ns_backward_ex; the
-        # fused TransE kernel is margin-only), its optimizer step left to optimizer.step()
-        ctx.fused = any(ctx.needs_input_grad[:4]) and not (kind != 0 and spec.model in ("transe", "transe_l2"))
+        # a shape without fused kernels (TransE under Softplus / Sigmoid or with neg > 32, dim > 512): the
+        # rows path (mmre_ns_forward_ex / mmre_ns_backward_ex), its optimizer step left to optimizer.step()
+        ctx.fused = any(ctx.needs_input_grad[:4]) and fused_supported(spec, neg, kind)
         ctx.has_im = ent_im is not None
         ctx.cfg = (spec, batch, neg, loss_margin, adv_t, regul_rate)
         ctx.sgd = sgd if ctx.fused else None
@@ -169,8 +192,10 @@ def fused_ns_loss(spec: NSSpec, ent, rel, h, t, r, batch: int, neg: int, loss_ma
     """Returns (loss scalar tensor, scores (B*(1+k),)). Differentiable w.r.t. the tables.
     loss: "margin" (MarginLoss), "softplus" (SoftplusLoss) or "sigmoid" (SigmoidLoss); the latter
     two ignore loss_margin and weight the negatives by softmax(+T n) under adv_temperature.
-    DistMult / ComplEx / RotatE take the fused kernels for every loss; TransE under softplus /
-    sigmoid takes the rows kernels (no float atomics either; the optimizer's step is then its own).
+    DistMult / ComplEx / RotatE take the fused kernels for every loss at dim <= 512, TransE for the
+    margin loss at dim <= 512 and neg <= 32 (fused_supported); every other shape up to dim 2048 and
+    neg 512 takes the rows kernels (no float atomics either; the optimizer's step is then its own).
+    Beyond that (rows_supported) the call raises MMREError before anything is launched.
     events: optional torch.cuda.Events recorded around the C-ABI calls alone (training mode), for
     kernel timing: (start, end) of mmre_ns_fused_forward, and with four, (start, end) of the
     backward's mmre_ns_fused_grad.
@@ -187,8 +212,12 @@ def fused_ns_loss(spec: NSSpec, ent, rel, h, t, r, batch: int, neg: int, loss_ma
     h, t, r = (x.to(torch.int64).contiguous() for x in (h, t, r))
     if ent.dtype != torch.float32 or rel.dtype != torch.float32:
         raise TypeError("fused_ns_loss: float32 tables")
+    if not rows_supported(spec, neg):
+        raise MMREError(f"fused_ns_loss: unsupported shape (code 3): dim {spec.dim} (<= 2048), neg {int(neg)} (<= 512)")
     tables = [x for x in (ent, rel, ent_im, rel_im) if x is not None]
     sgd = None
+    if optimizer is not None and not fused_supported(spec, neg, kind):
+        optimizer = None  # the rows path has no in-pass step: optimizer.step() updates the tables
     if optimizer is not None and hasattr(optimizer, "fused_state") and spec.model not in OpenKETrainStep.GENERIC:
         optimizer = None  # Adagrad rides in the generic row owner only; TransE: optimizer.step()
     if optimizer is not None and hasattr(optimizer, "fusable_lr"):
@@ -286,6 +315,9 @@ class OpenKETrainStep:
         if not self.generic and (loss != "margin" or adagrad is not None):
             raise ValueError("OpenKETrainStep: TransE takes the margin loss and SGD (its fused kernel is margin-only)")
         self.kind, self.adagrad = LOSS_KINDS[loss], adagrad
+        if int(neg) < 1 or not fused_supported(spec, neg, self.kind):
+            raise ValueError(f"OpenKETrainStep: no fused kernels for {spec.model} at dim {spec.dim}, neg {int(neg)} "
+                             f"(mmre.ns.fused_supported; train per batch through fused_ns_loss)")
         if not self.generic and (spec.model not in ("transe", "transe_l2") or spec.use_model_margin):
             raise ValueError("OpenKETrainStep: TransE without a model margin, DistMult, ComplEx or RotatE")
         if (spec.model == "complex") != (ent_im is not None and rel_im is not None):

@@ -114,7 +114,8 @@ class Trainer(object):
             from ..module.loss.SigmoidLoss import SigmoidLoss
             from ..module.loss.SoftplusLoss import SoftplusLoss
             from ..module.strategy.NegativeSampling import NegativeSampling
-            from mmre.ns import OpenKETrainStep
+            from mmre._lib import LOSS_KINDS
+            from mmre.ns import OpenKETrainStep, fused_supported
         except ImportError:
             return None
         m, dl = self.model, self.data_loader
@@ -136,13 +137,12 @@ class Trainer(object):
             # DistMult / ComplEx / RotatE: mmre_ns_step_openke_gen_pipe (the generic kernels' shapes)
             if (spec.model == "complex") != (ent_im is not None and rel_im is not None):
                 return None
-            if spec.dim > 512 or dl.negative_ent > 512 or dl.negative_ent < 1:
-                return None
         else:
             if spec.model not in ("transe", "transe_l2") or spec.use_model_margin or ent_im is not None:
                 return None
-            if spec.dim > 512 or dl.negative_ent > 32 or dl.negative_ent < 1:  # the fused kernel's shapes
-                return None
+        kind = "margin" if hinge else m.loss.fused_args()[0]
+        if dl.negative_ent < 1 or not fused_supported(spec, dl.negative_ent, LOSS_KINDS[kind]):
+            return None  # no fused kernels at this shape (train_one_step: the rows path)
         tables = [x for x in (ent, rel, ent_im, rel_im) if x is not None]
         if not hasattr(self.optimizer, "fusable_lr") or self.optimizer.fusable_lr(tables) is None:
             return None

@@ -68,10 +68,11 @@ def _spec(name):
                   phase_denom=rotate_phase_denom(6.0, 2.0, d) if model == "rotate" else 0.0)
 
 
-def _reference(name, tabs, h, t, r, kind, adv, regul):
-    """float64: (loss, scores, gradients per table, the float64 tables)"""
+def _reference(name, tabs, h, t, r, kind, adv, regul, B=B, model=None):
+    """float64: (loss, scores, gradients per table, the float64 tables). B, model = (model, d,
+    norm_flag): another batch size and model than this file's (tests/test_ns_shapes_gpu.py)."""
     import ref_trainer
-    model, d, nf = MODELS[name]
+    model, d, nf = model or MODELS[name]
     T64 = {k: v.double().requires_grad_(True) for k, v in tabs.items()}
     if model in ("transe", "transe_l2"):
         _, score = ref_trainer.transe_ns_loss(T64["ent"], T64["rel"], h, t, r, B, 0.0, norm_flag=nf,
