@@ -2252,33 +2252,87 @@ __global__ __launch_bounds__(256) void k_rows_slots(NSArgs A, const float* __res
   }
 }
 
-// which TransE fast-path instance fits: elements per lane (0: none, generic path)
-static int transe_fast_nc(const NSArgs& A) {
-  if (A.model != MMRE_TRANSE_L1 && A.model != MMRE_TRANSE_L2) return 0;
-  if (A.K > NS_MAXK) return 0;
-  if (A.dim <= 64) return 1;
-  if (A.dim <= 128) return 2;
-  if (A.dim <= 256) return 4;
-  if (A.dim <= 512) return 8;
+}  // namespace mmre
+
+// ---------------------------------------------------------------------------------------
+// Host side. Every kernel above is named in one place, its launcher (launch_*), which picks the
+// instance through with_nc / with_bool / with_gen_model; the dim -> NC rule is nc_for_dim. An entry
+// point fills one NSCall from its C arguments, validates it in the ABI's order and hands it on.
+// ---------------------------------------------------------------------------------------
+#include <type_traits>
+
+using namespace mmre;
+
+constexpr int NC_FUSED = 8;  // widest instance of the TransE forward and the fused families (dim <= 512)
+constexpr int NC_ROWS = 32;  // ... of the rows backward (dim <= 2,048)
+
+// 64-float chunks per lane (the kernels' NC: 1, 2, 4, ... max_nc) for rows of `dim` floats; 0: no
+// instance. Up to 2,048 floats per row plane in the rows backward (the reference's examples train
+// TransE at dim 1,024 with SigmoidLoss and cross sampling,
+// OpenKE/examples/train_transe_WN18_adv_sigmoidloss.py): the wide instances keep their rows in
+// more registers (they may spill at NC 32; these rows are not a hot shape).
+static int nc_for_dim(int dim, int max_nc) {
+  for (int nc = 1; nc <= max_nc; nc *= 2)
+    if (dim <= nc * kWave) return nc;
   return 0;
 }
 
-static int ns_args(NSArgs& A, int model, int norm_flag, float model_margin, int use_model_margin, const float* ent,
-                   const float* ent_im, const float* rel, const float* rel_im, int dim, float phase_denom,
-                   const int64_t* h, const int64_t* t, const int64_t* r, int64_t batch, int64_t neg,
-                   float loss_margin, float adv_t, float regul_rate) {
-  if (model < MMRE_TRANSE_L1 || model > MMRE_ROTATE) return MMRE_ERR_MODEL;
-  if (!ent || !rel || !h || !t || !r || batch <= 0 || neg < 0 || dim <= 0) return MMRE_ERR_ARG;
-  if (model == MMRE_COMPLEX && (!ent_im || !rel_im)) return MMRE_ERR_ARG;
-  if (model == MMRE_ROTATE && !(phase_denom != 0.0f)) return MMRE_ERR_ARG;
-  A.model = model; A.norm_flag = norm_flag; A.use_model_margin = use_model_margin; A.dim = dim;
-  A.model_margin = model_margin; A.phase_denom = phase_denom;
-  A.ent = ent; A.ent_im = ent_im; A.rel = rel; A.rel_im = rel_im;
-  A.h = h; A.t = t; A.r = r; A.B = batch; A.K = neg;
-  A.loss_margin = loss_margin; A.adv_t = adv_t; A.regul_rate = regul_rate;
-  A.loss_kind = MMRE_LOSS_MARGIN;
-  return MMRE_OK;
+// The launches f(std::integral_constant<int, NC>) makes for nc == NC in 1, 2, 4, ... MAX_NC (no
+// wider instance is built) and their error; anything else is no shape of the family.
+template <int MAX_NC, int NC = 1, class F>
+static int with_nc(int nc, F&& f) {
+  if constexpr (NC > MAX_NC) {
+    return MMRE_ERR_SHAPE;
+  } else {
+    if (nc != NC) return with_nc<MAX_NC, 2 * NC>(nc, f);
+    f(std::integral_constant<int, NC>{});
+    MMRE_CHECK_LAUNCH();
+    return MMRE_OK;
+  }
 }
+
+template <class F>
+static int with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// the models of the generic fused kernels
+template <class F>
+static int with_gen_model(int model, F&& f) {
+  if (model == MMRE_DISTMULT) return f(std::integral_constant<int, MMRE_DISTMULT>{});
+  if (model == MMRE_COMPLEX) return f(std::integral_constant<int, MMRE_COMPLEX>{});
+  if (model == MMRE_ROTATE) return f(std::integral_constant<int, MMRE_ROTATE>{});
+  return MMRE_ERR_MODEL;
+}
+
+static bool is_transe(int model) { return model == MMRE_TRANSE_L1 || model == MMRE_TRANSE_L2; }
+
+// elements per lane of the fused path's instances of the other models (0: none)
+static int gen_nc(int dim) { return nc_for_dim(dim, NC_FUSED); }
+
+// which TransE fast-path instance fits: elements per lane (0: none, generic path)
+static int transe_fast_nc(const NSArgs& A) { return is_transe(A.model) && A.K <= NS_MAXK ? gen_nc(A.dim) : 0; }
+
+struct NSTables {
+  float *ent, *ent_im, *rel, *rel_im;
+};
+
+// One call as the host code hands it on: the entry points fill what they have (the rest stays
+// null / zero) and validate it before anything is launched.
+struct NSCall {
+  NSArgs A{};
+  int64_t n_ent = 0, n_rel = 0;
+  const float* grad_loss = nullptr;  // upstream gradient of the loss (nullptr: 1)
+  NSTables grad{};                   // gradient tables, every row written
+  float lr = 0.0f;                   // != 0: the row owner also steps the tables `upd`
+  NSTables upd{};
+  float* score = nullptr;            // written by the forwards, read by the gradients
+  float* loss = nullptr;             // the forwards' output; a gradient call reduces the loss into it as well
+  float* work = nullptr;
+  hipStream_t st = nullptr;
+  int parity = 0;                    // which of the workspace's two slot-count arrays
+  NSOpt opt{};                       // Adagrad in the generic row owner
+};
 
 // the options' checks that need no other argument (first in every _ex entry point: before any launch)
 static int ns_opts_check(const mmre_ns_opts_t* o) {
@@ -2289,9 +2343,58 @@ static int ns_opts_check(const mmre_ns_opts_t* o) {
   return MMRE_OK;
 }
 
-}  // namespace mmre
+// The options, then the model, then the tables and the batch: C.A (with the options' loss) and
+// the stream. A is the entry point's arguments in NSArgs' order.
+static int ns_call(NSCall& C, const mmre_ns_opts_t* opts, const NSArgs& A, void* stream) {
+  const int rc = ns_opts_check(opts);
+  if (rc) return rc;
+  if (A.model < MMRE_TRANSE_L1 || A.model > MMRE_ROTATE) return MMRE_ERR_MODEL;
+  if (!A.ent || !A.rel || !A.h || !A.t || !A.r || A.B <= 0 || A.K < 0 || A.dim <= 0) return MMRE_ERR_ARG;
+  if (A.model == MMRE_COMPLEX && (!A.ent_im || !A.rel_im)) return MMRE_ERR_ARG;
+  if (A.model == MMRE_ROTATE && !(A.phase_denom != 0.0f)) return MMRE_ERR_ARG;
+  C.A = A;
+  C.A.loss_kind = opts ? opts->loss_kind : MMRE_LOSS_MARGIN;
+  C.st = (hipStream_t)stream;
+  return MMRE_OK;
+}
 
-using namespace mmre;
+// Adagrad's state when the call steps the tables with it: the sum tables (ComplEx: all four)
+static int ns_adagrad(NSCall& C, const mmre_ns_opts_t* opts) {
+  if (!opts || opts->optimizer != MMRE_OPT_ADAGRAD || C.lr == 0.0f) return MMRE_OK;
+  if (!opts->d_sum_ent || !opts->d_sum_rel) return MMRE_ERR_ARG;
+  if (C.A.model == MMRE_COMPLEX && (!opts->d_sum_ent_im || !opts->d_sum_rel_im)) return MMRE_ERR_ARG;
+  C.opt = NSOpt{1, opts->eps, opts->d_sum_ent, opts->d_sum_ent_im, opts->d_sum_rel, opts->d_sum_rel_im};
+  return MMRE_OK;
+}
+
+// what a gradient call reads (scores or row gradients), its gradient tables and the table sizes
+static int grad_tables_check(const NSCall& C, const float* in) {
+  if (!in || !C.grad.ent || !C.grad.rel || !C.work || C.n_ent <= 0 || C.n_rel <= 0) return MMRE_ERR_ARG;
+  if (C.A.model == MMRE_COMPLEX && (!C.grad.ent_im || !C.grad.rel_im)) return MMRE_ERR_ARG;
+  return MMRE_OK;
+}
+
+// Regularization scale per gathered row, of the entity and of the relation rows (TransE.py:92-102
+// and its kin, without the upstream gradient: the owner pass multiplies by it); A.B positives with
+// A.K negatives each.
+struct RegScale {
+  float ent, rel;
+};
+static RegScale reg_scale(const NSArgs& A) {
+  if (A.regul_rate == 0.0f) return {0.0f, 0.0f};
+  const double N = (double)A.B * (1.0 + (double)A.K);
+  const double nterms = A.model == MMRE_COMPLEX ? 6.0 : 3.0;
+  const double ew = A.model == MMRE_ROTATE ? 2.0 * A.dim : (double)A.dim;
+  return {(float)(A.regul_rate * 2.0 / (nterms * N * ew)), (float)(A.regul_rate * 2.0 / (nterms * N * A.dim))};
+}
+
+static int64_t al64(int64_t x) { return (x + 63) & ~(int64_t)63; }
+
+static int launch_reduce(const NSArgs& A, float* part, float* d_loss, hipStream_t st) {
+  hipLaunchKernelGGL(k_ns_reduce, dim3(1), dim3(256), 0, st, A, part, d_loss);  // the loss, fixed order
+  MMRE_CHECK_LAUNCH();
+  return MMRE_OK;
+}
 
 extern "C" int64_t mmre_ns_workspace(int64_t batch, int64_t neg) {
   (void)neg;
@@ -2304,39 +2407,30 @@ extern "C" int mmre_ns_forward_ex(int model, int norm_flag, float model_margin, 
                                   const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin,
                                   float adv_temperature, float regul_rate, float* d_score, float* d_loss, float* d_work,
                                   void* stream, const mmre_ns_opts_t* opts) {
-  NSArgs A;
-  int rc = ns_opts_check(opts);
+  NSCall C;
+  int rc = ns_call(C, opts,
+                   NSArgs{model, norm_flag, use_model_margin, dim, model_margin, phase_denom, d_ent, d_ent_im, d_rel,
+                          d_rel_im, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate},
+                   stream);
   if (rc) return rc;
-  rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
-               phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
-  if (rc) return rc;
-  if (opts) A.loss_kind = opts->loss_kind;
   if (!d_score || !d_work) return MMRE_ERR_ARG;
   if (neg > NS_MAXK) return MMRE_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
+  const NSArgs& A = C.A;
   const int nc = transe_fast_nc(A);
-  const dim3 grid((unsigned)batch), blk(256);
-  const bool l2 = model == MMRE_TRANSE_L2;
-#define MMRE_NS_FWD(NC_)                                                                              \
-  do {                                                                                                \
-    if (l2) hipLaunchKernelGGL((k_ns_transe_forward<NC_, true>), grid, blk, 0, st, A, d_score, d_work); \
-    else hipLaunchKernelGGL((k_ns_transe_forward<NC_, false>), grid, blk, 0, st, A, d_score, d_work);   \
-  } while (0)
-  if (nc == 1) MMRE_NS_FWD(1);
-  else if (nc == 2) MMRE_NS_FWD(2);
-  else if (nc == 4) MMRE_NS_FWD(4);
-  else if (nc == 8) MMRE_NS_FWD(8);
-  else {
-    hipLaunchKernelGGL(k_ns_forward, dim3((unsigned)((batch + NS_WAVES - 1) / NS_WAVES)), dim3(256), 0, st, A,
+  if (nc == 0) {  // the generic kernel: any model, any dim
+    hipLaunchKernelGGL(k_ns_forward, dim3((unsigned)((batch + NS_WAVES - 1) / NS_WAVES)), dim3(256), 0, C.st, A,
                        d_score, d_work, nullptr, (int64_t)0);
-  }
-#undef MMRE_NS_FWD
-  MMRE_CHECK_LAUNCH();
-  if (d_loss) {
-    hipLaunchKernelGGL(k_ns_reduce, dim3(1), dim3(256), 0, st, A, d_work, d_loss);
     MMRE_CHECK_LAUNCH();
+  } else {
+    rc = with_bool(model == MMRE_TRANSE_L2, [&](auto l2_) {
+      return with_nc<NC_FUSED>(nc, [&](auto nc_) {
+        hipLaunchKernelGGL((k_ns_transe_forward<decltype(nc_)::value, decltype(l2_)::value>), dim3((unsigned)batch),
+                           dim3(256), 0, C.st, A, d_score, d_work);
+      });
+    });
+    if (rc) return rc;
   }
-  return MMRE_OK;
+  return d_loss ? launch_reduce(A, d_work, d_loss, C.st) : MMRE_OK;
 }
 
 extern "C" int mmre_ns_forward(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
@@ -2354,65 +2448,46 @@ extern "C" int mmre_ns_forward(int model, int norm_flag, float model_margin, int
 struct RowsWs {
   int64_t coef, rec, counts, bucket, ovf, total;
 };
-static int64_t al64r(int64_t x) { return (x + 63) & ~(int64_t)63; }
-static void rows_ws(int model, int64_t n_rows, int64_t E, int64_t R, int d, RowsWs& w) {
+static RowsWs rows_ws(int model, int64_t n_rows, int64_t E, int64_t R, int d) {
+  RowsWs w;
   const int64_t width = (model == MMRE_COMPLEX || model == MMRE_ROTATE) ? 2 * (int64_t)d : d;
   int64_t o = 0;
-  w.coef = o;   o = al64r(o + n_rows);
-  w.rec = o;    o = al64r(o + 3 * n_rows * width);
-  w.counts = o; o = al64r(o + E + R + 1);
-  w.bucket = o; o = al64r(o + 2 * (E + R) * NS_BUCKET);
-  w.ovf = o;    o = al64r(o + 4 * 3 * n_rows);
+  w.coef = o;   o = al64(o + n_rows);
+  w.rec = o;    o = al64(o + 3 * n_rows * width);
+  w.counts = o; o = al64(o + E + R + 1);
+  w.bucket = o; o = al64(o + 2 * (E + R) * NS_BUCKET);
+  w.ovf = o;    o = al64(o + 4 * 3 * n_rows);
   w.total = o;
+  return w;
 }
 
 extern "C" int64_t mmre_rows_backward_workspace(int model, int64_t n_rows, int64_t n_ent, int64_t n_rel, int dim) {
   if (n_rows <= 0 || n_ent <= 0 || n_rel <= 0 || dim <= 0) return 0;
-  RowsWs w;
-  rows_ws(model, n_rows, n_ent, n_rel, dim, w);
-  return w.total;
+  return rows_ws(model, n_rows, n_ent, n_rel, dim).total;
 }
 
-// 64-float chunks per lane of the rows backward's slot / owner kernels. Up to 2,048 floats per
-// row plane (the reference's examples train TransE at dim 1,024 with SigmoidLoss and cross
-// sampling, OpenKE/examples/train_transe_WN18_adv_sigmoidloss.py): the wide instances keep
-// their rows in more registers (they may spill at NC 32; these rows are not a hot shape).
-static int gen_nc_rows(int dim) {
-  return dim <= 64 ? 1 : dim <= 128 ? 2 : dim <= 256 ? 4 : dim <= 512 ? 8 : dim <= 1024 ? 16 : dim <= 2048 ? 32 : 0;
-}
-
-// coefficients in w.coef already (or to be read from d_coef): slots, then the owner pass
-static int rows_backward_impl(const NSArgs& A, const float* d_coef, int64_t n_rows, int64_t n_ent, int64_t n_rel,
-                              float reg_ent, float reg_rel, const float* d_grad_loss, float* d_grad_ent,
-                              float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work,
-                              const RowsWs& w, hipStream_t st) {
-  const int nc = gen_nc_rows(A.dim);
-  if (nc == 0) return MMRE_ERR_SHAPE;
-  if (n_ent + n_rel >= (int64_t)UINT32_MAX || 3 * n_rows >= (int64_t)INT32_MAX) return MMRE_ERR_SHAPE;
-  int32_t* counts = reinterpret_cast<int32_t*>(d_work + w.counts);
-  NSSlots S{nullptr, d_work + w.rec, counts, reinterpret_cast<int64_t*>(d_work + w.bucket),
-            reinterpret_cast<int64_t*>(d_work + w.ovf), counts + n_ent + n_rel, (uint32_t)(n_ent + n_rel)};
-  MMRE_CHECK(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)(n_ent + n_rel + 1), st));
-  const dim3 sgrid((unsigned)((n_rows + NS_WAVES - 1) / NS_WAVES)), ogrid((unsigned)((n_ent + n_rel + 3) / 4)),
+// The rows backward of the C.A.B rows whose coefficients are at d_coef: their slots, then the owner
+// pass over the table rows.
+static int launch_rows(const NSCall& C, const float* d_coef, RegScale reg, const RowsWs& w) {
+  const NSArgs& A = C.A;
+  const int64_t n_rows = A.B, n_keys = C.n_ent + C.n_rel;
+  const int nc = nc_for_dim(A.dim, NC_ROWS);
+  if (nc == 0 || n_keys >= (int64_t)UINT32_MAX || 3 * n_rows >= (int64_t)INT32_MAX) return MMRE_ERR_SHAPE;
+  int32_t* counts = reinterpret_cast<int32_t*>(C.work + w.counts);
+  const NSSlots S{nullptr, C.work + w.rec, counts, reinterpret_cast<int64_t*>(C.work + w.bucket),
+                  reinterpret_cast<int64_t*>(C.work + w.ovf), counts + n_keys, (uint32_t)n_keys};
+  MMRE_CHECK(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)(n_keys + 1), C.st));
+  const dim3 sgrid((unsigned)((n_rows + NS_WAVES - 1) / NS_WAVES)), ogrid((unsigned)((n_keys + 3) / 4)),
       hgrid(ogrid.x + NS_HUB_WG), blk(256);
-  const int with_reg = (reg_ent != 0.0f || reg_rel != 0.0f) ? 1 : 0;
-#define MMRE_ROWS(NC_)                                                                                              \
-  do {                                                                                                              \
-    hipLaunchKernelGGL((k_rows_slots<NC_>), sgrid, blk, 0, st, A, d_coef, n_rows, S, n_ent, with_reg);              \
-    hipLaunchKernelGGL((k_ns_gen_owner<NC_>), hgrid, blk, 0, st, A, n_ent, n_rel, reg_ent, reg_rel, S.rec, S.counts, \
-                       S.bucket, S.ovf, S.ovf_n, 0, d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel,             \
-                       d_grad_rel_im, 0.0f, nullptr, nullptr, nullptr, nullptr, (int64_t)NS_HUB_WG, NS_HUB_WG,        \
-                       3 * n_rows, nullptr, nullptr, (int64_t)-1, NSNext{}, NSOpt{});                               \
-  } while (0)
-  if (nc == 1) MMRE_ROWS(1);
-  else if (nc == 2) MMRE_ROWS(2);
-  else if (nc == 4) MMRE_ROWS(4);
-  else if (nc == 8) MMRE_ROWS(8);
-  else if (nc == 16) MMRE_ROWS(16);
-  else MMRE_ROWS(32);
-#undef MMRE_ROWS
-  MMRE_CHECK_LAUNCH();
-  return MMRE_OK;
+  const int with_reg = (reg.ent != 0.0f || reg.rel != 0.0f) ? 1 : 0;
+  return with_nc<NC_ROWS>(nc, [&](auto nc_) {
+    constexpr int NC = decltype(nc_)::value;
+    hipLaunchKernelGGL((k_rows_slots<NC>), sgrid, blk, 0, C.st, A, d_coef, n_rows, S, C.n_ent, with_reg);
+    hipLaunchKernelGGL((k_ns_gen_owner<NC>), hgrid, blk, 0, C.st, A, C.n_ent, C.n_rel, reg.ent, reg.rel, S.rec,
+                       S.counts, S.bucket, S.ovf, S.ovf_n, 0, C.grad_loss, C.grad.ent, C.grad.ent_im, C.grad.rel,
+                       C.grad.rel_im, 0.0f, nullptr, nullptr, nullptr, nullptr, (int64_t)NS_HUB_WG, NS_HUB_WG,
+                       3 * n_rows, nullptr, nullptr, (int64_t)-1, NSNext{}, NSOpt{});
+  });
 }
 
 extern "C" int mmre_ns_backward_ex(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2423,36 +2498,29 @@ extern "C" int mmre_ns_backward_ex(int model, int norm_flag, float model_margin,
                                    const float* d_grad_loss, float* d_grad_ent, float* d_grad_ent_im,
                                    float* d_grad_rel, float* d_grad_rel_im, int64_t n_ent, int64_t n_rel,
                                    float* d_work, int64_t work_floats, void* stream, const mmre_ns_opts_t* opts) {
-  NSArgs A;
-  int rc = ns_opts_check(opts);
+  NSCall C;
+  int rc = ns_call(C, opts,
+                   NSArgs{model, norm_flag, use_model_margin, dim, model_margin, phase_denom, d_ent, d_ent_im, d_rel,
+                          d_rel_im, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate},
+                   stream);
   if (rc) return rc;
-  rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
-               phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  C.n_ent = n_ent; C.n_rel = n_rel; C.work = d_work;
+  C.grad_loss = d_grad_loss;
+  C.grad = {d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im};
+  rc = grad_tables_check(C, d_score);
   if (rc) return rc;
-  if (opts) A.loss_kind = opts->loss_kind;
-  if (!d_score || !d_grad_ent || !d_grad_rel || !d_work || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
-  if (model == MMRE_COMPLEX && (!d_grad_ent_im || !d_grad_rel_im)) return MMRE_ERR_ARG;
-  if (gen_nc_rows(dim) == 0 || neg > NS_MAXK) return MMRE_ERR_SHAPE;  // mmre_ns_rows_supported: before any launch
+  // mmre_ns_rows_supported: before any launch
+  if (nc_for_dim(dim, NC_ROWS) == 0 || neg > NS_MAXK) return MMRE_ERR_SHAPE;
   const int64_t n_rows = batch * (1 + neg);
-  RowsWs w;
-  rows_ws(model, n_rows, n_ent, n_rel, dim, w);
+  const RowsWs w = rows_ws(model, n_rows, n_ent, n_rel, dim);
   if (work_floats < w.total) return MMRE_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_ns_row_coef, dim3((unsigned)((batch + NS_WAVES - 1) / NS_WAVES)), dim3(256), 0, st, A, d_score,
-                     d_work + w.coef);
+  hipLaunchKernelGGL(k_ns_row_coef, dim3((unsigned)((batch + NS_WAVES - 1) / NS_WAVES)), dim3(256), 0, C.st, C.A,
+                     d_score, d_work + w.coef);
   MMRE_CHECK_LAUNCH();
-  // regularization scale per gathered row (TransE.py:92-102 and its kin, without the upstream gradient: the
-  // owner pass multiplies by it)
-  const double N = (double)batch * (1.0 + (double)neg);
-  const double nterms = model == MMRE_COMPLEX ? 6.0 : 3.0;
-  const double ew = model == MMRE_ROTATE ? 2.0 * dim : (double)dim;
-  const float reg_ent = regul_rate != 0.0f ? (float)(regul_rate * 2.0 / (nterms * N * ew)) : 0.0f;
-  const float reg_rel = regul_rate != 0.0f ? (float)(regul_rate * 2.0 / (nterms * N * dim)) : 0.0f;
-  NSArgs R = A;
-  R.B = n_rows;
-  R.K = 0;
-  return rows_backward_impl(R, d_work + w.coef, n_rows, n_ent, n_rel, reg_ent, reg_rel, d_grad_loss, d_grad_ent,
-                            d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, w, st);
+  const RegScale reg = reg_scale(C.A);
+  C.A.B = n_rows;  // from here on: the batch's rows, each on its own
+  C.A.K = 0;
+  return launch_rows(C, d_work + w.coef, reg, w);
 }
 
 extern "C" int mmre_ns_backward(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2476,17 +2544,19 @@ extern "C" int mmre_score_rows_backward(int model, int norm_flag, float model_ma
                                         const float* d_grad_score, float* d_grad_ent, float* d_grad_ent_im,
                                         float* d_grad_rel, float* d_grad_rel_im, int64_t n_ent, int64_t n_rel,
                                         float* d_work, int64_t work_floats, void* stream) {
-  NSArgs A;
-  int rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
-                   phase_denom, d_h, d_t, d_r, n_rows, 0, 0.0f, 0.0f, 0.0f);
+  NSCall C;
+  int rc = ns_call(C, nullptr,
+                   NSArgs{model, norm_flag, use_model_margin, dim, model_margin, phase_denom, d_ent, d_ent_im, d_rel,
+                          d_rel_im, d_h, d_t, d_r, n_rows, 0, 0.0f, 0.0f, 0.0f},
+                   stream);
   if (rc) return rc;
-  if (!d_grad_score || !d_grad_ent || !d_grad_rel || !d_work || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
-  if (model == MMRE_COMPLEX && (!d_grad_ent_im || !d_grad_rel_im)) return MMRE_ERR_ARG;
-  RowsWs w;
-  rows_ws(model, n_rows, n_ent, n_rel, dim, w);
+  C.n_ent = n_ent; C.n_rel = n_rel; C.work = d_work;
+  C.grad = {d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im};
+  rc = grad_tables_check(C, d_grad_score);
+  if (rc) return rc;
+  const RowsWs w = rows_ws(model, n_rows, n_ent, n_rel, dim);
   if (work_floats < w.total) return MMRE_ERR_WORKSPACE;
-  return rows_backward_impl(A, d_grad_score, n_rows, n_ent, n_rel, 0.0f, 0.0f, nullptr, d_grad_ent, d_grad_ent_im,
-                            d_grad_rel, d_grad_rel_im, d_work, w, (hipStream_t)stream);
+  return launch_rows(C, d_grad_score, RegScale{0.0f, 0.0f}, w);
 }
 
 // Workspace of the fused path, in 4-byte words, 256-B aligned pieces: loss partials, row
@@ -2499,11 +2569,8 @@ struct FusedWs {
   uint32_t sentinel;
 };
 
-static int64_t al64(int64_t x) { return (x + 63) & ~(int64_t)63; }
-
-static bool is_transe(int model) { return model == MMRE_TRANSE_L1 || model == MMRE_TRANSE_L2; }
-
-static void fused_ws(int model, int norm_flag, int64_t B, int64_t K, int64_t E, int64_t R, int d, FusedWs& w) {
+static FusedWs fused_ws(int model, int norm_flag, int64_t B, int64_t K, int64_t E, int64_t R, int d) {
+  FusedWs w;
   w.slots = (3 + 3 * K) * B;
   w.sentinel = (uint32_t)(E + R);
   w.dpad = (int)round_up(d, kWave);
@@ -2522,6 +2589,10 @@ static void fused_ws(int model, int norm_flag, int64_t B, int64_t K, int64_t E, 
   w.bucket = o;  o = al64(o + 2 * (E + R) * NS_BUCKET);   // int64 entries
   w.ovf = o;     o = al64(o + 4 * w.slots);                // int64 (row, entry) pairs
   w.total = o;
+  return w;
+}
+static FusedWs fused_ws(const NSCall& C) {
+  return fused_ws(C.A.model, C.A.norm_flag, C.A.B, C.A.K, C.n_ent, C.n_rel, C.A.dim);
 }
 
 static NSSlots ws_slots(float* d_work, const FusedWs& w, int64_t E, int64_t R, int parity = 0) {
@@ -2530,27 +2601,30 @@ static NSSlots ws_slots(float* d_work, const FusedWs& w, int64_t E, int64_t R, i
                  reinterpret_cast<int64_t*>(d_work + w.ovf), counts + E + R, w.sentinel};
 }
 
+// the TransE pre-pass's outputs in the workspace: the row norms and (norm_flag; else null) the
+// normalised tables
+struct PrePass {
+  float *nrm_e, *nrm_r, *ent_n, *rel_n;
+};
+static PrePass ws_prepass(const NSCall& C, const FusedWs& w) {
+  const bool nf = C.A.norm_flag != 0;
+  return {C.work + w.nrm_e, C.work + w.nrm_r, nf ? C.work + w.ent_n : nullptr, nf ? C.work + w.rel_n : nullptr};
+}
+
 extern "C" int64_t mmre_ns_fused_workspace(int model, int norm_flag, int64_t batch, int64_t neg, int64_t n_ent,
                                            int64_t n_rel, int dim) {
-  FusedWs w;
-  fused_ws(model, norm_flag, batch > 0 ? batch : 1, neg > 0 ? neg : 0, n_ent > 0 ? n_ent : 0, n_rel > 0 ? n_rel : 0,
-           dim > 0 ? dim : 1, w);
+  const FusedWs w = fused_ws(model, norm_flag, batch > 0 ? batch : 1, neg > 0 ? neg : 0, n_ent > 0 ? n_ent : 0,
+                             n_rel > 0 ? n_rel : 0, dim > 0 ? dim : 1);
   return w.total > 7 * batch ? w.total : 7 * batch;
 }
 
-// the fused TransE kernel's shapes; it is margin-only (k_ns_transe_fused has no other loss head)
-static bool fused_fast(const NSArgs& A) {
-  return A.loss_kind == MMRE_LOSS_MARGIN && transe_fast_nc(A) != 0 && A.K <= NSW * NSF_MAXJ;
-}
-
-// elements per lane of the row-owner path of the other models (d <= 512)
-static int gen_nc(int dim) { return dim <= 64 ? 1 : dim <= 128 ? 2 : dim <= 256 ? 4 : dim <= 512 ? 8 : 0; }
-
 // the shapes the fused entry points and the one-call steps have kernels for (model, dim, K and
-// loss_kind of A): TransE the fused margin kernel's, the other models the generic kernels'
+// loss_kind of A): TransE the fused margin kernel's (k_ns_transe_fused has no other loss head),
+// the other models the generic kernels'
 static bool fused_supported(const NSArgs& A) {
   if (A.dim <= 0 || A.K < 0) return false;
-  if (is_transe(A.model)) return fused_fast(A);
+  if (is_transe(A.model))
+    return A.loss_kind == MMRE_LOSS_MARGIN && transe_fast_nc(A) != 0 && A.K <= NSW * NSF_MAXJ;
   if (A.model != MMRE_DISTMULT && A.model != MMRE_COMPLEX && A.model != MMRE_ROTATE) return false;
   if (A.loss_kind != MMRE_LOSS_MARGIN && A.loss_kind != MMRE_LOSS_SOFTPLUS && A.loss_kind != MMRE_LOSS_SIGMOID)
     return false;
@@ -2564,7 +2638,91 @@ extern "C" int mmre_ns_fused_supported(int model, int dim, int64_t neg, int loss
 }
 
 extern "C" int mmre_ns_rows_supported(int dim, int64_t neg) {
-  return dim > 0 && gen_nc_rows(dim) != 0 && neg >= 0 && neg <= NS_MAXK ? 1 : 0;
+  return dim > 0 && nc_for_dim(dim, NC_ROWS) != 0 && neg >= 0 && neg <= NS_MAXK ? 1 : 0;
+}
+
+// the fused TransE loss kernel (scores, loss partials, slots) behind its pre-pass P
+static int launch_transe_fused(const NSCall& C, const FusedWs& w, const NSSlots& S, const PrePass& P) {
+  const NSArgs& A = C.A;
+  // norm_flag: the fused kernel reads the rows normalised by the pre-pass; else the tables
+  const float* ent_u = A.norm_flag ? P.ent_n : A.ent;
+  const float* rel_u = A.norm_flag ? P.rel_n : A.rel;
+  return with_bool(A.model == MMRE_TRANSE_L2, [&](auto l2_) {
+    return with_bool(A.regul_rate != 0.0f, [&](auto reg_) {
+      return with_nc<NC_FUSED>(transe_fast_nc(A), [&](auto nc_) {
+        hipLaunchKernelGGL((k_ns_transe_fused<decltype(nc_)::value, decltype(l2_)::value, decltype(reg_)::value>),
+                           dim3((unsigned)A.B), dim3(256), 0, C.st, A, P.nrm_e, P.nrm_r, C.score, C.work + w.part, S,
+                           C.n_ent, ent_u, rel_u);
+      });
+    });
+  });
+}
+
+// k_ns_gen_forward / k_ns_gen_slots: DistMult a workgroup per positive, the two-half models a wave per positive
+static dim3 gen_grid(const NSArgs& A) {
+  return dim3((unsigned)(A.model == MMRE_DISTMULT ? A.B : (A.B + NS_WAVES - 1) / NS_WAVES));
+}
+
+// the other models' forward: scores + loss partials (zeroing the bucket counts)
+static int launch_gen_forward(const NSCall& C, const FusedWs& w, const NSSlots& S) {
+  const NSArgs& A = C.A;
+  return with_gen_model(A.model, [&](auto m_) {
+    return with_nc<NC_FUSED>(gen_nc(A.dim), [&](auto nc_) {
+      hipLaunchKernelGGL((k_ns_gen_forward<decltype(nc_)::value, decltype(m_)::value>), gen_grid(A), dim3(256), 0,
+                         C.st, A, C.score, C.work + w.part, S.counts, C.n_ent + C.n_rel + 1);
+    });
+  });
+}
+
+// The other models' gradient: the slot records, then the row owner. Owner grid: the hub
+// workgroups, then (the one-call step) the loss reduction's workgroup and the next batch's sampler
+// workgroups, then one workgroup per 4 table rows.
+static int launch_gen_grad(const NSCall& C, const FusedWs& w, const NSSlots& S, const NSNext* next) {
+  const NSArgs& A = C.A;
+  const RegScale reg = reg_scale(A);
+  const dim3 ogrid((unsigned)((C.n_ent + C.n_rel + 3) / 4)), blk(256);
+  NSNext nx{};
+  if (next) nx = *next;
+  const int64_t reduce_block = C.loss ? (int64_t)NS_HUB_WG : -1;
+  nx.block0 = (int64_t)NS_HUB_WG + (C.loss ? 1 : 0);
+  const int64_t row0 = nx.block0 + nx.n_blocks;
+  return with_gen_model(A.model, [&](auto m_) {
+    return with_nc<NC_FUSED>(gen_nc(A.dim), [&](auto nc_) {
+      constexpr int NC = decltype(nc_)::value;
+      hipLaunchKernelGGL((k_ns_gen_slots<NC, decltype(m_)::value>), gen_grid(A), blk, 0, C.st, A, C.score, S, C.n_ent,
+                         w.dpad, (int)(A.regul_rate != 0.0f));
+      hipLaunchKernelGGL((k_ns_gen_owner<NC>), dim3(row0 + ogrid.x), blk, 0, C.st, A, C.n_ent, C.n_rel, reg.ent,
+                         reg.rel, S.rec, S.counts, S.bucket, S.ovf, S.ovf_n, w.dpad, C.grad_loss, C.grad.ent,
+                         C.grad.ent_im, C.grad.rel, C.grad.rel_im, C.lr, C.upd.ent, C.upd.ent_im, C.upd.rel,
+                         C.upd.rel_im, row0, NS_HUB_WG, w.slots, C.work + w.part, C.loss, reduce_block, nx, C.opt);
+    });
+  });
+}
+
+// TransE's row owner (gradient, SGD). Its grid: the hub workgroups first (their count scan starts
+// with the kernel), then (the training step) the loss reduction's workgroup, then (the pipelined
+// step, NSNext) the next batch's sampler workgroups, then one workgroup per 4 table rows.
+static int launch_transe_owner(const NSCall& C, const FusedWs& w, const NSSlots& S, const NSNext* next) {
+  const NSArgs& A = C.A;
+  const float reg = reg_scale(A).ent;  // entity and relation rows are both dim wide
+  const dim3 ogrid((unsigned)((C.n_ent + C.n_rel + 3) / 4)), blk(256);
+  NSNext nx{};
+  if (next) nx = *next;
+  constexpr bool kSamplerFirst = true;  // the next batch's workgroups before the row workgroups (dispatched early)
+  const int64_t reduce_block = C.loss ? (int64_t)NS_HUB_WG : -1;
+  const int64_t head = (int64_t)NS_HUB_WG + (C.loss ? 1 : 0);
+  nx.block0 = kSamplerFirst ? head : head + ogrid.x;
+  const int64_t row_block0 = kSamplerFirst ? head + nx.n_blocks : head;
+  const dim3 ogrid2((unsigned)(head + nx.n_blocks + ogrid.x));
+  return with_bool(A.model == MMRE_TRANSE_L2, [&](auto l2_) {
+    return with_nc<NC_FUSED>(transe_fast_nc(A), [&](auto nc_) {
+      hipLaunchKernelGGL((k_ns_row_owner<decltype(nc_)::value, decltype(l2_)::value>), ogrid2, blk, 0, C.st, A.ent,
+                         A.rel, C.n_ent, C.n_rel, A.dim, A.norm_flag, reg, C.work + w.nrm_e, C.work + w.nrm_r, S.shared,
+                         S.rec, S.counts, S.bucket, S.ovf, S.ovf_n, A.K, C.grad_loss, C.grad.ent, C.grad.rel, C.lr,
+                         C.upd.ent, C.upd.rel, A, C.work + w.part, C.loss, reduce_block, row_block0, NS_HUB_WG, w.slots,
+                         nx);
+    });
+  });
 }
 
 extern "C" int mmre_ns_fused_forward_ex(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2574,79 +2732,32 @@ extern "C" int mmre_ns_fused_forward_ex(int model, int norm_flag, float model_ma
                                         int64_t batch, int64_t neg, float loss_margin, float adv_temperature,
                                         float regul_rate, float* d_score, float* d_loss, float* d_work, void* stream,
                                         const mmre_ns_opts_t* opts) {
-  NSArgs A;
-  int rc = ns_opts_check(opts);
+  NSCall C;
+  int rc = ns_call(C, opts,
+                   NSArgs{model, norm_flag, use_model_margin, dim, model_margin, phase_denom, d_ent, d_ent_im, d_rel,
+                          d_rel_im, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate},
+                   stream);
   if (rc) return rc;
-  rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
-               phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
-  if (rc) return rc;
-  if (opts) A.loss_kind = opts->loss_kind;
+  C.n_ent = n_ent; C.n_rel = n_rel; C.score = d_score; C.loss = d_loss; C.work = d_work;
   // TransE under Softplus / Sigmoid is the rows path's (mmre_ns_forward_ex / mmre_ns_backward_ex)
-  if (is_transe(model) && A.loss_kind != MMRE_LOSS_MARGIN) return MMRE_ERR_MODEL;
+  if (is_transe(model) && C.A.loss_kind != MMRE_LOSS_MARGIN) return MMRE_ERR_MODEL;
   if (!d_score || !d_loss || !d_work || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
   // the gradient call has no kernel for any other shape (those are the rows path's): refused here,
   // not after a loss was returned
-  if (!fused_supported(A)) return MMRE_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  FusedWs w;
-  fused_ws(model, norm_flag, batch, neg, n_ent, n_rel, dim, w);
-  float* part = d_work + w.part;
-  NSSlots S = ws_slots(d_work, w, n_ent, n_rel);
-  if (!is_transe(model)) {  // other models: scores + partials (zeroing the bucket counts), then the loss
-    const int gnc = gen_nc(dim);
-    // k_ns_gen_forward: DistMult a workgroup per positive, the two-half models a wave per positive
-    const dim3 fgrid((unsigned)(model == MMRE_DISTMULT ? batch : (batch + NS_WAVES - 1) / NS_WAVES));
-#define MMRE_NS_GF(NC_, M_)                                                                                        \
-  hipLaunchKernelGGL((k_ns_gen_forward<NC_, M_>), fgrid, dim3(256), 0, st, A, d_score, part, S.counts,             \
-                     n_ent + n_rel + 1)
-#define MMRE_NS_GF_M(NC_)                                                                                          \
-  do {                                                                                                             \
-    if (model == MMRE_DISTMULT) MMRE_NS_GF(NC_, MMRE_DISTMULT);                                                    \
-    else if (model == MMRE_COMPLEX) MMRE_NS_GF(NC_, MMRE_COMPLEX);                                                 \
-    else MMRE_NS_GF(NC_, MMRE_ROTATE);                                                                             \
-  } while (0)
-    if (gnc == 1) MMRE_NS_GF_M(1);
-    else if (gnc == 2) MMRE_NS_GF_M(2);
-    else if (gnc == 4) MMRE_NS_GF_M(4);
-    else MMRE_NS_GF_M(8);
-#undef MMRE_NS_GF_M
-#undef MMRE_NS_GF
+  if (!fused_supported(C.A)) return MMRE_ERR_SHAPE;
+  const FusedWs w = fused_ws(C);
+  const NSSlots S = ws_slots(d_work, w, n_ent, n_rel);
+  if (is_transe(model)) {
+    const PrePass P = ws_prepass(C, w);
+    hipLaunchKernelGGL(k_ns_prepass, dim3((unsigned)((n_ent + n_rel + 3) / 4)), dim3(256), 0, C.st, d_ent, n_ent,
+                       d_rel, n_rel, dim, P.nrm_e, P.nrm_r, P.ent_n, P.rel_n, S.counts, S.ovf_n);
     MMRE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ns_reduce, dim3(1), dim3(256), 0, st, A, part, d_loss);
-    MMRE_CHECK_LAUNCH();
-    return MMRE_OK;
+    rc = launch_transe_fused(C, w, S, P);
+  } else {
+    rc = launch_gen_forward(C, w, S);
   }
-  float* nrm_e = d_work + w.nrm_e;
-  float* nrm_r = d_work + w.nrm_r;
-  // norm_flag: the fused kernel reads the rows normalised by the pre-pass; else the tables
-  float* ent_n = norm_flag ? d_work + w.ent_n : nullptr;
-  float* rel_n = norm_flag ? d_work + w.rel_n : nullptr;
-  hipLaunchKernelGGL(k_ns_prepass, dim3((unsigned)((n_ent + n_rel + 3) / 4)), dim3(256), 0, st, d_ent, n_ent, d_rel,
-                     n_rel, dim, nrm_e, nrm_r, ent_n, rel_n, S.counts, S.ovf_n);
-  MMRE_CHECK_LAUNCH();
-  const float* ent_u = norm_flag ? ent_n : d_ent;
-  const float* rel_u = norm_flag ? rel_n : d_rel;
-  const dim3 grid((unsigned)batch), blk(256);
-  const bool l2 = model == MMRE_TRANSE_L2;
-  const int nc = transe_fast_nc(A);
-#define MMRE_NS_FUSED(NC_, L2_)                                                                                    \
-  do {                                                                                                             \
-    if (A.regul_rate != 0.0f)                                                                                      \
-      hipLaunchKernelGGL((k_ns_transe_fused<NC_, L2_, true>), grid, blk, 0, st, A, nrm_e, nrm_r, d_score, part, S, \
-                         n_ent, ent_u, rel_u);                                                                     \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_ns_transe_fused<NC_, L2_, false>), grid, blk, 0, st, A, nrm_e, nrm_r, d_score, part,  \
-                         S, n_ent, ent_u, rel_u);                                                                  \
-  } while (0)
-  if (nc == 1) { if (l2) MMRE_NS_FUSED(1, true); else MMRE_NS_FUSED(1, false); }
-  else if (nc == 2) { if (l2) MMRE_NS_FUSED(2, true); else MMRE_NS_FUSED(2, false); }
-  else if (nc == 4) { if (l2) MMRE_NS_FUSED(4, true); else MMRE_NS_FUSED(4, false); }
-  else { if (l2) MMRE_NS_FUSED(8, true); else MMRE_NS_FUSED(8, false); }
-#undef MMRE_NS_FUSED
-  MMRE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_ns_reduce, dim3(1), dim3(256), 0, st, A, part, d_loss);  // the loss, fixed order
-  MMRE_CHECK_LAUNCH();
-  return MMRE_OK;
+  if (rc) return rc;
+  return launch_reduce(C.A, d_work + w.part, d_loss, C.st);
 }
 
 extern "C" int mmre_ns_fused_forward(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2660,107 +2771,29 @@ extern "C" int mmre_ns_fused_forward(int model, int norm_flag, float model_margi
                                   adv_temperature, regul_rate, d_score, d_loss, d_work, stream, nullptr);
 }
 
-static int fused_grad_impl(int model, int norm_flag, float model_margin, int use_model_margin, const float* d_ent,
-                           const float* d_ent_im, const float* d_rel, const float* d_rel_im, int64_t n_ent,
-                           int64_t n_rel, int dim, float phase_denom, const int64_t* d_h, const int64_t* d_t,
-                           const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin, float adv_temperature,
-                           float regul_rate, const float* d_score, const float* d_grad_loss, float* d_grad_ent,
-                           float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work, float lr,
-                           float* pe, float* pei, float* pr, float* pri, void* stream, float* d_loss_out = nullptr,
-                           int parity = 0, const NSNext* nxp = nullptr, const mmre_ns_opts_t* opts = nullptr) {
-  NSArgs A;
-  int rc = ns_opts_check(opts);
+// the gradient of a validated call (and its step, its loss reduction, the next batch: C.lr, C.loss, next)
+static int fused_grad_impl(const NSCall& C, const NSNext* next = nullptr) {
+  const FusedWs w = fused_ws(C);
+  const NSSlots S = ws_slots(C.work, w, C.n_ent, C.n_rel, C.parity);
+  return is_transe(C.A.model) ? launch_transe_owner(C, w, S, next) : launch_gen_grad(C, w, S, next);
+}
+
+// The fused gradient entry points behind their filled C: ns_call, then in the ABI's order TransE's
+// loss, Adagrad's state, the pointers, the shape; then the launches.
+static int fused_grad_entry(NSCall& C, const mmre_ns_opts_t* opts, const NSArgs& args, void* stream) {
+  int rc = ns_call(C, opts, args, stream);
   if (rc) return rc;
-  rc = ns_args(A, model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim,
-               phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate);
+  const NSArgs& A = C.A;
+  // TransE under Softplus / Sigmoid is the rows path's (mmre_ns_forward_ex / mmre_ns_backward_ex)
+  if (is_transe(A.model) && A.loss_kind != MMRE_LOSS_MARGIN) return MMRE_ERR_MODEL;
+  rc = ns_adagrad(C, opts);
   if (rc) return rc;
-  NSOpt gopt{};
-  if (opts) {
-    A.loss_kind = opts->loss_kind;
-    // TransE under Softplus / Sigmoid is the rows path's (mmre_ns_forward_ex / mmre_ns_backward_ex)
-    if (is_transe(model) && A.loss_kind != MMRE_LOSS_MARGIN) return MMRE_ERR_MODEL;
-    if (opts->optimizer == MMRE_OPT_ADAGRAD && lr != 0.0f) {  // the generic row owner's Adagrad branch
-      if (is_transe(model) || !opts->d_sum_ent || !opts->d_sum_rel) return MMRE_ERR_ARG;
-      if (model == MMRE_COMPLEX && (!opts->d_sum_ent_im || !opts->d_sum_rel_im)) return MMRE_ERR_ARG;
-      gopt = NSOpt{1, opts->eps, opts->d_sum_ent, opts->d_sum_ent_im, opts->d_sum_rel, opts->d_sum_rel_im};
-    }
-  }
-  if (!d_score || !d_work || !d_grad_ent || !d_grad_rel || n_ent <= 0 || n_rel <= 0) return MMRE_ERR_ARG;
-  if (model == MMRE_COMPLEX && (!d_grad_ent_im || !d_grad_rel_im)) return MMRE_ERR_ARG;
-  if (lr != 0.0f && (!pe || !pr || (model == MMRE_COMPLEX && (!pei || !pri)))) return MMRE_ERR_ARG;
-  if (!fused_supported(A)) return MMRE_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  FusedWs w;
-  fused_ws(model, norm_flag, batch, neg, n_ent, n_rel, dim, w);
-  NSSlots S = ws_slots(d_work, w, n_ent, n_rel, parity);
-  const double N = (double)batch * (1.0 + (double)neg);
-  const dim3 ogrid((unsigned)((n_ent + n_rel + 3) / 4)), blk(256);
-  if (!is_transe(model)) {
-    const int nc = gen_nc(dim);
-    const double nterms = model == MMRE_COMPLEX ? 6.0 : 3.0;
-    const double ew = model == MMRE_ROTATE ? 2.0 * dim : (double)dim;
-    const float reg_ent = regul_rate != 0.0f ? (float)(regul_rate * 2.0 / (nterms * N * ew)) : 0.0f;
-    const float reg_rel = regul_rate != 0.0f ? (float)(regul_rate * 2.0 / (nterms * N * dim)) : 0.0f;
-    // DistMult: a workgroup per positive; the two-half models: a wave per positive
-    const dim3 sgrid((unsigned)(model == MMRE_DISTMULT ? batch : (batch + NS_WAVES - 1) / NS_WAVES));
-    // owner grid: the hub workgroups, then (the one-call step) the loss reduction's workgroup and
-    // the next batch's sampler workgroups, then one workgroup per 4 table rows
-    NSNext gnx{};
-    if (nxp) gnx = *nxp;
-    const int64_t gen_reduce = d_loss_out ? (int64_t)NS_HUB_WG : -1;
-    gnx.block0 = (int64_t)NS_HUB_WG + (d_loss_out ? 1 : 0);
-    const int64_t gen_row0 = gnx.block0 + gnx.n_blocks;
-#define MMRE_NS_GEN(NC_)                                                                                            \
-  do {                                                                                                              \
-    if (model == MMRE_DISTMULT)                                                                                     \
-      hipLaunchKernelGGL((k_ns_gen_slots<NC_, MMRE_DISTMULT>), sgrid, blk, 0, st, A, d_score, S, n_ent, w.dpad,     \
-                         (int)(regul_rate != 0.0f));                                                                \
-    else if (model == MMRE_COMPLEX)                                                                                 \
-      hipLaunchKernelGGL((k_ns_gen_slots<NC_, MMRE_COMPLEX>), sgrid, blk, 0, st, A, d_score, S, n_ent, w.dpad,      \
-                         (int)(regul_rate != 0.0f));                                                                \
-    else                                                                                                            \
-      hipLaunchKernelGGL((k_ns_gen_slots<NC_, MMRE_ROTATE>), sgrid, blk, 0, st, A, d_score, S, n_ent, w.dpad,       \
-                         (int)(regul_rate != 0.0f));                                                                \
-    hipLaunchKernelGGL((k_ns_gen_owner<NC_>), dim3(gen_row0 + ogrid.x), blk, 0, st, A, n_ent, n_rel, reg_ent,        \
-                       reg_rel, S.rec, S.counts, S.bucket, S.ovf, S.ovf_n, w.dpad, d_grad_loss, d_grad_ent,          \
-                       d_grad_ent_im, d_grad_rel, d_grad_rel_im, lr, pe, pei, pr, pri, gen_row0, NS_HUB_WG, w.slots,  \
-                       d_work + w.part, d_loss_out, gen_reduce, gnx, gopt);                                         \
-  } while (0)
-    if (nc == 1) MMRE_NS_GEN(1);
-    else if (nc == 2) MMRE_NS_GEN(2);
-    else if (nc == 4) MMRE_NS_GEN(4);
-    else MMRE_NS_GEN(8);
-#undef MMRE_NS_GEN
-    MMRE_CHECK_LAUNCH();
-    return MMRE_OK;
-  }
-  const float reg = regul_rate != 0.0f ? (float)(regul_rate * 2.0 / (3.0 * N * dim)) : 0.0f;
-  // the training step (d_loss_out): one more workgroup reduces the forward's loss partials
-  // the hub workgroups first (their count scan starts with the kernel), then (the training
-  // step) the loss reduction's workgroup, then one workgroup per 4 table rows
-  // (the pipelined step: then the next batch's sampler workgroups, NSNext)
-  NSNext nx{};
-  if (nxp) nx = *nxp;
-  constexpr bool kSamplerFirst = true;  // the next batch's workgroups before the row workgroups (dispatched early)
-  const int64_t reduce_block = d_loss_out ? (int64_t)NS_HUB_WG : -1;
-  const int64_t head = (int64_t)NS_HUB_WG + (d_loss_out ? 1 : 0);
-  nx.block0 = kSamplerFirst ? head : head + ogrid.x;
-  const int64_t row_block0 = kSamplerFirst ? head + nx.n_blocks : head;
-  const dim3 ogrid2((unsigned)(head + nx.n_blocks + ogrid.x));
-#define MMRE_NS_OWNER(NC_, L2_)                                                                                     \
-  hipLaunchKernelGGL((k_ns_row_owner<NC_, L2_>), ogrid2, blk, 0, st, d_ent, d_rel, n_ent, n_rel, dim, norm_flag, reg, \
-                     d_work + w.nrm_e, d_work + w.nrm_r, S.shared, S.rec, S.counts, S.bucket, S.ovf, S.ovf_n,         \
-                     neg, d_grad_loss, d_grad_ent, d_grad_rel, lr, pe, pr, A, d_work + w.part, d_loss_out,           \
-                     reduce_block, row_block0, NS_HUB_WG, w.slots, nx)
-  const int nc = transe_fast_nc(A);
-  const bool l2 = model == MMRE_TRANSE_L2;
-  if (nc == 1) { if (l2) MMRE_NS_OWNER(1, true); else MMRE_NS_OWNER(1, false); }
-  else if (nc == 2) { if (l2) MMRE_NS_OWNER(2, true); else MMRE_NS_OWNER(2, false); }
-  else if (nc == 4) { if (l2) MMRE_NS_OWNER(4, true); else MMRE_NS_OWNER(4, false); }
-  else { if (l2) MMRE_NS_OWNER(8, true); else MMRE_NS_OWNER(8, false); }
-#undef MMRE_NS_OWNER
-  MMRE_CHECK_LAUNCH();
-  return MMRE_OK;
+  if (C.opt.adagrad && is_transe(A.model)) return MMRE_ERR_ARG;  // the generic row owner's branch only
+  rc = grad_tables_check(C, C.score);
+  if (rc) return rc;
+  if (C.lr != 0.0f && (!C.upd.ent || !C.upd.rel || (A.model == MMRE_COMPLEX && (!C.upd.ent_im || !C.upd.rel_im))))
+    return MMRE_ERR_ARG;
+  return fused_supported(A) ? fused_grad_impl(C) : MMRE_ERR_SHAPE;
 }
 
 extern "C" int mmre_ns_fused_grad_ex(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2771,10 +2804,14 @@ extern "C" int mmre_ns_fused_grad_ex(int model, int norm_flag, float model_margi
                                      const float* d_score, const float* d_grad_loss, float* d_grad_ent,
                                      float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work,
                                      void* stream, const mmre_ns_opts_t* opts) {
-  return fused_grad_impl(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, n_ent,
-                         n_rel, dim, phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate,
-                         d_score, d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, 0.0f,
-                         nullptr, nullptr, nullptr, nullptr, stream, nullptr, 0, nullptr, opts);
+  NSCall C;
+  C.n_ent = n_ent; C.n_rel = n_rel; C.score = const_cast<float*>(d_score); C.work = d_work;
+  C.grad_loss = d_grad_loss;
+  C.grad = {d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im};
+  return fused_grad_entry(C, opts,
+                          NSArgs{model, norm_flag, use_model_margin, dim, model_margin, phase_denom, d_ent, d_ent_im,
+                                 d_rel, d_rel_im, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate},
+                          stream);
 }
 
 extern "C" int mmre_ns_fused_grad(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2799,10 +2836,16 @@ extern "C" int mmre_ns_fused_grad_sgd_ex(int model, int norm_flag, float model_m
                                          float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work,
                                          float lr, void* stream, const mmre_ns_opts_t* opts) {
   if (!(lr != 0.0f)) return MMRE_ERR_ARG;
-  return fused_grad_impl(model, norm_flag, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, n_ent,
-                         n_rel, dim, phase_denom, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate,
-                         d_score, d_grad_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, lr, d_ent,
-                         d_ent_im, d_rel, d_rel_im, stream, nullptr, 0, nullptr, opts);
+  NSCall C;
+  C.n_ent = n_ent; C.n_rel = n_rel; C.score = const_cast<float*>(d_score); C.work = d_work;
+  C.grad_loss = d_grad_loss;
+  C.grad = {d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im};
+  C.lr = lr;
+  C.upd = {d_ent, d_ent_im, d_rel, d_rel_im};
+  return fused_grad_entry(C, opts,
+                          NSArgs{model, norm_flag, use_model_margin, dim, model_margin, phase_denom, d_ent, d_ent_im,
+                                 d_rel, d_rel_im, d_h, d_t, d_r, batch, neg, loss_margin, adv_temperature, regul_rate},
+                          stream);
 }
 
 extern "C" int mmre_ns_fused_grad_sgd(int model, int norm_flag, float model_margin, int use_model_margin,
@@ -2837,6 +2880,65 @@ extern "C" int mmre_ns_forward_backward(int model, int norm_flag, float model_ma
                             stream);
 }
 
+// The sampler's arguments as every one-call step takes them (include/mmre.h), spelled once.
+#define MMRE_SAMPLER_PARAMS                                                                                          \
+  const int64_t *d_train_list, int64_t train_total, const int64_t *d_head_hrt, const int64_t *d_tail_hrt,             \
+      const int64_t *d_rel_hrt, const int64_t *d_lef_head, const int64_t *d_rig_head, const int64_t *d_lef_tail,      \
+      const int64_t *d_rig_tail, const int64_t *d_lef_rel, const int64_t *d_rig_rel, const float *d_left_mean,       \
+      const float *d_right_mean, uint64_t *d_seeds, int64_t work_threads, int64_t mode, const int32_t *d_blocks,     \
+      int64_t n_blocks, int64_t *d_batch_h, int64_t *d_batch_t, int64_t *d_batch_r, float *d_batch_y,               \
+      int32_t *d_ticket
+#define MMRE_SAMPLER_ARGS                                                                                            \
+  d_train_list, train_total, d_head_hrt, d_tail_hrt, d_rel_hrt, d_lef_head, d_rig_head, d_lef_tail, d_rig_tail,     \
+      d_lef_rel, d_rig_rel, d_left_mean, d_right_mean, d_seeds, work_threads, mode, d_blocks, n_blocks, d_batch_h,  \
+      d_batch_t, d_batch_r, d_batch_y, d_ticket
+
+// What a one-call step has beside its NSCall: the sampler's arguments for the current batch, which
+// of its launches the previous call made already, the next batch's buffers.
+struct NSStep {
+  OpenKESamplerArgs sa;
+  int64_t n_sampler;  // sampler workgroups of one batch
+  int64_t prepared;   // bit 0: the batch is drawn, bit 1 (TransE): the pre-pass is current
+  int64_t *next_h, *next_t, *next_r;  // pipelined: where the row owner draws the next batch (next_h null: nowhere)
+  float* next_y;
+};
+
+// the sampler's part of a step: checked, then T.sa and T.n_sampler (the only function here that
+// takes the ABI's list as it is)
+static int step_sampler(NSStep& T, MMRE_SAMPLER_PARAMS, int64_t n_ent, int64_t n_rel, int64_t batch, int64_t neg) {
+  if (!d_train_list || !d_head_hrt || !d_tail_hrt || !d_lef_head || !d_rig_head || !d_lef_tail || !d_rig_tail ||
+      !d_seeds || !d_batch_h || !d_batch_t || !d_batch_r || !d_batch_y || !d_ticket)
+    return MMRE_ERR_ARG;
+  if ((d_left_mean == nullptr) != (d_right_mean == nullptr)) return MMRE_ERR_ARG;
+  if (train_total <= 0 || n_ent <= 1 || work_threads <= 0 || batch <= 0 || neg <= 0 || mode < -1 || mode > 1)
+    return MMRE_ERR_ARG;
+  if (n_blocks < 0 || (n_blocks > 0 && !d_blocks)) return MMRE_ERR_ARG;
+  T.sa = OpenKESamplerArgs{d_train_list, d_head_hrt, d_tail_hrt, d_rel_hrt, d_lef_head, d_rig_head, d_lef_tail,
+                           d_rig_tail, d_lef_rel, d_rig_rel, d_left_mean, d_right_mean, train_total, n_ent, n_rel,
+                           d_seeds, work_threads, batch, neg, 0, mode, d_blocks, n_blocks, d_batch_h, d_batch_t,
+                           d_batch_r, d_batch_y, d_ticket, mmre_sampler_draws_per_positive(neg, 0, mode), nullptr};
+  T.n_sampler = (batch * (1 + neg) + 255) / 256;
+  return MMRE_OK;
+}
+
+// the rest of a step's arguments that are refused as such (before the model is looked at)
+static int step_check(const NSCall& C, const NSStep& T) {
+  if (!C.score || !C.loss || !C.grad.ent || !C.grad.rel || !C.work || C.n_rel <= 0 || !(C.lr != 0.0f))
+    return MMRE_ERR_ARG;
+  if (T.prepared < 0 || T.prepared > 3) return MMRE_ERR_ARG;
+  if (T.next_h && (!T.next_t || !T.next_r || !T.next_y || T.next_h == T.sa.bh)) return MMRE_ERR_ARG;
+  return MMRE_OK;
+}
+
+// what the row owner does for the next step: the sampler's workgroups, drawing into the next batch's buffers
+static NSNext step_next(const NSStep& T) {
+  NSNext nx{};
+  nx.sa = T.sa;
+  nx.sa.bh = T.next_h; nx.sa.bt = T.next_t; nx.sa.br = T.next_r; nx.sa.by = T.next_y;
+  nx.n_blocks = T.n_sampler;
+  return nx;
+}
+
 // One OpenKE training step (Trainer.train_one_step, Trainer.py:43-54, over Base.cpp's sampling)
 // for TransE with the fused path's shapes: sample the batch, margin loss + gradients, plain SGD.
 // Three launches: the sampler's workgroups beside the pre-pass (k_ns_step_prep), the fused loss
@@ -2848,96 +2950,29 @@ extern "C" int mmre_ns_forward_backward(int model, int norm_flag, float model_ma
 // launch 1 unless `prepared` is 3 (bit 0: the batch is drawn, bit 1: the pre-pass is current);
 // the row owner also samples the next batch into the d_next_* buffers and does its pre-pass
 // (NSNext), so the next call with prepared = 3 and the other parity is two launches.
-static int step_openke_impl(const int64_t* d_train_list, int64_t train_total, const int64_t* d_head_hrt,
-                            const int64_t* d_tail_hrt, const int64_t* d_rel_hrt, const int64_t* d_lef_head,
-                            const int64_t* d_rig_head, const int64_t* d_lef_tail, const int64_t* d_rig_tail,
-                            const int64_t* d_lef_rel, const int64_t* d_rig_rel, const float* d_left_mean,
-                            const float* d_right_mean, uint64_t* d_seeds, int64_t work_threads, int64_t mode,
-                            const int32_t* d_blocks, int64_t n_blocks, int64_t* d_batch_h, int64_t* d_batch_t,
-                            int64_t* d_batch_r, float* d_batch_y, int32_t* d_ticket, int model, int norm_flag,
-                            float* d_ent, float* d_rel, int64_t n_ent, int64_t n_rel, int dim, int64_t batch,
-                            int64_t neg, float loss_margin, float adv_temperature, float regul_rate, float* d_score,
-                            float* d_loss, float* d_grad_ent, float* d_grad_rel, float* d_work, float lr,
-                            void* stream, int64_t prepared, int64_t parity, int64_t* d_next_h, int64_t* d_next_t,
-                            int64_t* d_next_r, float* d_next_y) {
-  if (!d_train_list || !d_head_hrt || !d_tail_hrt || !d_lef_head || !d_rig_head || !d_lef_tail || !d_rig_tail ||
-      !d_seeds || !d_batch_h || !d_batch_t || !d_batch_r || !d_batch_y || !d_ticket)
-    return MMRE_ERR_ARG;
-  if ((d_left_mean == nullptr) != (d_right_mean == nullptr)) return MMRE_ERR_ARG;
-  if (train_total <= 0 || n_ent <= 1 || work_threads <= 0 || batch <= 0 || neg <= 0 || mode < -1 || mode > 1)
-    return MMRE_ERR_ARG;
-  if (n_blocks < 0 || (n_blocks > 0 && !d_blocks)) return MMRE_ERR_ARG;
-  if (!d_score || !d_loss || !d_grad_ent || !d_grad_rel || !d_work || n_rel <= 0 || !(lr != 0.0f))
-    return MMRE_ERR_ARG;
-  const bool pipe = d_next_h != nullptr;
-  if (pipe && (!d_next_t || !d_next_r || !d_next_y || d_next_h == d_batch_h)) return MMRE_ERR_ARG;
-  if (parity < 0 || parity > 1 || prepared < 0 || prepared > 3) return MMRE_ERR_ARG;
-  NSArgs A;
-  int rc = ns_args(A, model, norm_flag, 0.0f, 0, d_ent, nullptr, d_rel, nullptr, dim, 0.0f, d_batch_h, d_batch_t,
-                   d_batch_r, batch, neg, loss_margin, adv_temperature, regul_rate);
-  if (rc) return rc;
-  if (!is_transe(model) || !fused_supported(A)) return MMRE_ERR_SHAPE;  // the fused TransE path's shapes only
-  hipStream_t st = (hipStream_t)stream;
-  FusedWs w;
-  fused_ws(model, norm_flag, batch, neg, n_ent, n_rel, dim, w);
-  NSSlots S = ws_slots(d_work, w, n_ent, n_rel, (int)parity);
-  float* nrm_e = d_work + w.nrm_e;
-  float* nrm_r = d_work + w.nrm_r;
-  float* ent_n = norm_flag ? d_work + w.ent_n : nullptr;
-  float* rel_n = norm_flag ? d_work + w.rel_n : nullptr;
-  const int64_t rows = batch * (1 + neg);
-  const int64_t n_sampler = (rows + 255) / 256;
-  const OpenKESamplerArgs sa{d_train_list, d_head_hrt, d_tail_hrt, d_rel_hrt, d_lef_head, d_rig_head, d_lef_tail,
-                             d_rig_tail, d_lef_rel, d_rig_rel, d_left_mean, d_right_mean, train_total, n_ent, n_rel,
-                             d_seeds, work_threads, batch, neg, 0, mode, d_blocks, n_blocks, d_batch_h, d_batch_t,
-                             d_batch_r, d_batch_y, d_ticket, mmre_sampler_draws_per_positive(neg, 0, mode), nullptr};
-  if (prepared != 3) {  // 1. sampler workgroups (unless the batch is drawn) + pre-pass workgroups
-    const int64_t ns1 = (prepared & 1) ? 0 : n_sampler;
-    hipLaunchKernelGGL(k_ns_step_prep, dim3((unsigned)(ns1 + (n_ent + n_rel + 3) / 4)), dim3(256), 0, st, sa, ns1,
-                       d_ent, n_ent, d_rel, n_rel, dim, nrm_e, nrm_r, ent_n, rel_n, S.counts, S.ovf_n);
+static int step_openke_impl(const NSCall& C, const NSStep& T) {
+  const NSArgs& A = C.A;
+  const FusedWs w = fused_ws(C);
+  const NSSlots S = ws_slots(C.work, w, C.n_ent, C.n_rel, C.parity);
+  const PrePass P = ws_prepass(C, w);
+  if (T.prepared != 3) {  // 1. sampler workgroups (unless the batch is drawn) + pre-pass workgroups
+    const int64_t ns1 = (T.prepared & 1) ? 0 : T.n_sampler;
+    hipLaunchKernelGGL(k_ns_step_prep, dim3((unsigned)(ns1 + (C.n_ent + C.n_rel + 3) / 4)), dim3(256), 0, C.st, T.sa,
+                       ns1, A.ent, C.n_ent, A.rel, C.n_rel, A.dim, P.nrm_e, P.nrm_r, P.ent_n, P.rel_n, S.counts,
+                       S.ovf_n);
     MMRE_CHECK_LAUNCH();
   }
   // 2. the fused loss kernel (scores, loss partials, slots)
-  const float* ent_u = norm_flag ? ent_n : d_ent;
-  const float* rel_u = norm_flag ? rel_n : d_rel;
-  const bool l2 = model == MMRE_TRANSE_L2;
-  const int nc = transe_fast_nc(A);
-  float* part = d_work + w.part;
-  const dim3 grid((unsigned)batch), blk(256);
-#define MMRE_NS_FUSED(NC_, L2_)                                                                                    \
-  do {                                                                                                             \
-    if (A.regul_rate != 0.0f)                                                                                      \
-      hipLaunchKernelGGL((k_ns_transe_fused<NC_, L2_, true>), grid, blk, 0, st, A, nrm_e, nrm_r, d_score, part, S, \
-                         n_ent, ent_u, rel_u);                                                                     \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_ns_transe_fused<NC_, L2_, false>), grid, blk, 0, st, A, nrm_e, nrm_r, d_score, part,  \
-                         S, n_ent, ent_u, rel_u);                                                                  \
-  } while (0)
-  if (nc == 1) { if (l2) MMRE_NS_FUSED(1, true); else MMRE_NS_FUSED(1, false); }
-  else if (nc == 2) { if (l2) MMRE_NS_FUSED(2, true); else MMRE_NS_FUSED(2, false); }
-  else if (nc == 4) { if (l2) MMRE_NS_FUSED(4, true); else MMRE_NS_FUSED(4, false); }
-  else { if (l2) MMRE_NS_FUSED(8, true); else MMRE_NS_FUSED(8, false); }
-#undef MMRE_NS_FUSED
-  MMRE_CHECK_LAUNCH();
-  // 3. gradient + SGD, and the loss (+ the pipelined step's next batch and pre-pass)
+  const int rc = launch_transe_fused(C, w, S, P);
+  if (rc) return rc;
+  // 3. gradient + SGD, and the loss (+ the pipelined step's next batch, its pre-pass and the other parity's counts)
   NSNext nx{};
-  if (pipe) {
-    nx.sa = sa;
-    nx.sa.bh = d_next_h;
-    nx.sa.bt = d_next_t;
-    nx.sa.br = d_next_r;
-    nx.sa.by = d_next_y;
-    nx.n_blocks = n_sampler;
-    nx.counts = ws_slots(d_work, w, n_ent, n_rel, (int)(1 - parity)).counts;
-    nx.nrm_e = nrm_e;
-    nx.nrm_r = nrm_r;
-    nx.ent_n = ent_n;
-    nx.rel_n = rel_n;
+  if (T.next_h) {
+    nx = step_next(T);
+    nx.counts = ws_slots(C.work, w, C.n_ent, C.n_rel, 1 - C.parity).counts;
+    nx.nrm_e = P.nrm_e; nx.nrm_r = P.nrm_r; nx.ent_n = P.ent_n; nx.rel_n = P.rel_n;
   }
-  return fused_grad_impl(model, norm_flag, 0.0f, 0, d_ent, nullptr, d_rel, nullptr, n_ent, n_rel, dim, 0.0f,
-                         d_batch_h, d_batch_t, d_batch_r, batch, neg, loss_margin, adv_temperature, regul_rate, d_score,
-                         nullptr, d_grad_ent, nullptr, d_grad_rel, nullptr, d_work, lr, d_ent, nullptr, d_rel, nullptr,
-                         stream, d_loss, (int)parity, pipe ? &nx : nullptr);
+  return fused_grad_impl(C, T.next_h ? &nx : nullptr);
 }
 
 // The one-call training step for DistMult / ComplEx / RotatE (the generic fused path), pipelined
@@ -2946,147 +2981,104 @@ static int step_openke_impl(const int64_t* d_train_list, int64_t train_total, co
 // (gradient + SGD, with the loss reduction and the NEXT batch's sampler workgroups in its grid).
 // Same kernels and values as OpenKESampler.sample + fused_ns_loss(...).backward() with the SGD
 // fused (mmre.optim.SGD), bit for bit; three launches a step instead of five.
-static int step_openke_gen_impl(const OpenKESamplerArgs& sa, int64_t n_sampler, int model, float model_margin,
-                                int use_model_margin, float* d_ent, float* d_ent_im, float* d_rel, float* d_rel_im,
-                                int64_t n_ent, int64_t n_rel, int dim, float phase_denom, int64_t batch, int64_t neg,
-                                float loss_margin, float adv_temperature, float regul_rate, float* d_score,
-                                float* d_loss, float* d_grad_ent, float* d_grad_ent_im, float* d_grad_rel,
-                                float* d_grad_rel_im, float* d_work, float lr, hipStream_t st, int64_t prepared,
-                                int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y,
-                                const mmre_ns_opts_t* opts) {
-  NSArgs A;
-  int rc = ns_args(A, model, 0, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, dim, phase_denom,
-                   sa.bh, sa.bt, sa.br, batch, neg, loss_margin, adv_temperature, regul_rate);
-  if (rc) return rc;
-  if (opts) {  // checked by the entry point; the sum tables before the forward is launched
-    A.loss_kind = opts->loss_kind;
-    if (opts->optimizer == MMRE_OPT_ADAGRAD &&
-        (!opts->d_sum_ent || !opts->d_sum_rel || (model == MMRE_COMPLEX && (!opts->d_sum_ent_im || !opts->d_sum_rel_im))))
-      return MMRE_ERR_ARG;
-  }
-  const int gnc = gen_nc(dim);
-  if (is_transe(model) || !fused_supported(A)) return MMRE_ERR_SHAPE;
-  FusedWs w;
-  fused_ws(model, 0, batch, neg, n_ent, n_rel, dim, w);
-  NSSlots S = ws_slots(d_work, w, n_ent, n_rel);
-  float* part = d_work + w.part;
-  if (!(prepared & 1)) {  // 1. the batch (the sampler's workgroups alone: no pre-pass for these models)
-    hipLaunchKernelGGL(k_ns_step_prep, dim3((unsigned)n_sampler), dim3(256), 0, st, sa, n_sampler, nullptr, n_ent,
-                       nullptr, n_rel, dim, nullptr, nullptr, nullptr, nullptr, S.counts, S.ovf_n);
+static int step_openke_gen_impl(const NSCall& C, const NSStep& T) {
+  const FusedWs w = fused_ws(C);
+  const NSSlots S = ws_slots(C.work, w, C.n_ent, C.n_rel);
+  if (!(T.prepared & 1)) {  // 1. the batch (the sampler's workgroups alone: no pre-pass for these models)
+    hipLaunchKernelGGL(k_ns_step_prep, dim3((unsigned)T.n_sampler), dim3(256), 0, C.st, T.sa, T.n_sampler, nullptr,
+                       C.n_ent, nullptr, C.n_rel, C.A.dim, nullptr, nullptr, nullptr, nullptr, S.counts, S.ovf_n);
     MMRE_CHECK_LAUNCH();
   }
   // 2. the forward: scores + loss partials (zeroes the slot counts)
-  const dim3 fgrid((unsigned)(model == MMRE_DISTMULT ? batch : (batch + NS_WAVES - 1) / NS_WAVES));
-#define MMRE_NS_GF(NC_, M_)                                                                                        \
-  hipLaunchKernelGGL((k_ns_gen_forward<NC_, M_>), fgrid, dim3(256), 0, st, A, d_score, part, S.counts,             \
-                     n_ent + n_rel + 1)
-#define MMRE_NS_GF_M(NC_)                                                                                          \
-  do {                                                                                                             \
-    if (model == MMRE_DISTMULT) MMRE_NS_GF(NC_, MMRE_DISTMULT);                                                    \
-    else if (model == MMRE_COMPLEX) MMRE_NS_GF(NC_, MMRE_COMPLEX);                                                 \
-    else MMRE_NS_GF(NC_, MMRE_ROTATE);                                                                             \
-  } while (0)
-  if (gnc == 1) MMRE_NS_GF_M(1);
-  else if (gnc == 2) MMRE_NS_GF_M(2);
-  else if (gnc == 4) MMRE_NS_GF_M(4);
-  else MMRE_NS_GF_M(8);
-#undef MMRE_NS_GF_M
-#undef MMRE_NS_GF
-  MMRE_CHECK_LAUNCH();
-  // 3.-4. slots, then the row owner with SGD, the loss reduction and the next batch
-  NSNext nx{};
-  if (d_next_h) {
-    nx.sa = sa;
-    nx.sa.bh = d_next_h;
-    nx.sa.bt = d_next_t;
-    nx.sa.br = d_next_r;
-    nx.sa.by = d_next_y;
-    nx.n_blocks = n_sampler;
-  }
-  return fused_grad_impl(model, 0, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im, n_ent, n_rel, dim,
-                         phase_denom, sa.bh, sa.bt, sa.br, batch, neg, loss_margin, adv_temperature, regul_rate,
-                         d_score, nullptr, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, lr, d_ent,
-                         d_ent_im, d_rel, d_rel_im, st, d_loss, 0, d_next_h ? &nx : nullptr, opts);
+  const int rc = launch_gen_forward(C, w, S);
+  if (rc) return rc;
+  // 3.-4. slots, then the row owner with its step, the loss reduction and the next batch
+  const NSNext nx = T.next_h ? step_next(T) : NSNext{};
+  return fused_grad_impl(C, T.next_h ? &nx : nullptr);
 }
 
 #define MMRE_STEP_OPENKE_PARAMS                                                                                      \
-  const int64_t *d_train_list, int64_t train_total, const int64_t *d_head_hrt, const int64_t *d_tail_hrt,             \
-      const int64_t *d_rel_hrt, const int64_t *d_lef_head, const int64_t *d_rig_head, const int64_t *d_lef_tail,      \
-      const int64_t *d_rig_tail, const int64_t *d_lef_rel, const int64_t *d_rig_rel, const float *d_left_mean,       \
-      const float *d_right_mean, uint64_t *d_seeds, int64_t work_threads, int64_t mode, const int32_t *d_blocks,     \
-      int64_t n_blocks, int64_t *d_batch_h, int64_t *d_batch_t, int64_t *d_batch_r, float *d_batch_y,               \
-      int32_t *d_ticket, int model, int norm_flag, float *d_ent, float *d_rel, int64_t n_ent, int64_t n_rel, int dim, \
+  MMRE_SAMPLER_PARAMS, int model, int norm_flag, float *d_ent, float *d_rel, int64_t n_ent, int64_t n_rel, int dim,  \
       int64_t batch, int64_t neg, float loss_margin, float adv_temperature, float regul_rate, float *d_score,         \
       float *d_loss, float *d_grad_ent, float *d_grad_rel, float *d_work, float lr, void *stream
 #define MMRE_STEP_OPENKE_ARGS                                                                                        \
-  d_train_list, train_total, d_head_hrt, d_tail_hrt, d_rel_hrt, d_lef_head, d_rig_head, d_lef_tail, d_rig_tail,     \
-      d_lef_rel, d_rig_rel, d_left_mean, d_right_mean, d_seeds, work_threads, mode, d_blocks, n_blocks, d_batch_h,  \
-      d_batch_t, d_batch_r, d_batch_y, d_ticket, model, norm_flag, d_ent, d_rel, n_ent, n_rel, dim, batch, neg,      \
-      loss_margin, adv_temperature, regul_rate, d_score, d_loss, d_grad_ent, d_grad_rel, d_work, lr, stream
-
-extern "C" int mmre_ns_step_openke(MMRE_STEP_OPENKE_PARAMS) {
-  return step_openke_impl(MMRE_STEP_OPENKE_ARGS, 0, 0, nullptr, nullptr, nullptr, nullptr);
-}
+  MMRE_SAMPLER_ARGS, model, norm_flag, d_ent, d_rel, n_ent, n_rel, dim, batch, neg, loss_margin, adv_temperature,   \
+      regul_rate, d_score, d_loss, d_grad_ent, d_grad_rel, d_work, lr, stream
 
 extern "C" int mmre_ns_step_openke_pipe(MMRE_STEP_OPENKE_PARAMS, int64_t prepared, int64_t parity, int64_t* d_next_h,
                                         int64_t* d_next_t, int64_t* d_next_r, float* d_next_y) {
-  return step_openke_impl(MMRE_STEP_OPENKE_ARGS, prepared, parity, d_next_h, d_next_t, d_next_r, d_next_y);
+  NSStep T;
+  int rc = step_sampler(T, MMRE_SAMPLER_ARGS, n_ent, n_rel, batch, neg);
+  if (rc) return rc;
+  T.prepared = prepared;
+  T.next_h = d_next_h; T.next_t = d_next_t; T.next_r = d_next_r; T.next_y = d_next_y;
+  NSCall C;
+  C.n_ent = n_ent; C.n_rel = n_rel; C.score = d_score; C.loss = d_loss; C.work = d_work;
+  C.grad = {d_grad_ent, nullptr, d_grad_rel, nullptr};
+  C.lr = lr;
+  C.upd = {d_ent, nullptr, d_rel, nullptr};
+  if (parity < 0 || parity > 1) return MMRE_ERR_ARG;
+  C.parity = (int)parity;
+  rc = step_check(C, T);
+  if (rc) return rc;
+  rc = ns_call(C, nullptr,
+               NSArgs{model, norm_flag, 0, dim, 0.0f, 0.0f, d_ent, nullptr, d_rel, nullptr, d_batch_h, d_batch_t,
+                      d_batch_r, batch, neg, loss_margin, adv_temperature, regul_rate},
+               stream);
+  if (rc) return rc;
+  if (!is_transe(model) || !fused_supported(C.A)) return MMRE_ERR_SHAPE;  // the fused TransE path's shapes only
+  return step_openke_impl(C, T);
 }
 
+extern "C" int mmre_ns_step_openke(MMRE_STEP_OPENKE_PARAMS) {
+  return mmre_ns_step_openke_pipe(MMRE_STEP_OPENKE_ARGS, 0, 0, nullptr, nullptr, nullptr, nullptr);
+}
 
 // The one-call step for DistMult / ComplEx / RotatE (step_openke_gen_impl): the sampler arguments of
 // mmre_ns_step_openke, then the generic model's (ComplEx im tables, RotatE's model margin and phase),
 // then prepared (bit 0: d_batch_* already drawn) and the next batch's buffers (nullable).
 extern "C" int mmre_ns_step_openke_gen_pipe_ex(
-    const int64_t* d_train_list, int64_t train_total, const int64_t* d_head_hrt, const int64_t* d_tail_hrt,
-    const int64_t* d_rel_hrt, const int64_t* d_lef_head, const int64_t* d_rig_head, const int64_t* d_lef_tail,
-    const int64_t* d_rig_tail, const int64_t* d_lef_rel, const int64_t* d_rig_rel, const float* d_left_mean,
-    const float* d_right_mean, uint64_t* d_seeds, int64_t work_threads, int64_t mode, const int32_t* d_blocks,
-    int64_t n_blocks, int64_t* d_batch_h, int64_t* d_batch_t, int64_t* d_batch_r, float* d_batch_y, int32_t* d_ticket,
-    int model, float model_margin, int use_model_margin, float* d_ent, float* d_ent_im, float* d_rel, float* d_rel_im,
-    int64_t n_ent, int64_t n_rel, int dim, float phase_denom, int64_t batch, int64_t neg, float loss_margin,
-    float adv_temperature, float regul_rate, float* d_score, float* d_loss, float* d_grad_ent, float* d_grad_ent_im,
-    float* d_grad_rel, float* d_grad_rel_im, float* d_work, float lr, void* stream, int64_t prepared,
-    int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y, const mmre_ns_opts_t* opts) {
+    MMRE_SAMPLER_PARAMS, int model, float model_margin, int use_model_margin, float* d_ent, float* d_ent_im,
+    float* d_rel, float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim, float phase_denom, int64_t batch, int64_t neg,
+    float loss_margin, float adv_temperature, float regul_rate, float* d_score, float* d_loss, float* d_grad_ent,
+    float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work, float lr, void* stream,
+    int64_t prepared, int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y,
+    const mmre_ns_opts_t* opts) {
   if (ns_opts_check(opts)) return MMRE_ERR_ARG;
-  if (!d_train_list || !d_head_hrt || !d_tail_hrt || !d_lef_head || !d_rig_head || !d_lef_tail || !d_rig_tail ||
-      !d_seeds || !d_batch_h || !d_batch_t || !d_batch_r || !d_batch_y || !d_ticket)
-    return MMRE_ERR_ARG;
-  if ((d_left_mean == nullptr) != (d_right_mean == nullptr)) return MMRE_ERR_ARG;
-  if (train_total <= 0 || n_ent <= 1 || work_threads <= 0 || batch <= 0 || neg <= 0 || mode < -1 || mode > 1)
-    return MMRE_ERR_ARG;
-  if (n_blocks < 0 || (n_blocks > 0 && !d_blocks)) return MMRE_ERR_ARG;
-  if (!d_score || !d_loss || !d_grad_ent || !d_grad_rel || !d_work || n_rel <= 0 || !(lr != 0.0f)) return MMRE_ERR_ARG;
+  NSStep T;
+  int rc = step_sampler(T, MMRE_SAMPLER_ARGS, n_ent, n_rel, batch, neg);
+  if (rc) return rc;
+  T.prepared = prepared;
+  T.next_h = d_next_h; T.next_t = d_next_t; T.next_r = d_next_r; T.next_y = d_next_y;
+  NSCall C;
+  C.n_ent = n_ent; C.n_rel = n_rel; C.score = d_score; C.loss = d_loss; C.work = d_work;
+  C.grad = {d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im};
+  C.lr = lr;
+  C.upd = {d_ent, d_ent_im, d_rel, d_rel_im};
+  rc = step_check(C, T);
+  if (rc) return rc;
   if (model == MMRE_COMPLEX && (!d_ent_im || !d_rel_im || !d_grad_ent_im || !d_grad_rel_im)) return MMRE_ERR_ARG;
-  if (prepared < 0 || prepared > 3) return MMRE_ERR_ARG;
-  if (d_next_h && (!d_next_t || !d_next_r || !d_next_y || d_next_h == d_batch_h)) return MMRE_ERR_ARG;
-  const int64_t n_sampler = (batch * (1 + neg) + 255) / 256;
-  const OpenKESamplerArgs sa{d_train_list, d_head_hrt, d_tail_hrt, d_rel_hrt, d_lef_head, d_rig_head, d_lef_tail,
-                             d_rig_tail, d_lef_rel, d_rig_rel, d_left_mean, d_right_mean, train_total, n_ent, n_rel,
-                             d_seeds, work_threads, batch, neg, 0, mode, d_blocks, n_blocks, d_batch_h, d_batch_t,
-                             d_batch_r, d_batch_y, d_ticket, mmre_sampler_draws_per_positive(neg, 0, mode), nullptr};
-  return step_openke_gen_impl(sa, n_sampler, model, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im,
-                              n_ent, n_rel, dim, phase_denom, batch, neg, loss_margin, adv_temperature, regul_rate,
-                              d_score, d_loss, d_grad_ent, d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, lr,
-                              (hipStream_t)stream, prepared, d_next_h, d_next_t, d_next_r, d_next_y, opts);
+  rc = ns_call(C, opts,
+               NSArgs{model, 0, use_model_margin, dim, model_margin, phase_denom, d_ent, d_ent_im, d_rel, d_rel_im,
+                      d_batch_h, d_batch_t, d_batch_r, batch, neg, loss_margin, adv_temperature, regul_rate},
+               stream);
+  if (rc) return rc;
+  rc = ns_adagrad(C, opts);  // the sum tables before the forward is launched
+  if (rc) return rc;
+  if (is_transe(model) || !fused_supported(C.A)) return MMRE_ERR_SHAPE;
+  return step_openke_gen_impl(C, T);
 }
 
 extern "C" int mmre_ns_step_openke_gen_pipe(
-    const int64_t* d_train_list, int64_t train_total, const int64_t* d_head_hrt, const int64_t* d_tail_hrt,
-    const int64_t* d_rel_hrt, const int64_t* d_lef_head, const int64_t* d_rig_head, const int64_t* d_lef_tail,
-    const int64_t* d_rig_tail, const int64_t* d_lef_rel, const int64_t* d_rig_rel, const float* d_left_mean,
-    const float* d_right_mean, uint64_t* d_seeds, int64_t work_threads, int64_t mode, const int32_t* d_blocks,
-    int64_t n_blocks, int64_t* d_batch_h, int64_t* d_batch_t, int64_t* d_batch_r, float* d_batch_y, int32_t* d_ticket,
-    int model, float model_margin, int use_model_margin, float* d_ent, float* d_ent_im, float* d_rel, float* d_rel_im,
-    int64_t n_ent, int64_t n_rel, int dim, float phase_denom, int64_t batch, int64_t neg, float loss_margin,
-    float adv_temperature, float regul_rate, float* d_score, float* d_loss, float* d_grad_ent, float* d_grad_ent_im,
-    float* d_grad_rel, float* d_grad_rel_im, float* d_work, float lr, void* stream, int64_t prepared,
-    int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y) {
-  return mmre_ns_step_openke_gen_pipe_ex(
-      d_train_list, train_total, d_head_hrt, d_tail_hrt, d_rel_hrt, d_lef_head, d_rig_head, d_lef_tail, d_rig_tail,
-      d_lef_rel, d_rig_rel, d_left_mean, d_right_mean, d_seeds, work_threads, mode, d_blocks, n_blocks, d_batch_h,
-      d_batch_t, d_batch_r, d_batch_y, d_ticket, model, model_margin, use_model_margin, d_ent, d_ent_im, d_rel, d_rel_im,
-      n_ent, n_rel, dim, phase_denom, batch, neg, loss_margin, adv_temperature, regul_rate, d_score, d_loss, d_grad_ent,
-      d_grad_ent_im, d_grad_rel, d_grad_rel_im, d_work, lr, stream, prepared, d_next_h, d_next_t, d_next_r, d_next_y,
-      nullptr);
+    MMRE_SAMPLER_PARAMS, int model, float model_margin, int use_model_margin, float* d_ent, float* d_ent_im,
+    float* d_rel, float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim, float phase_denom, int64_t batch, int64_t neg,
+    float loss_margin, float adv_temperature, float regul_rate, float* d_score, float* d_loss, float* d_grad_ent,
+    float* d_grad_ent_im, float* d_grad_rel, float* d_grad_rel_im, float* d_work, float lr, void* stream,
+    int64_t prepared, int64_t* d_next_h, int64_t* d_next_t, int64_t* d_next_r, float* d_next_y) {
+  return mmre_ns_step_openke_gen_pipe_ex(MMRE_SAMPLER_ARGS, model, model_margin, use_model_margin, d_ent, d_ent_im,
+                                         d_rel, d_rel_im, n_ent, n_rel, dim, phase_denom, batch, neg, loss_margin,
+                                         adv_temperature, regul_rate, d_score, d_loss, d_grad_ent, d_grad_ent_im,
+                                         d_grad_rel, d_grad_rel_im, d_work, lr, stream, prepared, d_next_h, d_next_t,
+                                         d_next_r, d_next_y, nullptr);
 }
+

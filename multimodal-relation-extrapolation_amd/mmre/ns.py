@@ -61,8 +61,13 @@ def rows_supported(spec: NSSpec, neg: int) -> bool:
     return _query("mmre_ns_rows_supported", spec.dim, int(neg))
 
 
-def _scalar_args(spec, batch, neg, loss_margin, adv_t, regul_rate):
-    return (spec.model_id, int(spec.norm_flag), spec.model_margin, int(spec.use_model_margin))
+def _prefix(spec, tables, rows=(), sizes=False):
+    """What every NS entry point's arguments start with: the model, its tables (ent, ent_im, rel,
+    rel_im), [sizes: their row counts,] dim and phase, [the index rows (h, t, r)]."""
+    ent, ent_im, rel, rel_im = tables
+    return ((spec.model_id, int(spec.norm_flag), spec.model_margin, int(spec.use_model_margin), ptr(ent), ptr(ent_im),
+             ptr(rel), ptr(rel_im)) + ((int(ent.shape[0]), int(rel.shape[0])) if sizes else ())
+            + (spec.dim, spec.phase_denom) + tuple(ptr(x) for x in rows))
 
 
 def _ns_opts(kind: int, adagrad=None):
@@ -113,26 +118,24 @@ class _FusedNS(torch.autograd.Function):
         ctx.sgd = sgd if ctx.fused else None
         ctx.kind = kind
         opts = _ns_opts(kind)
+        tables = (ent, ent_im, rel, rel_im)
         if ctx.fused:
             E, R = int(ent.shape[0]), int(rel.shape[0])
             work = torch.empty(int(lib().mmre_ns_fused_workspace(spec.model_id, int(spec.norm_flag), batch, neg, E, R,
                                                                  spec.dim)), dtype=torch.float32, device=dev)
             if events is not None:
                 events[0].record()
-            _call_ex("mmre_ns_fused_forward", opts, spec.model_id, int(spec.norm_flag), spec.model_margin,
-                     int(spec.use_model_margin), ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), E, R, spec.dim,
-                     spec.phase_denom, ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t),
-                     float(regul_rate), ptr(score), ptr(loss), ptr(work), stream_ptr(dev))
+            _call_ex("mmre_ns_fused_forward", opts, *_prefix(spec, tables, (h, t, r), sizes=True), batch, neg,
+                     float(loss_margin), float(adv_t), float(regul_rate), ptr(score), ptr(loss), ptr(work),
+                     stream_ptr(dev))
             if events is not None:
                 events[1].record()
             ctx.work = work
             ctx.events = events
         else:
             work = torch.empty(int(lib().mmre_ns_workspace(batch, neg)), dtype=torch.float32, device=dev)
-            _call_ex("mmre_ns_forward", opts, spec.model_id, int(spec.norm_flag), spec.model_margin,
-                     int(spec.use_model_margin), ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), spec.dim,
-                     spec.phase_denom, ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t),
-                     float(regul_rate), ptr(score), ptr(loss), ptr(work), stream_ptr(dev))
+            _call_ex("mmre_ns_forward", opts, *_prefix(spec, tables, (h, t, r)), batch, neg, float(loss_margin),
+                     float(adv_t), float(regul_rate), ptr(score), ptr(loss), ptr(work), stream_ptr(dev))
         ctx.save_for_backward(ent, rel, ent_im if ent_im is not None else ent, rel_im if rel_im is not None else rel,
                               h, t, r, score)
         return loss[0], score
@@ -154,10 +157,9 @@ class _FusedNS(torch.autograd.Function):
             ev = ctx.events
             if ev is not None and len(ev) > 2:
                 ev[2].record()
-            args = (spec.model_id, int(spec.norm_flag), spec.model_margin, int(spec.use_model_margin), ptr(ent),
-                    ptr(ent_im), ptr(rel), ptr(rel_im), int(ent.shape[0]), int(rel.shape[0]), spec.dim,
-                    spec.phase_denom, ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t),
-                    float(regul_rate), ptr(score), ptr(gl), ptr(ge), ptr(gei), ptr(gr), ptr(gri), ptr(ctx.work))
+            args = (*_prefix(spec, (ent, ent_im, rel, rel_im), (h, t, r), sizes=True), batch, neg, float(loss_margin),
+                    float(adv_t), float(regul_rate), ptr(score), ptr(gl), ptr(ge), ptr(gei), ptr(gr), ptr(gri),
+                    ptr(ctx.work))
             if ctx.sgd is not None:  # the optimizer's plain step in the same pass (step() skips these tables)
                 opt, lr, tables = ctx.sgd
                 adagrad = opt.fused_state(tables) if hasattr(opt, "fused_state") else None
@@ -179,10 +181,9 @@ class _FusedNS(torch.autograd.Function):
         gri = torch.empty_like(rel_im) if rel_im is not None else None
         nw = int(lib().mmre_rows_backward_workspace(spec.model_id, batch * (1 + neg), E, R, spec.dim))
         work = torch.empty(nw, dtype=torch.float32, device=dev)
-        _call_ex("mmre_ns_backward", _ns_opts(ctx.kind), spec.model_id, int(spec.norm_flag), spec.model_margin,
-                 int(spec.use_model_margin), ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), spec.dim, spec.phase_denom,
-                 ptr(h), ptr(t), ptr(r), batch, neg, float(loss_margin), float(adv_t), float(regul_rate), ptr(score),
-                 ptr(gl), ptr(ge), ptr(gei), ptr(gr), ptr(gri), E, R, ptr(work), nw, stream_ptr(dev))
+        _call_ex("mmre_ns_backward", _ns_opts(ctx.kind), *_prefix(spec, (ent, ent_im, rel, rel_im), (h, t, r)), batch,
+                 neg, float(loss_margin), float(adv_t), float(regul_rate), ptr(score), ptr(gl), ptr(ge), ptr(gei),
+                 ptr(gr), ptr(gri), E, R, ptr(work), nw, stream_ptr(dev))
         return ge, gr, gei, gri, None, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -236,9 +237,8 @@ class _ScoreRows(torch.autograd.Function):
         dev = ent.device
         score = torch.empty(n, dtype=torch.float32, device=dev)
         work = torch.empty(int(lib().mmre_ns_workspace(n, 0)), dtype=torch.float32, device=dev)
-        call("mmre_ns_forward", spec.model_id, int(spec.norm_flag), spec.model_margin, int(spec.use_model_margin),
-             ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), spec.dim, spec.phase_denom, ptr(h), ptr(t), ptr(r), n, 0,
-             0.0, 0.0, 0.0, ptr(score), None, ptr(work), stream_ptr(dev))
+        call("mmre_ns_forward", *_prefix(spec, (ent, ent_im, rel, rel_im), (h, t, r)), n, 0, 0.0, 0.0, 0.0, ptr(score),
+             None, ptr(work), stream_ptr(dev))
         ctx.save_for_backward(ent, rel, ent_im if ent_im is not None else ent, rel_im if rel_im is not None else rel,
                               h, t, r)
         ctx.has_im = ent_im is not None
@@ -260,10 +260,8 @@ class _ScoreRows(torch.autograd.Function):
         n = int(h.shape[0])
         nw = int(lib().mmre_rows_backward_workspace(spec.model_id, n, E, R, spec.dim))
         work = torch.empty(nw, dtype=torch.float32, device=ent.device)
-        call("mmre_score_rows_backward", spec.model_id, int(spec.norm_flag), spec.model_margin,
-             int(spec.use_model_margin), ptr(ent), ptr(ent_im), ptr(rel), ptr(rel_im), spec.dim, spec.phase_denom,
-             ptr(h), ptr(t), ptr(r), n, ptr(g), ptr(ge), ptr(gei), ptr(gr), ptr(gri), E, R, ptr(work), nw,
-             stream_ptr(ent.device))
+        call("mmre_score_rows_backward", *_prefix(spec, (ent, ent_im, rel, rel_im), (h, t, r)), n, ptr(g), ptr(ge),
+             ptr(gei), ptr(gr), ptr(gri), E, R, ptr(work), nw, stream_ptr(ent.device))
         return ge, gr, gei, gri, None, None, None, None
 
 
@@ -357,33 +355,45 @@ class OpenKETrainStep:
         return (self.sampler.draws, tuple(t._version for t in (self.ent, self.rel, self.ent_im, self.rel_im)
                                           if t is not None))
 
-    def _generic_call(self, prefetch: bool):
-        s = self.spec
-        E, R = int(self.ent.shape[0]), int(self.rel.shape[0])
+    def _pipelined(self, prefetch: bool, prepass: bool, launch):
+        """The prefetch bookkeeping around one step: launch(sampler arguments for the current batch,
+        prepared, parity, the next batch's four buffer pointers or Nones) makes the call and marks what
+        it wrote. prepared bit 0: the current batch was drawn by the previous call's gradient launch
+        (else this call's first launch draws it); bit 1 (prepass: TransE alone tracks it): the
+        pre-pass that launch made is current."""
         p = self._parity
         cur = self._bufs[p]
         nxt = self._bufs[1 - p] if (self.pipeline and prefetch) else None
         st = self._state()
-        prepared = 1 if (self.pipeline and self._ready is not None and self._ready[0] == st[0]) else 0
-        args = self.sampler.step_args(self.B, self.K, self.mode, cur, advance=not prepared)
-        tables = [x for x in (self.ent, self.rel, self.ent_im, self.rel_im) if x is not None]
-        opts = _ns_opts(self.kind, self.adagrad.fused_state(tables) if self.adagrad is not None else None)
-        _call_ex("mmre_ns_step_openke_gen_pipe", opts, *args, s.model_id, s.model_margin, int(s.use_model_margin),
-                 ptr(self.ent), ptr(self.ent_im), ptr(self.rel), ptr(self.rel_im), E, R, s.dim, s.phase_denom, self.B,
-                 self.K, self.margin, self.adv, self.regul, ptr(self.score), ptr(self.loss), ptr(self.ge),
-                 ptr(self.gei), ptr(self.gr), ptr(self.gri), ptr(self.work), self.lr, stream_ptr(self.ent.device),
-                 prepared, ptr(nxt["batch_h"]) if nxt else None, ptr(nxt["batch_t"]) if nxt else None,
-                 ptr(nxt["batch_r"]) if nxt else None, ptr(nxt["batch_y"]) if nxt else None)
-        mark_written(self.ent, self.rel, self.ent_im, self.rel_im)
-        if self.adagrad is not None:
-            self.adagrad.count_fused_step(tables)
+        prepared = 0
+        if self.pipeline and self._ready is not None:
+            prepared = (1 if self._ready[0] == st[0] else 0) | (2 if prepass and self._ready[1] == st[1] else 0)
+        args = self.sampler.step_args(self.B, self.K, self.mode, cur, advance=not prepared & 1)
+        keys = ("batch_h", "batch_t", "batch_r", "batch_y")
+        launch(args, prepared, p, tuple(ptr(nxt[k]) if nxt else None for k in keys))
         self.batch = cur
-        if nxt is not None:
+        if nxt is not None:  # (after the step's update was marked: the prefetch's state includes it)
             self.sampler.advance(self.B, self.K, self.mode)
             self._parity = 1 - p
             self._ready = self._state()
         else:
             self._ready = None
+
+    def _generic_call(self, prefetch: bool):
+        s = self.spec
+        tables = [x for x in (self.ent, self.rel, self.ent_im, self.rel_im) if x is not None]
+        model = _prefix(s, (self.ent, self.ent_im, self.rel, self.rel_im), sizes=True)
+
+        def launch(args, prepared, parity, nx):
+            opts = _ns_opts(self.kind, self.adagrad.fused_state(tables) if self.adagrad is not None else None)
+            _call_ex("mmre_ns_step_openke_gen_pipe", opts, *args, model[0], *model[2:], self.B, self.K, self.margin,
+                     self.adv, self.regul, ptr(self.score), ptr(self.loss), ptr(self.ge), ptr(self.gei), ptr(self.gr),
+                     ptr(self.gri), ptr(self.work), self.lr, stream_ptr(self.ent.device), prepared, *nx)
+            mark_written(self.ent, self.rel, self.ent_im, self.rel_im)
+            if self.adagrad is not None:
+                self.adagrad.count_fused_step(tables)
+
+        self._pipelined(prefetch, False, launch)  # (no norm_flag in this entry point: model[1])
         self.ent.grad, self.rel.grad = self.ge, self.gr
         if self.ent_im is not None:
             self.ent_im.grad, self.rel_im.grad = self.gei, self.gri
@@ -403,25 +413,10 @@ class OpenKETrainStep:
             call("mmre_ns_step_openke", *self.sampler.step_args(self.B, self.K, self.mode, self.batch), *tail)
             mark_written(self.ent, self.rel)
         else:
-            p = self._parity
-            cur, nxt = self._bufs[p], (self._bufs[1 - p] if prefetch else None)
-            st = self._state()
-            # bit 0: the current batch was drawn by the previous call's gradient launch (else this
-            # call's first launch draws it); bit 1: the pre-pass that launch made is current
-            prepared = 0
-            if self._ready is not None:
-                prepared = (1 if self._ready[0] == st[0] else 0) | (2 if self._ready[1] == st[1] else 0)
-            args = self.sampler.step_args(self.B, self.K, self.mode, cur, advance=not prepared & 1)
-            nx = (ptr(nxt["batch_h"]), ptr(nxt["batch_t"]), ptr(nxt["batch_r"]), ptr(nxt["batch_y"])) if nxt \
-                else (None, None, None, None)
-            call("mmre_ns_step_openke_pipe", *args, *tail, prepared, p, *nx)
-            mark_written(self.ent, self.rel)  # the SGD update, before the prefetch's state is recorded
-            self.batch = cur
-            if nxt is not None:
-                self.sampler.advance(self.B, self.K, self.mode)
-                self._parity = 1 - p
-                self._ready = self._state()
-            else:
-                self._ready = None
+            def launch(args, prepared, parity, nx):
+                call("mmre_ns_step_openke_pipe", *args, *tail, prepared, parity, *nx)
+                mark_written(self.ent, self.rel)  # the SGD update, before the prefetch's state is recorded
+
+            self._pipelined(prefetch, True, launch)
         self.ent.grad, self.rel.grad = self.ge, self.gr  # as backward() leaves them
         return self.loss[0]
