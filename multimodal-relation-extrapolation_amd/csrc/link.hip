@@ -1072,7 +1072,7 @@ __device__ __forceinline__ void sweep_valu_body(
   // dynamic scheduling claims chunks of consecutive units (the units of a group are query-tile
   // major: a chunk mostly keeps its query tile, so its counts flush and its query metadata loads
   // once, not at every unit): 4 when a workgroup sweeps many units, 1 for a rank's small share
-  // (launch_valu_one; C2 N = 1, per evaluation: chunks of 1 / 2 / 4 / 8 / 16 units 1.053 / 1.007 /
+  // (valu_grid; C2 N = 1, per evaluation: chunks of 1 / 2 / 4 / 8 / 16 units 1.053 / 1.007 /
   // 0.975 / 0.997 / 1.017 ms; 8-way shares: 1 or 2 best)
   constexpr int ch_log2 = DYNC >= 4 ? 2 : DYNC >= 2 ? 1 : 0;
   constexpr int ch_mask = (1 << ch_log2) - 1;
@@ -2539,9 +2539,11 @@ static int l1q_rows8(int dim) { return (int)round_up((plane_rows(MMRE_TRANSE_L1,
 // the counts are the exact sweep's bit for bit. ~2e-4 of the C3 pairs and 2e-5 of C5's land
 // in the list. A list that overflows its capacity sets a flag on the device: the raw counts
 // are reset and the exact f32 sweep runs instead (gated launches, no host round trip).
-// Workspace: header (BF3_HDR bytes: word 1 overflow flag, words 2-3 the appended pairs (uint64)) | pair list
-// (bf3_cap int2) | |q| (q_pad floats) | |e| (e_pad floats) | split query planes (K/16 blocks
-// x q_pad rows x 64 B: hi[16] | lo[16]) | split entity planes (K/16 x e_pad x 64 B).
+// Workspace: header (BF3_HDR bytes of 32-bit words: word 1 the overflow flag, word 4 the segment
+// capacity, the list's append counters from word BF3_SEG_W0 on, one per 128-B line: segment s at
+// BF3_SEG_W0 + 32 s, the shared half's at s = BF3_SEGS) | pair list (bf3_cap int2) | |q| (q_pad
+// floats) | |e| (e_pad floats) | split query planes (K/16 blocks x q_pad rows x 64 B: hi[16] |
+// lo[16]) | split entity planes (K/16 x e_pad x 64 B) | the wide sweep's operands (Bf3Work).
 // The list: half of it cut into BF3_SEGS segments of cap / (2 BF3_SEGS) pairs, each with its own
 // counter on a 128-B line of the header (32-bit words BF3_SEG_W0 + 32 s), the other half shared
 // (its counter: segment index BF3_SEGS). A sweep workgroup b appends to segment b % BF3_SEGS and,
@@ -3403,29 +3405,146 @@ __global__ void k_bf3_stats(const uint32_t* __restrict__ hdr, unsigned long long
 }
 
 // ---------------------------------------------------------------- launch ---
+// An entry point fills one SweepCall, each kernel family has one launcher that takes it, run-time
+// choices reach the template arguments through with_op / with_bool(s) / with_chunk, grid rules are functions.
+
 // Resident workgroups of a persistent sweep: the occupancy API's blocks per CU (capped at 4,
-// the VGPR-limited residency of a 256-thread group at <= 128 VGPRs) x the device's CUs.
-static int resident_groups_query(const void* kernel, int threads) {
-  int dev = 0, cus = 256, per = 0;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, threads, 0) != hipSuccess || per <= 0) per = 1;
-  if (per > 4) per = 4;
-  return cus * per;
-}
-// (queried once per kernel and device: the fused evaluation asks on every call)
+// the VGPR-limited residency of a 256-thread group at <= 128 VGPRs) x the device's CUs. Queried
+// once per kernel and device: the fused evaluation asks on every call.
 static int resident_groups(const void* kernel, int threads) {
   static std::mutex mu;
   static std::map<std::tuple<const void*, int, int>, int> cache;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) dev = 0;
   std::lock_guard<std::mutex> lock(mu);
-  const auto key = std::make_tuple(kernel, threads, dev);
-  auto it = cache.find(key);
-  if (it == cache.end()) it = cache.emplace(key, resident_groups_query(kernel, threads)).first;
+  const auto [it, fresh] = cache.try_emplace(std::make_tuple(kernel, threads, dev), 0);
+  if (fresh) {
+    int cus = 0, per = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, threads, 0) != hipSuccess || per <= 0) per = 1;
+    it->second = cus * std::min(per, 4);
+  }
   return it->second;
+}
+
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class F>
+static int with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <class F>  // f(a_, b_, c_)
+static int with_bools(bool a, bool b, bool c, F&& f) {
+  return with_bool(a, [&](auto a_) {
+    return with_bool(b, [&](auto b_) { return with_bool(c, [&](auto c_) { return f(a_, b_, c_); }); });
+  });
+}
+// f(int_c<DYNC>) for the units per claim, among the instances the caller has (MASK: their sum)
+template <int MASK, class F>
+static void with_chunk(int chunk, F&& f) {
+  if ((MASK & 4) && chunk == 4) f(int_c<MASK & 4>{});
+  else if ((MASK & 2) && chunk == 2) f(int_c<MASK & 2>{});
+  else if ((MASK & 1) && chunk == 1) f(int_c<MASK & 1>{});
+  else f(int_c<0>{});
+}
+// f(int_c<OP>) for the score operator op = op_of_model(model), 0 .. 4
+template <int OP = 0, class F>
+static int with_op(int op, F&& f) {
+  if constexpr (OP < 4) {
+    if (op != OP) return with_op<OP + 1>(op, f);
+  }
+  return f(int_c<OP>{});
+}
+
+// What every sweep launcher needs. An entry point fills the first part from its ABI arguments
+// (ent: the table's k-major planes), check_link_args validates it, sweep_slice() the rest.
+struct SweepCall {
+  hipStream_t st;
+  const float* ent;
+  int64_t e_pad;
+  const float* q;
+  int64_t q_pad, n_query;
+  int pred_kind;
+  float margin;
+  const float* truth;
+  const int32_t* q_true;
+  const int64_t* qr;
+  const int8_t* qmode;
+  const uint32_t *type_head, *type_tail;  // both or neither
+  int32_t* counts;
+  float* scores;
+  // sweep_slice: ent now at the first column of the slice [e_base, e_base + n_slice) -- e_cols
+  // columns in n_et whole tiles; kp K rows of the planes (ktot for the MFMA sweeps); tw type words
+  int kp, n_et, e_base;
+  int64_t n_slice, e_cols, tw;
+  bool tc() const { return type_head != nullptr; }
+  bool store() const { return scores != nullptr; }
+  int64_t q_tiles() const { return q_pad / TQ; }
+};
+
+// The sweep over entities [e_begin, e_end) of the table (e_begin a multiple of TE): the kernels
+// see the slice (pointer offset by e_begin columns, row stride e_pad, n_slice ids) and add
+// e_base back wherever an absolute id matters (truth exclusion, type-constraint bits).
+static int sweep_slice(SweepCall& C, int64_t n_ent, int64_t e_begin, int64_t e_end, int kp) {
+  if (e_begin < 0 || e_begin % TE || e_end <= e_begin || e_end > n_ent) return MMRE_ERR_ARG;
+  C.ent += e_begin;
+  C.kp = kp;
+  C.e_base = (int)e_begin;
+  C.n_slice = e_end - e_begin;
+  C.n_et = (int)((C.n_slice + TE - 1) / TE);
+  C.e_cols = round_up(e_end, TE) - e_begin;
+  C.tw = (n_ent + 31) / 32;  // type bitsets span the whole table
+  return MMRE_OK;
+}
+// the same call over other planes of kp rows (ent: the table's first column, as the ABI's)
+static SweepCall planes(SweepCall C, const void* ent, const void* q, int kp) {
+  C.ent = (const float*)ent + C.e_base;
+  C.q = (const float*)q;
+  C.kp = kp;
+  return C;
+}
+static bool valid_model(int m) { return m >= MMRE_TRANSE_L1 && m <= MMRE_ROTATE; }
+static int check_link_args(int model, const SweepCall& C, int64_t n_ent) {
+  if (!valid_model(model)) return MMRE_ERR_MODEL;
+  if (C.pred_kind < 0 || C.pred_kind > 4) return MMRE_ERR_ARG;
+  if (!C.ent || !C.q || !C.q_true || !C.counts || !C.truth || !C.qmode || !C.qr) return MMRE_ERR_ARG;
+  if (C.n_query <= 0 || n_ent <= 0 || C.e_pad < n_ent || C.e_pad % TE || C.q_pad < C.n_query || C.q_pad % TQ)
+    return MMRE_ERR_ARG;
+  if ((C.type_head == nullptr) != (C.type_tail == nullptr)) return MMRE_ERR_ARG;
+  if (n_ent > (int64_t)INT32_MAX - 256) return MMRE_ERR_SHAPE;  // padded ids stay int32
+  return MMRE_OK;
+}
+
+// Work units (query tile x entity tile) of an XCD-grouped sweep: the busiest group's (UnitMap) x 8.
+static int64_t sweep_units(int64_t q_tiles, int n_et) {
+  return n_et >= 8 ? 8 * q_tiles * ((n_et + 7) / 8) : q_tiles * n_et;
+}
+static int xcd_groups(int g, int n_et) { return (g % 8 == 0 && n_et >= 8) ? 8 : 1; }  // of a grid of g workgroups
+// MMRE_SWEEP_GRID (experiments): a number = that many persistent workgroups; "tiles" = the
+// caller's tile grid, where it has one (the VALU sweep)
+static int grid_override(int g, int tiles = 0) {
+  static const char* env = getenv("MMRE_SWEEP_GRID");
+  if (env && env[0] == 't' && tiles > 0) return tiles;
+  return (env && env[0] >= '1' && env[0] <= '9') ? atoi(env) : g;
+}
+// Units per claim of a dynamically scheduled sweep: 4 from 16 units per workgroup on, else 1
+// (measurements: launch_valu_grp, sweep_valu_body). MMRE_SWEEP_CHUNK (A/B) forces 1, 4 or -- where
+// the launcher has that instance (allow2) -- 2.
+static int sweep_chunk(int64_t per_wg, bool allow2) {
+  static const char* env = getenv("MMRE_SWEEP_CHUNK");
+  if (!env) return per_wg >= 16 ? 4 : 1;
+  const int v = atoi(env);
+  return v >= 4 ? 4 : (allow2 && v >= 2) ? 2 : 1;
+}
+// Units entity-tile-major inside each XCD group when the entity planes outgrow the caches
+// (> 64 MB; the 256 MB MALL also holds the query planes): a workgroup's consecutive units then
+// share its entity tile (L2-resident) and sweep the query tiles, which stay MALL-resident, so
+// the table streams from HBM about once instead of once per query tile (C5, a 1 GB table:
+// 35.8 -> 34.5 ms on one box, 60 -> ~1 GB of entity reads per launch); C3's 20 MB planes keep
+// the query-major order (0.979 vs 0.982 ms). MMRE_MFMA_EMAJOR (experiments): 0 / 1 force the order.
+static int mfma_emajor(int64_t e_pad, int ktot) {
+  static const char* env = getenv("MMRE_MFMA_EMAJOR");
+  return env ? atoi(env) : ((double)e_pad * ktot * 4.0 > 64.0 * (1 << 20) ? 1 : 0);
 }
 
 static int launch_finalize(hipStream_t st, int32_t* counts, int64_t n_query, bool tc) {
@@ -3435,16 +3554,13 @@ static int launch_finalize(hipStream_t st, int32_t* counts, int64_t n_query, boo
   return MMRE_OK;
 }
 
-template <int OP, bool TCV, bool STV, int PK>
-static void launch_valu_one(hipStream_t st, const float* ent_km, int64_t e_pad, int64_t n_ent, int n_et, int e_base,
-                            const float* q_km, int64_t q_pad, int64_t n_query, int kp, int pk, float m,
-                            const float* thr, const int32_t* qtrue, const int64_t* qr, const int8_t* qmode,
-                            const uint32_t* th, const uint32_t* tt, int64_t tw, int32_t* counts, float* scores,
-                            L1Q l1) {
+struct ValuGrid { int g, ng, chunk; };  // workgroups, XCD groups, units per claim (0: static ranges)
+// (k_static / k_dyn: the instance with static ranges and the dynamically scheduled one, if any)
+static ValuGrid valu_grid(const SweepCall& C, const L1Q& l1, const void* k_static, const void* k_dyn) {
   // 16 workgroups per resident slot: short per-workgroup ranges let the dispatcher balance
   // CUs that run at different speeds (C2 on MI355X: 1,024 groups 4.0 ms, 8,192 3.43 ms,
   // 16,384 3.30 ms, 30,528 (one unit each) 3.36 ms).
-  int g = 16 * resident_groups((const void*)k_sweep_valu<OP, TCV, STV, PK>, NT);
+  int g = 16 * resident_groups(k_static, NT);
   // a gated launch (the L1 filter's f32 fallback, l1.gate) runs 4 workgroups per resident
   // slot: when the gate is shut -- every time but the rare fallback -- its workgroups only
   // read the flag and leave, and a 16x grid of such workgroups cost 77 us per evaluation at
@@ -3457,81 +3573,62 @@ static void launch_valu_one(hipStream_t st, const float* ent_km, int64_t e_pad, 
   // Dynamic scheduling (l1.wq, the TransE L1 filter sweeps): one persistent workgroup per
   // resident slot, units from the XCD groups' work counters -- the shut gated launch too (its
   // workgroups only read the gate).
-  constexpr bool DYN_OK = OP == 5 || OP == 6;
-  const bool dyn = DYN_OK && l1.wq != nullptr && kp / KC >= 2;
-  int chunk = 0;  // dynamic scheduling: units per claim (0: static ranges)
+  const bool dyn = k_dyn != nullptr && l1.wq != nullptr && C.kp / KC >= 2;
+  const int64_t q_tiles = C.q_tiles();
+  int chunk = 0;
   if (dyn) {
-    g = resident_groups((const void*)k_sweep_valu<OP, TCV, STV, PK, DYN_OK ? 4 : 0>, NT);
-    const int64_t per_wg = (q_pad / TQ) * n_et / (g > 0 ? g : 1);
-    static const char* ch_env = getenv("MMRE_SWEEP_CHUNK");  /* A/B: 1 or 4 units per claim */
-    chunk = ch_env ? (atoi(ch_env) >= 4 ? 4 : 1) : (per_wg >= 16 ? 4 : 1);
+    g = resident_groups(k_dyn, NT);
+    chunk = sweep_chunk(q_tiles * C.n_et / (g > 0 ? g : 1), false);
   }
   // Small sweeps (a rank's share under relation sharding): no more workgroups than the
   // busiest XCD group has units, so every workgroup gets at most one unit and no empty
   // workgroups are dispatched (C2 at 8-way: 4,380 sweeps 0.52 -> 0.47 ms; 4-way 0.89 -> 0.85).
-  {
-    const int64_t q_tiles = q_pad / TQ;
-    const int64_t units = (n_et >= 8) ? 8 * q_tiles * ((n_et + 7) / 8) : q_tiles * n_et;
-    if (units < g) g = (int)(units > 0 ? units : 1);
-    // Dynamic scheduling of a small share: as many workgroups per XCD group as make its units an
-    // (almost) whole number of rounds -- the same rounds as the full grid, no nearly empty last
-    // round (an 8-way C2 share: 527 units per group over 128 workgroups = 4.1 rounds, the fifth
-    // run by 15 of them; over 106 workgroups, 5 rounds). Measured no faster on 8-way C2 shares
-    // (ranks 1 / 3 / 7: 0.190 / 0.203 / 0.199 against 0.185 / 0.193 / 0.196 ms, profiles/r6): off
-    // unless MMRE_SWEEP_BALANCE=1 (A/B).
-    static const char* bal_env = getenv("MMRE_SWEEP_BALANCE");
-    if (dyn && g % 8 == 0 && n_et >= 8 && bal_env && bal_env[0] == '1') {
-      const int64_t per_group = (q_tiles * n_et + 7) / 8;  // UnitMap: every group within +-1 of this
-      const int64_t slots = g / 8;
-      const int64_t rounds = (per_group + slots - 1) / slots;
-      if (rounds <= 16) g = 8 * (int)((per_group + rounds - 1) / rounds);
-    }
+  const int64_t units = sweep_units(q_tiles, C.n_et);
+  if (units < g) g = (int)(units > 0 ? units : 1);
+  // Dynamic scheduling of a small share: as many workgroups per XCD group as make its units an
+  // (almost) whole number of rounds -- the same rounds as the full grid, no nearly empty last
+  // round (an 8-way C2 share: 527 units per group over 128 workgroups = 4.1 rounds, the fifth
+  // run by 15 of them; over 106 workgroups, 5 rounds). Measured no faster on 8-way C2 shares
+  // (ranks 1 / 3 / 7: 0.190 / 0.203 / 0.199 against 0.185 / 0.193 / 0.196 ms, profiles/r6): off
+  // unless MMRE_SWEEP_BALANCE=1 (A/B).
+  static const char* bal_env = getenv("MMRE_SWEEP_BALANCE");
+  if (dyn && g % 8 == 0 && C.n_et >= 8 && bal_env && bal_env[0] == '1') {
+    const int64_t per_group = (q_tiles * C.n_et + 7) / 8;  // UnitMap: every group within +-1 of this
+    const int64_t slots = g / 8;
+    const int64_t rounds = (per_group + slots - 1) / slots;
+    if (rounds <= 16) g = 8 * (int)((per_group + rounds - 1) / rounds);
   }
-  // MMRE_SWEEP_GRID (experiments): "tiles" = one workgroup per (query tile, 1/8 of the
-  // entity tiles); a number = that many persistent workgroups.
-  static const char* gmode = getenv("MMRE_SWEEP_GRID");
-  if (gmode && gmode[0] == 't') g = 8 * (int)(q_pad / TQ);
-  else if (gmode && gmode[0] >= '1' && gmode[0] <= '9') g = atoi(gmode);
-  const int ng = (g % 8 == 0 && n_et >= 8) ? 8 : 1;
-  if (chunk == 4)
-    hipLaunchKernelGGL((k_sweep_valu<OP, TCV, STV, PK, DYN_OK ? 4 : 0>), dim3((unsigned)g), dim3(NT), 0, st, ent_km,
-                       e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base, ng, pk, m, thr, qtrue, qr, qmode, th, tt, tw,
-                       counts, scores, l1);
-  else if (chunk == 1)
-    hipLaunchKernelGGL((k_sweep_valu<OP, TCV, STV, PK, DYN_OK ? 1 : 0>), dim3((unsigned)g), dim3(NT), 0, st, ent_km,
-                       e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base, ng, pk, m, thr, qtrue, qr, qmode, th, tt, tw,
-                       counts, scores, l1);
-  else
-    hipLaunchKernelGGL((k_sweep_valu<OP, TCV, STV, PK>), dim3((unsigned)g), dim3(NT), 0, st, ent_km, e_pad, n_ent, q_km,
-                       q_pad, n_query, kp, n_et, e_base, ng, pk, m, thr, qtrue, qr, qmode, th, tt, tw, counts, scores, l1);
+  g = grid_override(g, 8 * (int)q_tiles);  // "tiles": one workgroup per (query tile, 1/8 of the entity tiles)
+  return {g, xcd_groups(g, C.n_et), chunk};
 }
 
+// The VALU sweep of operator OP (0 - 2 the f32 sweeps, 5 / 6 the integer filter's count-only ones,
+// the only ones with DYNC instances). The model's usual prediction kind is compiled into the
+// epilogue (PK = fast) of the plain sweep (C2 3.27 -> 3.23 ms) and of the integer filter's sweeps,
+// type masks or not (integer thresholds: prediction = the score); all else decodes it (PK = -1).
 template <int OP>
-static int launch_valu(bool tc, bool store, hipStream_t st, const float* ent_km, int64_t e_pad, int64_t n_ent,
-                       int n_et, int e_base, const float* q_km, int64_t q_pad, int64_t n_query, int kp, int pk, float m, const float* thr,
-                       const int32_t* qtrue, const int64_t* qr, const int8_t* qmode, const uint32_t* th,
-                       const uint32_t* tt, int64_t tw, int32_t* counts, float* scores, L1Q l1 = {},
-                       bool finalize = true) {
-#define MMRE_LV1(TCV, STV, PKV) \
-  launch_valu_one<OP, TCV, STV, PKV>(st, ent_km, e_pad, n_ent, n_et, e_base, q_km, q_pad, n_query, kp, pk, m, thr, qtrue, qr, qmode, th, tt, tw, counts, scores, l1)
-  // the model's usual prediction kind is compiled into the epilogue of the plain sweep
+static int launch_valu(const SweepCall& C, const L1Q& l1 = {}, bool finalize = true) {
   constexpr int fast = (OP == 2) ? 3 : 0;  // RotatE -(m - s), TransE s
-  if constexpr (OP == 5 || OP == 6) {  // the integer filter: count-only sweeps
-    if (store) return MMRE_ERR_ARG;
-    if (tc && pk == fast) MMRE_LV1(true, false, fast);  // integer thresholds (prediction = the score)
-    else if (tc) MMRE_LV1(true, false, -1);
-    else if (pk == fast) MMRE_LV1(false, false, fast);
-    else MMRE_LV1(false, false, -1);
-  } else {
-    if (tc && store) MMRE_LV1(true, true, -1);
-    else if (tc) MMRE_LV1(true, false, -1);
-    else if (store) MMRE_LV1(false, true, -1);
-    else if (pk == fast) MMRE_LV1(false, false, fast);  // C2 3.27 -> 3.23 ms
-    else MMRE_LV1(false, false, -1);
-  }
-#undef MMRE_LV1
+  constexpr bool COUNT_ONLY = OP == 5 || OP == 6;
+  if (COUNT_ONLY && C.store()) return MMRE_ERR_ARG;
+  const bool fast_pk = C.pred_kind == fast && (COUNT_ONLY || (!C.tc() && !C.store()));
+  with_bools(C.tc(), C.store(), fast_pk, [&](auto tc_, auto st_, auto fast_) {
+    constexpr bool TC = decltype(tc_)::value, ST = decltype(st_)::value;
+    constexpr int PK = decltype(fast_)::value ? fast : -1;
+    if constexpr (!(COUNT_ONLY && ST) && !(PK == fast && !COUNT_ONLY && (TC || ST))) {  // the instances there are
+      const void* k_dyn = COUNT_ONLY ? (const void*)k_sweep_valu<OP, TC, ST, PK, COUNT_ONLY ? 4 : 0> : nullptr;
+      const ValuGrid G = valu_grid(C, l1, (const void*)k_sweep_valu<OP, TC, ST, PK>, k_dyn);
+      with_chunk<COUNT_ONLY ? 4 + 1 : 0>(G.chunk, [&](auto dync_) {
+        hipLaunchKernelGGL((k_sweep_valu<OP, TC, ST, PK, decltype(dync_)::value>), dim3((unsigned)G.g), dim3(NT), 0,
+                           C.st, C.ent, C.e_pad, C.n_slice, C.q, C.q_pad, C.n_query, C.kp, C.n_et, C.e_base, G.ng,
+                           C.pred_kind, C.margin, C.truth, C.q_true, C.qr, C.qmode, C.type_head, C.type_tail, C.tw,
+                           C.counts, C.scores, l1);
+      });
+    }
+    return MMRE_OK;
+  });
   MMRE_CHECK_LAUNCH();
-  return finalize ? launch_finalize(st, counts, n_query, tc) : MMRE_OK;
+  return finalize ? launch_finalize(C.st, C.counts, C.n_query, C.tc()) : MMRE_OK;
 }
 
 // The grouped integer-filter sweep of the fused evaluation (k_sweep_valu<.., GS = L1Q_GS>): work
@@ -3541,36 +3638,74 @@ static int launch_valu(bool tc, bool store, hipStream_t st, const float* ent_km,
 // each, heavy tiles first), per evaluation: chunks of 1 / 2 / 4 units (MMRE_SWEEP_CHUNK) 0.705 /
 // 0.733 / 0.969 ms -- with so few units per workgroup a 4-unit claim is a third of its share, and
 // the last claims leave a long tail (the ungrouped sweep's ~30 units each favoured 4: see
-// sweep_valu_body). The host picks 1 below 16 units per workgroup, as launch_valu_one does.
+// sweep_valu_body). The host picks 1 below 16 units per workgroup, as valu_grid does.
 template <int OP>
-static int launch_valu_grp(hipStream_t st, const float* ent_km, int64_t e_pad, int64_t n_ent, int n_et, int e_base,
-                           const float* q_km, int64_t q_pad, int64_t n_query, int kp, const float* thr,
-                           const int32_t* qtrue, int32_t* counts, L1Q l1, int64_t rows_max) {
-  const bool dyn = l1.wq != nullptr && kp / KC >= 2;
+static int launch_valu_grp(const SweepCall& C, L1Q l1, int64_t rows_max) {
+  const bool dyn = l1.wq != nullptr && C.kp / KC >= 2;
   if (!dyn) l1.wq = nullptr;
   int g = resident_groups((const void*)k_sweep_valu<OP, false, false, 0, 1, L1Q_GS>, NT);
-  if (!dyn) g *= 16;  // static ranges: short ones (launch_valu_one)
+  if (!dyn) g *= 16;  // static ranges: short ones (valu_grid)
   const int64_t q_tiles = (rows_max + TQ - 1) / TQ;
-  const int64_t units = (n_et >= 8) ? 8 * q_tiles * ((n_et + 7) / 8) : q_tiles * n_et;
+  const int64_t units = sweep_units(q_tiles, C.n_et);
   if (units < g) g = (int)(units > 0 ? units : 1);
-  int chunk = 0;
-  if (dyn) {
-    static const char* ch_env = getenv("MMRE_SWEEP_CHUNK");  /* A/B: 1, 2 or 4 units per claim */
-    const int64_t per_wg = q_tiles * n_et / (g > 0 ? g : 1);
-    chunk = ch_env ? (atoi(ch_env) >= 4 ? 4 : atoi(ch_env) >= 2 ? 2 : 1) : (per_wg >= 16 ? 4 : 1);
-  }
-  const int ng = (g % 8 == 0 && n_et >= 8) ? 8 : 1;
-#define MMRE_LVG(DYNCV)                                                                                             \
-  hipLaunchKernelGGL((k_sweep_valu<OP, false, false, 0, DYNCV, L1Q_GS>), dim3((unsigned)g), dim3(NT), 0, st, ent_km,  \
-                     e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base, ng, 0, 0.0f, thr, qtrue, nullptr, nullptr, \
-                     nullptr, nullptr, (int64_t)0, counts, nullptr, l1)
-  if (chunk == 4) MMRE_LVG(4);
-  else if (chunk == 2) MMRE_LVG(2);
-  else if (chunk == 1) MMRE_LVG(1);
-  else MMRE_LVG(0);
-#undef MMRE_LVG
+  const int chunk = dyn ? sweep_chunk(q_tiles * C.n_et / (g > 0 ? g : 1), true) : 0;
+  const int ng = xcd_groups(g, C.n_et);
+  with_chunk<4 + 2 + 1>(chunk, [&](auto dync_) {
+    hipLaunchKernelGGL((k_sweep_valu<OP, false, false, 0, decltype(dync_)::value, L1Q_GS>), dim3((unsigned)g), dim3(NT),
+                       0, C.st, C.ent, C.e_pad, C.n_slice, C.q, C.q_pad, C.n_query, C.kp, C.n_et, C.e_base, ng, 0, 0.0f,
+                       C.truth, C.q_true, nullptr, nullptr, nullptr, nullptr, (int64_t)0, C.counts, nullptr, l1);
+  });
   MMRE_CHECK_LAUNCH();
   return MMRE_OK;
+}
+
+// 16 units per workgroup, between lo = 1 (2 with 32-row stages) and 8 x the resident slots: short
+// ranges let the dispatcher balance CUs of different speed (C5 1,024 / 4,096 groups: 35.1 / 34.3
+// ms) while the few-unit C3 keeps ranges long enough to amortise each group's first stage (16-row
+// stages at 4 / CU, C3: 1,024 groups 0.97 ms, 2,048 1.04, 4,096 1.02). Gated (the bf3 fallback):
+// one residency round when shut.
+static int mfma_grid(int res, bool ks32, bool gated, int64_t units) {
+  const int64_t lo = ks32 ? 2LL * res : (int64_t)res;
+  int g = (int)std::min<int64_t>(8LL * res, std::max<int64_t>(lo, units / 16)) & ~7;
+  if (gated) g = (int)lo & ~7;
+  return grid_override(g);
+}
+
+// The f32 MFMA sweep's launch (DistMult / ComplEx; C.kp = ktot). gate != NULL: every workgroup
+// returns at once unless *gate != 0 (the split-bf16 filter's overflow fallback).
+static int launch_mfma(const SweepCall& C, const uint32_t* gate, bool finalize) {
+  // persistent XCD-grouped grid as for the VALU sweep, 2 workgroups per resident slot (MI355X,
+  // KCM = 16: C3 1.20 / 1.24 / 1.22 / 1.24 ms and C5 36.5 / 36.5 / 36.5 / 36.6 ms at 1/2/3/4x)
+  // K stages of 32 rows (a unit's last one 16 when K = 32 n + 16: C3 ComplEx 2 x 200): half the
+  // per-stage staging and barriers per MFMA of 16-row stages (scripts/probes/mfma_stage.hip:
+  // 0.79 -> 0.86 of the f32 MFMA peak, L2-resident or HBM-streamed alike)
+  // The plain sweep (no type constraint, no score store) runs 16-row stages at 4 workgroups
+  // per CU (33 KB of LDS, 112 VGPRs with the ballot row counters): C3 1.03 -> 0.97 ms, C5
+  // 33.7 -> 33.0 ms against 32-row stages at 2 per CU; the TC / STORE variants keep 32-row
+  // stages (their extra registers would spill at 4 per CU).
+  static const char* ks_env = getenv("MMRE_MFMA_STAGE");  // experiments: 16 / 32 force the stage
+  const int ks_force = ks_env ? atoi(ks_env) : 0;
+  const bool ks32 = ks_force == 32 || (ks_force != 16 && (C.tc() || C.store()));
+  const int emajor = mfma_emajor(C.e_pad, C.kp);
+  // DistMult / ComplEx predict -s: compiled into the plain sweep's epilogue (one compare with a
+  // negated operand per pair); other kinds and the TC / STORE variants decode it at run time
+  const bool fast_pk = C.pred_kind == 2 && !C.tc() && !C.store();
+  with_bools(C.tc(), C.store(), fast_pk, [&](auto tc_, auto st_, auto fast_) {
+    return with_bool(ks32, [&](auto ks32_) {
+      constexpr bool TC = decltype(tc_)::value, ST = decltype(st_)::value, FAST = decltype(fast_)::value;
+      if constexpr (!(FAST && (TC || ST))) {  // the instances there are
+        auto kernel = k_sweep_mfma<TC, ST, FAST ? 2 : -1, decltype(ks32_)::value ? 32 : 16>;
+        const int g = mfma_grid(resident_groups((const void*)kernel, NT), ks32, gate != nullptr,
+                                C.q_tiles() * (int64_t)C.n_et);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)g), dim3(NT), 0, C.st, C.ent, C.e_pad, C.n_slice, C.q, C.q_pad,
+                           C.n_query, C.kp, C.n_et, C.e_base, xcd_groups(g, C.n_et), C.pred_kind, C.margin, C.truth,
+                           C.qr, C.qmode, C.type_head, C.type_tail, C.tw, C.counts, C.scores, emajor, gate);
+      }
+      return MMRE_OK;
+    });
+  });
+  MMRE_CHECK_LAUNCH();
+  return finalize ? launch_finalize(C.st, C.counts, C.n_query, C.tc()) : MMRE_OK;
 }
 
 // ------------------------------------------ fused TransE L1 evaluation (round 5) ---
@@ -4251,7 +4386,15 @@ using namespace mmre;
 extern "C" int64_t mmre_link_k(int model, int dim) { return (int64_t)n_planes(model) * plane_rows(model, dim); }
 extern "C" int64_t mmre_link_pad(int64_t n) { return round_up(n > 0 ? n : 1, 128); }
 
-static bool valid_model(int m) { return m >= MMRE_TRANSE_L1 && m <= MMRE_ROTATE; }
+struct Carver {  // carves consecutive regions out of a workspace; a NULL base only adds the sizes up
+  char* base;
+  int64_t off = 0;
+  template <class T>
+  T* take(int64_t bytes) {
+    off += bytes;
+    return base ? reinterpret_cast<T*>(base + off - bytes) : nullptr;
+  }
+};
 
 extern "C" int mmre_link_prepare_entities(int model, int norm_flag, const float* d_ent, const float* d_ent_im,
                                           int64_t n_ent, int dim, float* d_ent_km, int64_t e_pad, float* d_ent_rows,
@@ -4298,46 +4441,6 @@ extern "C" int mmre_link_prepare_queries(int model, int norm_flag, const float* 
   return MMRE_OK;
 }
 
-template <int OP>
-static int launch_truth_filter(hipStream_t st, const float* ent_rows, int64_t n_ent, const float* q_km, int64_t q_pad,
-                               int kp, const float* q_rows, const int32_t* qtrue, const int64_t* qr, const int8_t* qmode, int64_t n_query,
-                               int pk, float m, const int64_t* grp_qoff, const int32_t* grp_q, int64_t n_groups,
-                               const int64_t* off, const int32_t* ids, const uint32_t* th, const uint32_t* tt,
-                               int64_t tw, float* thr, int32_t* counts) {
-  constexpr int NP = (OP == 2 || OP == 4) ? 2 : 1;
-  const size_t lds = sizeof(float) * (size_t)NP * kp;
-  if (lds > 64 * 1024) return MMRE_ERR_SHAPE;
-  const unsigned blocks = (unsigned)(n_groups < (1 << 20) ? n_groups : (1 << 20));
-  hipLaunchKernelGGL((k_truth_filter<OP>), dim3(blocks), dim3(FT), lds, st, ent_rows, n_ent, q_km, q_pad, kp, q_rows,
-                     qtrue, qr, qmode, n_query, pk, m, grp_qoff, grp_q, n_groups, off, ids, th, tt, tw, thr, counts);
-  MMRE_CHECK_LAUNCH();
-  return MMRE_OK;
-}
-
-static int check_link_args(int model, int pred_kind, const float* d_ent_km, int64_t n_ent, int64_t e_pad,
-                           const float* d_q_km, const int32_t* d_q_true, const int64_t* d_qr, const int8_t* d_qmode,
-                           int64_t n_query, int64_t q_pad, const uint32_t* d_type_head, const uint32_t* d_type_tail,
-                           const int32_t* d_counts, const float* d_truth) {
-  if (!valid_model(model)) return MMRE_ERR_MODEL;
-  if (pred_kind < 0 || pred_kind > 4) return MMRE_ERR_ARG;
-  if (!d_ent_km || !d_q_km || !d_q_true || !d_counts || !d_truth || !d_qmode || !d_qr) return MMRE_ERR_ARG;
-  if (n_query <= 0 || n_ent <= 0 || e_pad < n_ent || e_pad % TE || q_pad < n_query || q_pad % TQ) return MMRE_ERR_ARG;
-  if ((d_type_head == nullptr) != (d_type_tail == nullptr)) return MMRE_ERR_ARG;
-  if (n_ent > (int64_t)INT32_MAX - 256) return MMRE_ERR_SHAPE;  // padded ids stay int32
-  return MMRE_OK;
-}
-
-template <int OP>
-static int launch_filter_scores(hipStream_t st, const float* ent_rows, int64_t n_ent, const float* q_rows, int kp,
-                                const int32_t* qtrue, int64_t n_query, int pk, float m, const int32_t* entry_q,
-                                const int32_t* ids, int64_t n_entries, float* thr, float* list_v) {
-  const int64_t tasks = n_query + n_entries;
-  hipLaunchKernelGGL((k_filter_scores<OP>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st, ent_rows, n_ent,
-                     q_rows, kp, qtrue, n_query, pk, m, entry_q, ids, n_entries, thr, list_v);
-  MMRE_CHECK_LAUNCH();
-  return MMRE_OK;
-}
-
 extern "C" int mmre_link_truth_grouped(int model, int pred_kind, float margin, const float* d_ent_rows, int64_t n_ent,
                                        const float* d_q_rows, const int32_t* d_q_true, const int64_t* d_qr,
                                        const int8_t* d_qmode, int64_t n_query, int dim, const int64_t* d_grp_qoff,
@@ -4356,19 +4459,14 @@ extern "C" int mmre_link_truth_grouped(int model, int pred_kind, float margin, c
   if (n_ent >= (int64_t)INT32_MAX || n_query >= (int64_t)INT32_MAX) return MMRE_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int kp = plane_rows(model, dim);
-  int rc;
-#define MMRE_FS(OPV)                                                                                              \
-  launch_filter_scores<OPV>(st, d_ent_rows, n_ent, d_q_rows, kp, d_q_true, n_query, pred_kind, margin, d_entry_q, \
-                            d_filt_ids, n_entries, d_truth, d_list_scores)
-  switch (op_of_model(model)) {
-    case 0: rc = MMRE_FS(0); break;
-    case 1: rc = MMRE_FS(1); break;
-    case 2: rc = MMRE_FS(2); break;
-    case 3: rc = MMRE_FS(3); break;
-    default: rc = MMRE_FS(4); break;
-  }
-#undef MMRE_FS
-  if (rc) return rc;
+  const int64_t tasks = n_query + n_entries;  // k_filter_scores: a thread per truth and per list entry
+  with_op(op_of_model(model), [&](auto op_) {
+    hipLaunchKernelGGL((k_filter_scores<decltype(op_)::value>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st,
+                       d_ent_rows, n_ent, d_q_rows, kp, d_q_true, n_query, pred_kind, margin, d_entry_q, d_filt_ids,
+                       n_entries, d_truth, d_list_scores);
+    return MMRE_OK;
+  });
+  MMRE_CHECK_LAUNCH();
   const unsigned blocks = (unsigned)(n_groups < (1 << 20) ? n_groups : (1 << 20));
   hipLaunchKernelGGL(k_filter_count, dim3(blocks), dim3(64), 0, st, d_grp_qoff, d_grp_q, n_groups, d_filt_off,
                      d_filt_ids, d_list_scores, d_q_true, d_truth, d_qr, d_qmode, n_query, n_ent, d_type_head,
@@ -4382,124 +4480,39 @@ extern "C" int mmre_link_truth(int model, int pred_kind, float margin, const flo
                                const int64_t* d_qr, const int8_t* d_qmode, int64_t n_query, int64_t q_pad, int dim,
                                const int64_t* d_filt_off, const int32_t* d_filt_ids, const uint32_t* d_type_head,
                                const uint32_t* d_type_tail, int32_t* d_counts, float* d_truth, void* stream) {
-  int rc = check_link_args(model, pred_kind, d_ent_km, n_ent, e_pad, d_q_km, d_q_true, d_qr, d_qmode, n_query, q_pad,
-                           d_type_head, d_type_tail, d_counts, d_truth);
+  const SweepCall C{nullptr, d_ent_km, e_pad, d_q_km, q_pad, n_query, pred_kind, margin, d_truth, d_q_true, d_qr,
+                    d_qmode, d_type_head, d_type_tail, d_counts};
+  int rc = check_link_args(model, C, n_ent);
   if (rc) return rc;
   if (!d_ent_rows) return MMRE_ERR_ARG;
   if ((d_filt_off == nullptr) != (d_filt_ids == nullptr)) return MMRE_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
   const int kp = plane_rows(model, dim);
-  const int64_t tw = (n_ent + 31) / 32;
-#define MMRE_TF(OPV)                                                                                              \
-  launch_truth_filter<OPV>(st, d_ent_rows, n_ent, d_q_km, q_pad, kp, nullptr, d_q_true, d_qr, d_qmode, n_query,   \
-                           pred_kind, margin, nullptr, nullptr, n_query, d_filt_off, d_filt_ids, d_type_head,      \
-                           d_type_tail, tw, d_truth, d_counts)
-  switch (op_of_model(model)) {
-    case 0: return MMRE_TF(0);
-    case 1: return MMRE_TF(1);
-    case 2: return MMRE_TF(2);
-    case 3: return MMRE_TF(3);
-    default: return MMRE_TF(4);
-  }
-#undef MMRE_TF
-}
-
-// The f32 MFMA sweep's launch (DistMult / ComplEx; d_ent_km already at the slice's first
-// column). gate != NULL: every workgroup returns at once unless *gate != 0 (the split-bf16
-// filter's overflow fallback, mmre_link_sweep_bf3).
-static void launch_mfma(bool tc, bool store, int pred_kind, float margin, const float* d_ent_km, int64_t n_ent,
-                        int64_t e_pad, int n_et, int e_base, const float* d_q_km, int64_t q_pad, int64_t n_query,
-                        int ktot, const float* d_truth, const int64_t* d_qr, const int8_t* d_qmode,
-                        const uint32_t* d_type_head, const uint32_t* d_type_tail, int64_t tw, int32_t* d_counts,
-                        float* d_scores, hipStream_t st, const uint32_t* gate) {
-  // persistent XCD-grouped grid as for the VALU sweep, 2 workgroups per resident slot (MI355X,
-  // KCM = 16: C3 1.20 / 1.24 / 1.22 / 1.24 ms and C5 36.5 / 36.5 / 36.5 / 36.6 ms at 1/2/3/4x)
-  // K stages of 32 rows (a unit's last one 16 when K = 32 n + 16: C3 ComplEx 2 x 200): half the
-  // per-stage staging and barriers per MFMA of 16-row stages (scripts/probes/mfma_stage.hip:
-  // 0.79 -> 0.86 of the f32 MFMA peak, L2-resident or HBM-streamed alike)
-  // The plain sweep (no type constraint, no score store) runs 16-row stages at 4 workgroups
-  // per CU (33 KB of LDS, 112 VGPRs with the ballot row counters): C3 1.03 -> 0.97 ms, C5
-  // 33.7 -> 33.0 ms against 32-row stages at 2 per CU; the TC / STORE variants keep 32-row
-  // stages (their extra registers would spill at 4 per CU).
-  static const char* ks_env = getenv("MMRE_MFMA_STAGE"); /* experiments: 16 / 32 force the stage */
-  const int ks_force = ks_env ? atoi(ks_env) : 0;
-  const bool ks32 = ks_force == 32 || (ks_force != 16 && (tc || store));
-  static const char* grid_env = getenv("MMRE_SWEEP_GRID"); /* experiments: workgroup count */
-  // Units entity-tile-major inside each XCD group when the entity planes outgrow the caches
-  // (> 64 MB; the 256 MB MALL also holds the query planes): a workgroup's consecutive units then
-  // share its entity tile (L2-resident) and sweep the query tiles, which stay MALL-resident, so
-  // the table streams from HBM about once instead of once per query tile (C5, a 1 GB table:
-  // 35.8 -> 34.5 ms on one box, 60 -> ~1 GB of entity reads per launch); C3's 20 MB planes keep
-  // the query-major order (0.979 vs 0.982 ms).
-  static const char* order_env = getenv("MMRE_MFMA_EMAJOR"); /* experiments: 0 / 1 force the order */
-  const int emajor = order_env ? atoi(order_env) : ((double)e_pad * ktot * 4.0 > 64.0 * (1 << 20) ? 1 : 0);
-#define MMRE_MFMA_K(KERNEL)                                                                                       \
-  do {                                                                                                            \
-    /* 16 units per workgroup, between 1 (2 with 32-row stages) and 8 x the resident slots:    */                \
-    /* short ranges let the dispatcher balance CUs of different speed (C5 1,024 / 4,096 groups:  */                \
-    /* 35.1 / 34.3 ms) while the few-unit C3 keeps ranges long enough to amortise each group's   */                \
-    /* first stage (16-row stages at 4 / CU, C3: 1,024 groups 0.97 ms, 2,048 1.04, 4,096 1.02)   */                \
-    const int res = resident_groups((const void*)KERNEL, NT);                                                     \
-    const int64_t units = (q_pad / TQ) * (int64_t)n_et;                                                           \
-    const int64_t lo = ks32 ? 2LL * res : (int64_t)res;                                                           \
-    int g = (int)std::min<int64_t>(8LL * res, std::max<int64_t>(lo, units / 16)) & ~7;                            \
-    if (gate != nullptr) g = (int)lo & ~7; /* gated (the bf3 fallback): one residency round when shut */          \
-    if (grid_env && grid_env[0] >= '1' && grid_env[0] <= '9') g = atoi(grid_env);                              \
-    const int ng = (g % 8 == 0 && n_et >= 8) ? 8 : 1;                                                             \
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)g), dim3(NT), 0, st, d_ent_km, e_pad, n_ent, d_q_km, q_pad,       \
-                       n_query, ktot, n_et, e_base, ng, pred_kind, margin, d_truth, d_qr, d_qmode, d_type_head,  \
-                       d_type_tail, tw, d_counts, d_scores, emajor, gate);                                              \
-  } while (0)
-#define MMRE_MFMA(TCV, STV, PKV)                                                                           \
-  do {                                                                                                 \
-    if (ks32) MMRE_MFMA_K((k_sweep_mfma<TCV, STV, PKV, 32>));                                          \
-    else MMRE_MFMA_K((k_sweep_mfma<TCV, STV, PKV, 16>));                                               \
-  } while (0)
-  // DistMult / ComplEx predict -s: compiled into the plain sweep's epilogue (one compare with a
-  // negated operand per pair); other kinds and the TC / STORE variants decode it at run time
-  if (tc) { if (store) MMRE_MFMA(true, true, -1); else MMRE_MFMA(true, false, -1); }
-  else if (store) MMRE_MFMA(false, true, -1);
-  else if (pred_kind == 2) MMRE_MFMA(false, false, 2);
-  else MMRE_MFMA(false, false, -1);
-#undef MMRE_MFMA
-#undef MMRE_MFMA_K
-}
-
-// The sweep over entities [e_begin, e_end) of the table (e_begin a multiple of TE): the kernels
-// see the slice (pointer offset by e_begin columns, row stride e_pad, n_ent_local ids) and add
-// e_begin back wherever an absolute id matters (truth exclusion, type-constraint bits).
-static int sweep_impl(int model, int pred_kind, float margin, const float* d_ent_km, int64_t n_ent, int64_t e_pad,
-                      int64_t e_begin, int64_t e_end, const float* d_q_km, const int32_t* d_q_true,
-                      const int64_t* d_qr, const int8_t* d_qmode, int64_t n_query, int64_t q_pad, int dim,
-                      const uint32_t* d_type_head, const uint32_t* d_type_tail, int32_t* d_counts,
-                      const float* d_truth, float* d_scores, hipStream_t st) {
-  int rc = check_link_args(model, pred_kind, d_ent_km, n_ent, e_pad, d_q_km, d_q_true, d_qr, d_qmode, n_query, q_pad,
-                           d_type_head, d_type_tail, d_counts, d_truth);
+  rc = with_op(op_of_model(model), [&](auto op_) -> int {
+    constexpr int OP = decltype(op_)::value, NP = (OP == 2 || OP == 4) ? 2 : 1;
+    const size_t lds = sizeof(float) * (size_t)NP * kp;
+    if (lds > 64 * 1024) return MMRE_ERR_SHAPE;
+    const unsigned blocks = (unsigned)(n_query < (1 << 20) ? n_query : (1 << 20));
+    hipLaunchKernelGGL((k_truth_filter<OP>), dim3(blocks), dim3(FT), lds, (hipStream_t)stream, d_ent_rows, n_ent,
+                       d_q_km, q_pad, kp, nullptr, d_q_true, d_qr, d_qmode, n_query, pred_kind, margin, nullptr, nullptr,
+                       n_query, d_filt_off, d_filt_ids, d_type_head, d_type_tail, (n_ent + 31) / 32, d_truth, d_counts);
+    return MMRE_OK;
+  });
   if (rc) return rc;
-  if (e_begin < 0 || e_begin % TE || e_end <= e_begin || e_end > n_ent) return MMRE_ERR_ARG;
-  if (d_scores && (e_begin != 0 || e_end != n_ent)) return MMRE_ERR_ARG;  // score rows are whole-table
-  const int64_t tw = (n_ent + 31) / 32;  // type bitsets span the whole table
-  const int e_base = (int)e_begin;
-  d_ent_km += e_begin;
-  n_ent = e_end - e_begin;
-  const int n_et = (int)((n_ent + TE - 1) / TE);
-  const int kp = plane_rows(model, dim);
-  const bool tc = d_type_head != nullptr;
-  const bool store = d_scores != nullptr;
-  const int op = op_of_model(model);
-  if (op <= 2) {
-#define MMRE_LV(OPV) launch_valu<OPV>(tc, store, st, d_ent_km, e_pad, n_ent, n_et, e_base, d_q_km, q_pad, n_query, kp, pred_kind, \
-                                      margin, d_truth, d_q_true, d_qr, d_qmode, d_type_head, d_type_tail, tw, d_counts, d_scores)
-    if (op == 0) return MMRE_LV(0);
-    if (op == 1) return MMRE_LV(1);
-    return MMRE_LV(2);
-#undef MMRE_LV
-  }
-  const int ktot = n_planes(model) * kp;
-  launch_mfma(tc, store, pred_kind, margin, d_ent_km, n_ent, e_pad, n_et, e_base, d_q_km, q_pad, n_query, ktot,
-              d_truth, d_qr, d_qmode, d_type_head, d_type_tail, tw, d_counts, d_scores, st, nullptr);
   MMRE_CHECK_LAUNCH();
-  return launch_finalize(st, d_counts, n_query, tc);
+  return MMRE_OK;
+}
+
+// mmre_link_sweep / mmre_link_sweep_range: the exact sweep of the model's own planes.
+static int sweep_impl(int model, SweepCall C, int64_t n_ent, int64_t e_begin, int64_t e_end, int dim) {
+  if (int rc = check_link_args(model, C, n_ent); rc) return rc;
+  const int k = mfma_model(model) ? (int)mmre_link_k(model, dim) : plane_rows(model, dim);
+  if (int rc = sweep_slice(C, n_ent, e_begin, e_end, k); rc) return rc;
+  if (C.scores && (e_begin != 0 || e_end != n_ent)) return MMRE_ERR_ARG;  // score rows are whole-table
+  return with_op(op_of_model(model), [&](auto op_) -> int {
+    constexpr int OP = decltype(op_)::value;
+    if constexpr (OP <= 2) return launch_valu<OP>(C);
+    else return launch_mfma(C, nullptr, true);
+  });
 }
 
 extern "C" int mmre_link_sweep(int model, int pred_kind, float margin, const float* d_ent_km, int64_t n_ent,
@@ -4508,13 +4521,47 @@ extern "C" int mmre_link_sweep(int model, int pred_kind, float margin, const flo
                                const uint32_t* d_type_head, const uint32_t* d_type_tail, int32_t* d_counts,
                                const float* d_truth, float* d_scores, void* stream) {
   if (n_ent <= 0) return MMRE_ERR_ARG;
-  return sweep_impl(model, pred_kind, margin, d_ent_km, n_ent, e_pad, 0, n_ent, d_q_km, d_q_true, d_qr, d_qmode,
-                    n_query, q_pad, dim, d_type_head, d_type_tail, d_counts, d_truth, d_scores, (hipStream_t)stream);
+  return sweep_impl(model, {(hipStream_t)stream, d_ent_km, e_pad, d_q_km, q_pad, n_query, pred_kind, margin, d_truth,
+                            d_q_true, d_qr, d_qmode, d_type_head, d_type_tail, d_counts, d_scores}, n_ent, 0, n_ent,
+                    dim);
+}
+
+extern "C" int mmre_link_sweep_range(int model, int pred_kind, float margin, const float* d_ent_km, int64_t n_ent,
+                                     int64_t e_pad, int64_t e_begin, int64_t e_end, const float* d_q_km,
+                                     const int32_t* d_q_true, const int64_t* d_qr, const int8_t* d_qmode,
+                                     int64_t n_query, int64_t q_pad, int dim, const uint32_t* d_type_head,
+                                     const uint32_t* d_type_tail, int32_t* d_counts, const float* d_truth,
+                                     void* stream) {
+  return sweep_impl(model, {(hipStream_t)stream, d_ent_km, e_pad, d_q_km, q_pad, n_query, pred_kind, margin, d_truth,
+                            d_q_true, d_qr, d_qmode, d_type_head, d_type_tail, d_counts, nullptr}, n_ent, e_begin,
+                    e_end, dim);
+}
+
+// ------------------------------------------------ the TransE L1 integer filter ---
+// The L1Q workspace: header | 16-bit code planes, queries then entities (k2 rows of q_pad / e_pad
+// words) | 8-bit code planes (k4 rows) | the tight bound's error sums (q_pad floats).
+struct L1QWork {
+  int k2, k4;
+  uint32_t *hdr, *uq, *ue, *vq, *ve;
+  float* q_l1c;
+};
+static int64_t l1q_layout(L1QWork& W, int dim, int64_t e_pad, int64_t q_pad, void* base) {
+  Carver w{(char*)base};
+  W.k2 = l1q_rows(dim);
+  W.k4 = l1q_rows8(dim);
+  W.hdr = w.take<uint32_t>(L1Q_HDR);
+  W.uq = w.take<uint32_t>(4 * (int64_t)W.k2 * q_pad);
+  W.ue = w.take<uint32_t>(4 * (int64_t)W.k2 * e_pad);
+  W.vq = w.take<uint32_t>(4 * (int64_t)W.k4 * q_pad);
+  W.ve = w.take<uint32_t>(4 * (int64_t)W.k4 * e_pad);
+  W.q_l1c = w.take<float>(4 * q_pad);
+  return w.off;
 }
 
 extern "C" int64_t mmre_link_l1q_workspace(int dim, int64_t e_pad, int64_t q_pad) {
   if (dim <= 0 || e_pad <= 0 || q_pad <= 0) return 0;
-  return L1Q_HDR + 4 * (int64_t)(l1q_rows(dim) + l1q_rows8(dim)) * (e_pad + q_pad) + 4 * q_pad;
+  L1QWork W;
+  return l1q_layout(W, dim, e_pad, q_pad, nullptr);
 }
 
 extern "C" int mmre_link_l1q_stats(const void* d_work, int64_t work_bytes, uint64_t* d_out, void* stream) {
@@ -4525,123 +4572,145 @@ extern "C" int mmre_link_l1q_stats(const void* d_work, int64_t work_bytes, uint6
   return MMRE_OK;
 }
 
+static float l1q_ratio() {  // fallback ratio M / mean|x| (MMRE_L1Q_RATIO: experiments; <= 0 forces the fallback)
+  static const char* env = getenv("MMRE_L1Q_RATIO");
+  return env ? (float)atof(env) : 128.0f;
+}
+// code width (MMRE_L1_BITS: experiments and tests, read per call): 8 / 16 forces it, otherwise the
+// 8-bit codes unless the probe finds their band too wide for this data
+static int l1q_bits() {
+  const char* env = getenv("MMRE_L1_BITS");
+  return env ? atoi(env) : 0;
+}
+// (C: the f32 call; TransE L1 has one plane, kt = kp)
+static L1Q l1q_operands(const L1QWork& W, const SweepCall& C, const float* q_rows, const float* ent_rows, bool tight,
+                        uint32_t* und_q) {
+  L1Q l1{q_rows, ent_rows, W.hdr, (unsigned long long*)((char*)W.hdr + 256), C.q, C.ent, C.kp,
+         C.kp, nullptr, tight ? W.q_l1c : nullptr, W.hdr + 4, und_q};
+  l1.wq = l1q_work_counters(W.hdr);
+  return l1;
+}
+
 extern "C" int mmre_link_sweep_l1q(int pred_kind, float margin, const float* d_ent_km, const float* d_ent_rows,
                                    int64_t n_ent, int64_t e_pad, int64_t e_begin, int64_t e_end, const float* d_q_km,
                                    const float* d_q_rows, const int32_t* d_q_true, const int64_t* d_qr,
                                    const int8_t* d_qmode, int64_t n_query, int64_t q_pad, int dim,
                                    const uint32_t* d_type_head, const uint32_t* d_type_tail, int32_t* d_counts,
                                    const float* d_truth, void* d_work, int64_t work_bytes, void* stream) {
-  int rc = check_link_args(MMRE_TRANSE_L1, pred_kind, d_ent_km, n_ent, e_pad, d_q_km, d_q_true, d_qr, d_qmode, n_query,
-                           q_pad, d_type_head, d_type_tail, d_counts, d_truth);
-  if (rc) return rc;
-  if (!d_ent_rows || !d_q_rows || !d_work || work_bytes < mmre_link_l1q_workspace(dim, e_pad, q_pad)) return MMRE_ERR_WORKSPACE;
-  if (e_begin < 0 || e_begin % TE || e_end <= e_begin || e_end > n_ent) return MMRE_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int kp = plane_rows(MMRE_TRANSE_L1, dim), k2 = l1q_rows(dim), k4 = l1q_rows8(dim);
-  uint32_t* hdr = (uint32_t*)d_work;
-  uint32_t* uq = (uint32_t*)((char*)d_work + L1Q_HDR);  // 16-bit planes
-  uint32_t* ue = uq + (int64_t)k2 * q_pad;
-  uint32_t* vq = ue + (int64_t)k2 * e_pad;              // 8-bit planes
-  uint32_t* ve = vq + (int64_t)k4 * q_pad;
-  float* q_l1c = (float*)(ve + (int64_t)k4 * e_pad);     // tight bound: per query row error sums
-  const int64_t e_cols = round_up(e_end, TE) - e_begin;  // the slice's whole tiles
-  // fallback ratio M / mean|x| (MMRE_L1Q_RATIO: experiments; <= 0 forces the fallback)
-  static const char* ratio_env = getenv("MMRE_L1Q_RATIO");
-  const float ratio = ratio_env ? (float)atof(ratio_env) : 128.0f;
+  SweepCall C{(hipStream_t)stream, d_ent_km, e_pad, d_q_km, q_pad, n_query, pred_kind, margin, d_truth,
+              d_q_true, d_qr, d_qmode, d_type_head, d_type_tail, d_counts};
+  if (int rc = check_link_args(MMRE_TRANSE_L1, C, n_ent); rc) return rc;
+  L1QWork W;
+  if (!d_ent_rows || !d_q_rows || !d_work || work_bytes < mmre_link_l1q_workspace(dim, e_pad, q_pad))
+    return MMRE_ERR_WORKSPACE;
+  l1q_layout(W, dim, e_pad, q_pad, d_work);
+  const int kp = plane_rows(MMRE_TRANSE_L1, dim), kt = n_planes(MMRE_TRANSE_L1) * kp;
+  if (int rc = sweep_slice(C, n_ent, e_begin, e_end, kp); rc) return rc;
+  hipStream_t st = C.st;
+  const float ratio = l1q_ratio();
   const int n_abs = std::min(kp * 8, L1Q_MAX_BLOCKS);
-  const double n_elem = (double)kp * (double)(q_pad + e_cols);
-  // code width (MMRE_L1_BITS: experiments and tests): 8 / 16 forces it, otherwise the 8-bit
-  // codes unless k_l1q_probe finds their band too wide for this data
-  const char* bits_env = getenv("MMRE_L1_BITS");
-  const int bits = bits_env ? atoi(bits_env) : 0;
-  const int64_t tw = (n_ent + 31) / 32;
-  const int64_t n_slice = e_end - e_begin;
-  const int n_et = (int)((n_slice + TE - 1) / TE);
-  hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(256), 0, st, hdr, L1Q_PART / 4);
-  hipLaunchKernelGGL(k_l1q_absmax, dim3((unsigned)n_abs), dim3(256), 0, st, d_q_km, q_pad, d_ent_km + e_begin, e_pad, e_cols,
-                     kp, hdr);
-  const L1QPlane p8q{d_q_km, q_pad, 0, q_pad, vq}, p8e{d_ent_km, e_pad, e_begin, e_cols, ve};
-  const L1QPlane p16q{d_q_km, q_pad, 0, q_pad, uq}, p16e{d_ent_km, e_pad, e_begin, e_cols, ue};
+  const double n_elem = (double)kp * (double)(q_pad + C.e_cols);
+  const int bits = l1q_bits();
+  hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(256), 0, st, W.hdr, L1Q_PART / 4);
+  hipLaunchKernelGGL(k_l1q_absmax, dim3((unsigned)n_abs), dim3(256), 0, st, d_q_km, q_pad, C.ent, e_pad, C.e_cols, kp,
+                     W.hdr);
+  const L1QPlane p8q{d_q_km, q_pad, 0, q_pad, W.vq}, p8e{d_ent_km, e_pad, e_begin, C.e_cols, W.ve};
+  const L1QPlane p16q{d_q_km, q_pad, 0, q_pad, W.uq}, p16e{d_ent_km, e_pad, e_begin, C.e_cols, W.ue};
   // the tight per-pair bound (k_l1q_quant8): prediction = the score, no type masks (their sweep
   // keeps the uniform bound), and error offsets that fit one code row (kt <= 1984);
-  // MMRE_L1_TIGHT=0 keeps the uniform bound (A/B)
+  // MMRE_L1_TIGHT=0 keeps the uniform bound (A/B; read per call: tests switch it)
   const char* tight_env = getenv("MMRE_L1_TIGHT");
-  const int kt = n_planes(MMRE_TRANSE_L1) * kp;
   const bool tight = pred_kind == 0 && d_type_head == nullptr && kt <= 1984 && !(tight_env && tight_env[0] == '0');
-  if (bits != 16) {
-    if (tight)
-      hipLaunchKernelGGL(k_l1q_quant8<true>, dim3(2048, 2), dim3(256), 0, st, p8q, p8e, kp, k4, kt, hdr, n_abs, n_elem,
-                         ratio, q_l1c);
-    else
-      hipLaunchKernelGGL(k_l1q_quant8<false>, dim3(2048, 2), dim3(256), 0, st, p8q, p8e, kp, k4, kt, hdr, n_abs, n_elem,
-                         ratio, q_l1c);
-  }
-  if (bits == 0) {
-    hipLaunchKernelGGL(k_l1q_probe, dim3(L1Q_PROBE_Q), dim3(L1Q_PROBE_E / 4), 0, st, vq, q_pad, n_query, ve + e_begin, e_pad,
-                       n_slice, k4, kt, d_truth, pred_kind, margin, hdr, tight ? q_l1c : nullptr);
-    const uint32_t probe_max = l1q_probe_max(n_slice);
-    hipLaunchKernelGGL(k_l1q_quant<16>, dim3(1024, 2), dim3(256), 0, st, p16q, p16e, kp, k2, hdr, n_abs, n_elem, ratio,
-                       1, probe_max);
-  } else if (bits == 16) {
-    hipLaunchKernelGGL(k_l1q_quant<16>, dim3(1024, 2), dim3(256), 0, st, p16q, p16e, kp, k2, hdr, n_abs, n_elem, ratio,
-                       0, 0u);
-  }
+  if (bits != 16)
+    with_bool(tight, [&](auto tight_) {
+      hipLaunchKernelGGL(k_l1q_quant8<decltype(tight_)::value>, dim3(2048, 2), dim3(256), 0, st, p8q, p8e, kp, W.k4, kt,
+                         W.hdr, n_abs, n_elem, ratio, W.q_l1c);
+      return MMRE_OK;
+    });
+  if (bits == 0)
+    hipLaunchKernelGGL(k_l1q_probe, dim3(L1Q_PROBE_Q), dim3(L1Q_PROBE_E / 4), 0, st, W.vq, q_pad, n_query,
+                       W.ve + e_begin, e_pad, C.n_slice, W.k4, kt, d_truth, pred_kind, margin, W.hdr,
+                       tight ? W.q_l1c : nullptr);
+  if (bits == 0 || bits == 16)  // after the probe: it decides whether these codes count
+    hipLaunchKernelGGL(k_l1q_quant<16>, dim3(1024, 2), dim3(256), 0, st, p16q, p16e, kp, W.k2, W.hdr, n_abs, n_elem,
+                       ratio, bits == 0 ? 1 : 0, bits == 0 ? l1q_probe_max(C.n_slice) : 0u);
   MMRE_CHECK_LAUNCH();
-  L1Q l1{d_q_rows, d_ent_rows, hdr, (unsigned long long*)((char*)d_work + 256), d_q_km, d_ent_km + e_begin, kp,
-         kt, nullptr, tight ? q_l1c : nullptr, hdr + 4};
-  l1.wq = l1q_work_counters(hdr);
-  const bool tc = d_type_head != nullptr;
+  const L1Q l1 = l1q_operands(W, C, d_q_rows, d_ent_rows, tight, nullptr);
   // the gated sweeps: the one the code-width word names counts, the others' workgroups leave
-  if (bits != 16) {
-    rc = launch_valu<6>(tc, false, st, (const float*)(ve + e_begin), e_pad, n_slice, n_et, (int)e_begin,
-                        (const float*)vq, q_pad, n_query, k4, pred_kind, margin, d_truth, d_q_true, d_qr, d_qmode,
-                        d_type_head, d_type_tail, tw, d_counts, nullptr, l1, false);
-    if (rc) return rc;
-  }
-  if (bits != 8) {
-    // after the 8-bit sweep the 16-bit one rarely counts: gated at its top (one flag load per
-    // workgroup, 4 workgroups per resident slot) like the f32 fallback below
-    L1Q l16 = l1;
-    if (bits == 0) l16.gate = hdr + 1;
-    rc = launch_valu<5>(tc, false, st, (const float*)(ue + e_begin), e_pad, n_slice, n_et, (int)e_begin,
-                        (const float*)uq, q_pad, n_query, k2, pred_kind, margin, d_truth, d_q_true, d_qr, d_qmode,
-                        d_type_head, d_type_tail, tw, d_counts, nullptr, l16, false);
-    if (rc) return rc;
-  }
+  int rc = bits != 16 ? launch_valu<6>(planes(C, W.ve, W.vq, W.k4), l1, false) : MMRE_OK;
+  if (rc) return rc;
+  // after the 8-bit sweep the 16-bit one rarely counts: gated at its top (one flag load per
+  // workgroup, 4 workgroups per resident slot) like the f32 fallback below
+  L1Q l16 = l1;
+  if (bits == 0) l16.gate = W.hdr + 1;
+  if (bits != 8 && (rc = launch_valu<5>(planes(C, W.ue, W.uq, W.k2), l16, false))) return rc;
   // the fallback: the exact f32 sweep of the float planes, gated on the flag k_l1q_quant wrote
   // (its workgroups return at once when the codes were used)
   L1Q gate{};
-  gate.gate = hdr + 1;
-  return launch_valu<0>(tc, false, st, d_ent_km + e_begin, e_pad, n_slice, n_et, (int)e_begin, d_q_km, q_pad, n_query,
-                        kp, pred_kind, margin, d_truth, d_q_true, d_qr, d_qmode, d_type_head, d_type_tail, tw,
-                        d_counts, nullptr, gate, true);
+  gate.gate = W.hdr + 1;
+  return launch_valu<0>(C, gate, true);
 }
 
+// ------------------------------------------------------ split-bf16 MFMA filter ---
 // The lock-step window QB x EB for P workgroups per XCD group (BlockMap): about 8 query tiles
 // (MMRE_BF3_QB) by P / QB entity tiles, evened out so the last window along each axis is not
 // mostly empty (C5: P 96, 64 query tiles, 976 entity tiles per group -> 8 x 12; C3: 89 x 12-13
 // -> 7 x 13).
-static void bf3_window(int P, int n_qt, int m_e, int& qb, int& eb) {
+static void bf3_window(int P, int n_qt, int m_e, int& q, int& e) {
   static const char* qb_env = getenv("MMRE_BF3_QB");
-  int q = qb_env ? atoi(qb_env) : 8;
-  q = std::max(1, std::min(q, std::min(P, n_qt)));
-  int e = std::max(1, std::min(P / q, m_e));
+  q = std::max(1, std::min(qb_env ? atoi(qb_env) : 8, std::min(P, n_qt)));
+  e = std::max(1, std::min(P / q, m_e));
   const int ne = (m_e + e - 1) / e;      // windows along the entity tiles, then even them out
   e = (m_e + ne - 1) / ne;
   q = std::max(1, std::min(P / e, n_qt));
   const int nq = (n_qt + q - 1) / q;
   q = (n_qt + nq - 1) / nq;
-  qb = q;
-  eb = e;
+}
+
+// The grid of k_sweep_bf3 / k_sweep_bf3w over q_tiles x n_tiles units: g_ranges workgroups with
+// contiguous unit ranges, or -- blocked, the planes overflow the caches -- one resident wave of
+// workgroups (res) stepping through lock-step windows bq x be; the windows are those of the grid
+// actually launched (MMRE_SWEEP_GRID: a multiple of 8).
+struct Bf3Grid { int g, bq, be; bool blk; };
+static Bf3Grid bf3_grid(int g_ranges, int res, bool blocked, int q_tiles, int n_tiles) {
+  Bf3Grid G{g_ranges, 0, 0, blocked && n_tiles >= 8 && res % 8 == 0};
+  if (G.blk) G.g = res;
+  G.g = grid_override(G.g);
+  if (G.blk) {
+    G.g = std::max(8, G.g & ~7);
+    bf3_window(G.g / 8, q_tiles, n_tiles / 8, G.bq, G.be);
+  }
+  return G;
+}
+
+// The split-bf16 workspace (the comment above BF3_HDR), then the wide sweep's padded thresholds and
+// bound factors (q_pad floats each) and its 32-column block maxima of |e| (e_pad / 32 floats).
+struct Bf3Work {
+  int64_t cap;
+  uint32_t* hdr;
+  int2* pairs;
+  uint4 *qb, *eb;
+  float *qn, *en, *thr_pad, *qbf, *ebm;
+};
+static int64_t bf3_layout(Bf3Work& W, int64_t ktot, int64_t e_pad, int64_t q_pad, void* base) {
+  Carver w{(char*)base};
+  W.cap = bf3_cap(q_pad, e_pad);
+  W.hdr = w.take<uint32_t>(BF3_HDR);
+  W.pairs = w.take<int2>(8 * W.cap);
+  W.qn = w.take<float>(4 * q_pad);
+  W.en = w.take<float>(4 * e_pad);
+  W.qb = w.take<uint4>(4 * ktot * q_pad);
+  W.eb = w.take<uint4>(4 * ktot * e_pad);
+  W.thr_pad = w.take<float>(4 * q_pad);
+  W.qbf = w.take<float>(4 * q_pad);
+  W.ebm = w.take<float>(4 * (e_pad / 32));
+  return w.off;
 }
 
 extern "C" int64_t mmre_link_bf3_workspace(int model, int dim, int64_t e_pad, int64_t q_pad) {
   if (!mfma_model(model) || dim <= 0 || e_pad <= 0 || q_pad <= 0) return 0;
-  const int64_t ktot = (int64_t)n_planes(model) * plane_rows(model, dim);
-  // ... | the wide sweep's padded thresholds and bound factors (2 x q_pad floats) | its 32-column
-  // block maxima of |e| (e_pad / 32 floats)
-  return BF3_HDR + 8 * bf3_cap(q_pad, e_pad) + 4 * (q_pad + e_pad) + 4 * ktot * (q_pad + e_pad) + 8 * q_pad +
-         4 * (e_pad / 32);
+  Bf3Work W;
+  return bf3_layout(W, (int64_t)n_planes(model) * plane_rows(model, dim), e_pad, q_pad, nullptr);
 }
 
 extern "C" int mmre_link_bf3_stats(const void* d_work, int64_t work_bytes, uint64_t* d_out, void* stream) {
@@ -4656,161 +4725,118 @@ extern "C" int mmre_link_bf3_stats(const void* d_work, int64_t work_bytes, uint6
 // lock-step windows where the planes overflow the caches (as k_sweep_bf3's), else contiguous
 // unit ranges.
 template <int QT>
-static void launch_bf3w(hipStream_t st, const uint4* eb, int64_t e_pad, int64_t e_cols, int64_t n_slice,
-                        const uint4* qb, int64_t q_pad, int64_t n_query, int nkb, int e_begin, const float* thr_pad,
-                        const float* qbf, const float* en, int32_t* d_counts, uint32_t* hdr, int2* pairs, int64_t cap,
-                        int emajor, bool blocked, const char* grid_env) {
+static void launch_bf3w(const SweepCall& C, const Bf3Work& W, int nkb, int emajor, bool blocked) {
   using G = W3Geom<QT>;
-  const int n_etw = (int)((n_slice + W3E - 1) / W3E);
+  const int n_etw = (int)((C.n_slice + W3E - 1) / W3E);
   const int res = resident_groups((const void*)k_sweep_bf3w<2, QT, true>, G::NT);
-  const int64_t units = (q_pad / QT) * (int64_t)n_etw;
-  int g = (int)std::min<int64_t>(8LL * res, std::max<int64_t>((int64_t)res, units / 16)) & ~7;
-  int bq = 0, be = 0;
-  const bool blk = blocked && n_etw >= 8 && res % 8 == 0;
-  if (blk) g = res;
-  if (grid_env && grid_env[0] >= '1' && grid_env[0] <= '9') g = atoi(grid_env);
-  if (blk) {  // the windows of the grid actually launched (an env grid: a multiple of 8)
-    g = std::max(8, g & ~7);
-    bf3_window(g / 8, (int)(q_pad / QT), n_etw / 8, bq, be);
-  }
-  if (g < 1) g = 1;
-  const int ng = (g % 8 == 0 && n_etw >= 8) ? 8 : 1;
-  if (blk)
-    hipLaunchKernelGGL((k_sweep_bf3w<2, QT, true>), dim3((unsigned)g), dim3(G::NT), 0, st, eb, e_pad, e_cols, n_slice,
-                       qb, q_pad, n_query, nkb, n_etw, e_begin, ng, thr_pad, qbf, en, d_counts, hdr, pairs, cap,
-                       emajor, bq, be);
-  else
-    hipLaunchKernelGGL((k_sweep_bf3w<2, QT, false>), dim3((unsigned)g), dim3(G::NT), 0, st, eb, e_pad, e_cols, n_slice,
-                       qb, q_pad, n_query, nkb, n_etw, e_begin, ng, thr_pad, qbf, en, d_counts, hdr, pairs, cap,
-                       emajor, bq, be);
+  const int64_t units = (C.q_pad / QT) * (int64_t)n_etw;
+  const int g_ranges = (int)std::min<int64_t>(8LL * res, std::max<int64_t>((int64_t)res, units / 16)) & ~7;
+  const Bf3Grid B = bf3_grid(g_ranges, res, blocked, (int)(C.q_pad / QT), n_etw);
+  const int g = std::max(1, B.g);
+  with_bool(B.blk, [&](auto blk_) {
+    hipLaunchKernelGGL((k_sweep_bf3w<2, QT, decltype(blk_)::value>), dim3((unsigned)g), dim3(G::NT), 0, C.st, W.eb,
+                       C.e_pad, C.e_cols, C.n_slice, W.qb, C.q_pad, C.n_query, nkb, n_etw, C.e_base,
+                       xcd_groups(g, n_etw), W.thr_pad, W.qbf, W.ebm, C.counts, W.hdr, W.pairs, W.cap, emajor, B.bq,
+                       B.be);
+    return MMRE_OK;
+  });
 }
 
-// rows_src (mmre_link_sweep_bf3_rows): the entity split planes, norms and block maxima come from
+// The 128 x 128 sweep's launch: whole rounds of the resident capacity, ~3 units per workgroup --
+// static ranges of ~12 units left the list-heavy units' workgroups last (C3, 8,900 units at 768
+// resident: 4 rounds 0.454 ms against 0.479 for one, profiles/r6) -- or the lock-step windows.
+template <int PK>
+static void launch_bf3(const SweepCall& C, const Bf3Work& W, int nkb, float cb, int emajor, bool blocked) {
+  const int res = resident_groups((const void*)k_sweep_bf3<PK>, NT);
+  const int64_t units = C.q_tiles() * (int64_t)C.n_et;
+  const int64_t rounds = std::max<int64_t>(1, std::min<int64_t>(8, units / (3LL * res)));
+  const Bf3Grid B = bf3_grid((int)(rounds * res) & ~7, res, blocked, (int)C.q_tiles(), C.n_et);
+  hipLaunchKernelGGL((k_sweep_bf3<PK>), dim3((unsigned)B.g), dim3(NT), 0, C.st, W.eb, C.e_pad, C.n_slice, W.qb, C.q_pad,
+                     C.n_query, nkb, C.n_et, C.e_base, xcd_groups(B.g, C.n_et), C.pred_kind, C.margin, C.truth, W.qn,
+                     W.en, cb, C.counts, W.hdr, W.pairs, W.cap, emajor, B.bq, B.be);
+}
+
+// mmre_link_sweep_bf3 / _rows. rows_src: the entity split planes, norms and block maxima come from
 // the row-major table d_ent_rows in one pass (k_bf3_split_rows), and d_ent_km is written only by
 // the gated overflow fallback, right before the exact f32 sweep that reads it.
-static int sweep_bf3_impl(int model, int pred_kind, float margin, float* d_ent_km, const float* d_ent_rows,
-                          int64_t n_ent, int64_t e_pad, int64_t e_begin, int64_t e_end, const float* d_q_km,
-                          const float* d_q_rows, const int32_t* d_q_true, const int64_t* d_qr, const int8_t* d_qmode,
-                          int64_t n_query, int64_t q_pad, int dim, int32_t* d_counts, const float* d_truth,
-                          void* d_work, int64_t work_bytes, void* stream, bool rows_src) {
+static int sweep_bf3_impl(int model, SweepCall C, float* d_ent_km, const float* d_ent_rows, const float* d_q_rows,
+                          int64_t n_ent, int64_t e_begin, int64_t e_end, int dim, void* d_work, int64_t work_bytes,
+                          bool rows_src) {
   if (!mfma_model(model)) return MMRE_ERR_MODEL;
-  int rc = check_link_args(model, pred_kind, d_ent_km, n_ent, e_pad, d_q_km, d_q_true, d_qr, d_qmode, n_query,
-                           q_pad, nullptr, nullptr, d_counts, d_truth);
-  if (rc) return rc;
+  if (int rc = check_link_args(model, C, n_ent); rc) return rc;
+  const int64_t e_pad = C.e_pad, q_pad = C.q_pad;
   if (!d_ent_rows || !d_q_rows || !d_work || work_bytes < mmre_link_bf3_workspace(model, dim, e_pad, q_pad))
     return MMRE_ERR_WORKSPACE;
-  if (e_begin < 0 || e_begin % TE || e_end <= e_begin || e_end > n_ent) return MMRE_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
   const int kp = plane_rows(model, dim);
   const int ktot = n_planes(model) * kp;  // a multiple of 16 (plane_rows)
-  const int64_t cap = bf3_cap(q_pad, e_pad);
-  char* w = (char*)d_work;
-  uint32_t* hdr = (uint32_t*)w;
-  int2* pairs = (int2*)(w + BF3_HDR);
-  float* qn = (float*)(w + BF3_HDR + 8 * cap);
-  float* en = qn + q_pad;
-  uint4* qb = (uint4*)(en + e_pad);
-  uint4* eb = qb + (int64_t)ktot * q_pad / 4;
-  float* thr_pad = reinterpret_cast<float*>(eb + (int64_t)ktot * e_pad / 4);
-  float* qbf = thr_pad + q_pad;
-  float* ebm = qbf + q_pad;  // e_pad / 32 block maxima
-  const int64_t e_cols = round_up(e_end, TE) - e_begin;  // the slice's whole tiles
-  const int64_t n_slice = e_end - e_begin;
-  const int n_et = (int)((n_slice + TE - 1) / TE);
+  if (int rc = sweep_slice(C, n_ent, e_begin, e_end, ktot); rc) return rc;
+  C.qr = nullptr, C.qmode = nullptr, C.tw = 0;  // no type masks: the fallback's f32 sweep is passed none of these
+  hipStream_t st = C.st;
+  Bf3Work W;
+  bf3_layout(W, ktot, e_pad, q_pad, d_work);
   // bound coefficient (see k_sweep_bf3's header): 1.02 (7K 2^-24 (1 + 2^-7) + 3.02 2^-16 + 2^-29 sqrt K)
   const double K = (double)ktot;
   const float cb = (float)(1.02 * (7.0 * K * std::ldexp(1.0, -24) * (1.0 + std::ldexp(1.0, -7)) +
                                    3.02 * std::ldexp(1.0, -16) + std::ldexp(1.0, -29) * std::sqrt(K)));
   static_assert(BF3_SEGS == 64, "k_bf3_stats sums one segment per lane of a wave");
-  hipLaunchKernelGGL(k_bf3_hdr_init, dim3((BF3_HDR / 4 + 255) / 256), dim3(256), 0, st, hdr, cap);
+  hipLaunchKernelGGL(k_bf3_hdr_init, dim3((BF3_HDR / 4 + 255) / 256), dim3(256), 0, st, W.hdr, W.cap);
   const int nkb = ktot / 16;
-  hipLaunchKernelGGL(k_bf3_split, dim3((unsigned)((q_pad * nkb + 255) / 256)), dim3(256), 0, st, d_q_km, q_pad,
-                     (int64_t)0, q_pad, nkb, qb, q_pad);
+  hipLaunchKernelGGL(k_bf3_split, dim3((unsigned)((q_pad * nkb + 255) / 256)), dim3(256), 0, st, C.q, q_pad,
+                     (int64_t)0, q_pad, nkb, W.qb, q_pad);
   if (!rows_src)
-    hipLaunchKernelGGL(k_bf3_split, dim3((unsigned)((e_cols * nkb + 255) / 256)), dim3(256), 0, st, d_ent_km, e_pad,
-                       e_begin, e_cols, nkb, eb, e_pad);
-  static const char* order_env = getenv("MMRE_MFMA_EMAJOR");
-  const int emajor = order_env ? atoi(order_env) : ((double)e_pad * ktot * 4.0 > 64.0 * (1 << 20) ? 1 : 0);
+    hipLaunchKernelGGL(k_bf3_split, dim3((unsigned)((C.e_cols * nkb + 255) / 256)), dim3(256), 0, st, d_ent_km, e_pad,
+                       e_begin, C.e_cols, nkb, W.eb, e_pad);
+  const int emajor = mfma_emajor(e_pad, ktot);
   // the wide sweep (k_sweep_bf3w, prediction -S) where the planes overflow the caches (C5: 15.9
   // -> 14.5 ms per evaluation); on cache-resident planes the 128 x 128 one is faster (C3: 0.74 vs
   // 0.86-0.88 ms -- its per-pair bound lists fewer pairs than the wide sweep's per-tile one on
   // trained tables, whose norms vary); MMRE_BF3_WIDE=1 / 0 forces either (tests, A/B)
   const char* wide_env = getenv("MMRE_BF3_WIDE");  // read per call: tests switch it
-  const bool wide = pred_kind == 2 && (wide_env ? wide_env[0] != '0' : emajor != 0);
+  const bool wide = C.pred_kind == 2 && (wide_env ? wide_env[0] != '0' : emajor != 0);
   const char* qt_env = getenv("MMRE_BF3_QT");  // the wide sweep's query tile, 256 or 128
   const int wide_qt = qt_env ? atoi(qt_env) : 256;
-  hipLaunchKernelGGL(k_bf3_norms, dim3((unsigned)((q_pad + 3) / 4)), dim3(256), 0, st, d_q_rows, n_query, (int64_t)0,
-                     q_pad, ktot, qn, d_truth, wide ? thr_pad : nullptr, qbf, cb);
+  hipLaunchKernelGGL(k_bf3_norms, dim3((unsigned)((q_pad + 3) / 4)), dim3(256), 0, st, d_q_rows, C.n_query, (int64_t)0,
+                     q_pad, ktot, W.qn, C.truth, wide ? W.thr_pad : nullptr, W.qbf, cb);
   if (rows_src)  // split planes, norms and block maxima in one read of the rows (e_cols: whole tiles)
-    hipLaunchKernelGGL(k_bf3_split_rows, dim3((unsigned)(e_cols / 32)), dim3(256), 0, st, d_ent_rows, n_ent, e_begin,
-                       ktot, eb, e_pad, en, wide ? ebm : nullptr);
+    hipLaunchKernelGGL(k_bf3_split_rows, dim3((unsigned)(C.e_cols / 32)), dim3(256), 0, st, d_ent_rows, n_ent, e_begin,
+                       ktot, W.eb, e_pad, W.en, wide ? W.ebm : nullptr);
   else if (wide)
-    hipLaunchKernelGGL(k_bf3_enorms, dim3((unsigned)((e_cols + 31) / 32)), dim3(256), 0, st, d_ent_rows, n_ent,
-                       e_begin, e_cols, ktot, en, ebm);
+    hipLaunchKernelGGL(k_bf3_enorms, dim3((unsigned)((C.e_cols + 31) / 32)), dim3(256), 0, st, d_ent_rows, n_ent,
+                       e_begin, C.e_cols, ktot, W.en, W.ebm);
   else
-    hipLaunchKernelGGL(k_bf3_norms, dim3((unsigned)((e_cols + 3) / 4)), dim3(256), 0, st, d_ent_rows, n_ent, e_begin,
-                       e_cols, ktot, en, nullptr, nullptr, nullptr, 0.0f);
+    hipLaunchKernelGGL(k_bf3_norms, dim3((unsigned)((C.e_cols + 3) / 4)), dim3(256), 0, st, d_ent_rows, n_ent, e_begin,
+                       C.e_cols, ktot, W.en, nullptr, nullptr, nullptr, 0.0f);
   MMRE_CHECK_LAUNCH();
-  static const char* grid_env = getenv("MMRE_SWEEP_GRID"); /* experiments: workgroup count */
   // the lock-step windows pay where the planes overflow the caches (C5, 1 GB: 16.45 -> 16.24 ms);
   // on planes that stay L2 / MALL resident the contiguous ranges are faster (C3, 20 MB: 0.75 vs
   // 0.85 ms, profiles/r5) -- the emajor threshold; MMRE_BF3_BLOCKED=0 / 1 forces either (A/B)
   static const char* blk_env = getenv("MMRE_BF3_BLOCKED");
   const bool blocked = blk_env ? blk_env[0] != '0' : emajor != 0;
-#define MMRE_BF3(PKV)                                                                                           \
-  do {                                                                                                          \
-    if (wide && PKV == 2) {                                                                                     \
-      if (q_pad % 256 == 0 && wide_qt == 256)                                                                  \
-        launch_bf3w<256>(st, eb, e_pad, e_cols, n_slice, qb, q_pad, n_query, ktot / 16, (int)e_begin, thr_pad,   \
-                         qbf, ebm, d_counts, hdr, pairs, cap, emajor, blocked, grid_env);                       \
-      else                                                                                                     \
-        launch_bf3w<128>(st, eb, e_pad, e_cols, n_slice, qb, q_pad, n_query, ktot / 16, (int)e_begin, thr_pad,   \
-                         qbf, ebm, d_counts, hdr, pairs, cap, emajor, blocked, grid_env);                       \
-      MMRE_CHECK_LAUNCH();                                                                                     \
-    } else {                                                                                                   \
-    const int res = resident_groups((const void*)k_sweep_bf3<PKV>, NT);                                        \
-    const int64_t units = (q_pad / TQ) * (int64_t)n_et;                                                        \
-    /* whole rounds of the resident capacity, ~3 units per workgroup: static ranges of ~12 units left    \
-       the list-heavy units' workgroups last (C3, 8,900 units at 768 resident: 4 rounds 0.454 ms against    \
-       0.479 for one, profiles/r6) */                                                                        \
-    const int64_t rounds = std::max<int64_t>(1, std::min<int64_t>(8, units / (3LL * res)));                   \
-    int g = (int)(rounds * res) & ~7;                                                                          \
-    int bq = 0, be = 0;                                                                                        \
-    const bool blk = blocked && n_et >= 8 && res % 8 == 0;                                                    \
-    if (blk) g = res; /* the lock-step windows: one resident wave of workgroups */                            \
-    if (grid_env && grid_env[0] >= '1' && grid_env[0] <= '9') g = atoi(grid_env);                           \
-    if (blk) { /* the windows of the grid actually launched (an env grid: a multiple of 8) */                  \
-      g &= ~7;                                                                                                 \
-      if (g < 8) g = 8;                                                                                        \
-      bf3_window(g / 8, (int)(q_pad / TQ), n_et / 8, bq, be);                                                  \
-    }                                                                                                           \
-    const int ng = (g % 8 == 0 && n_et >= 8) ? 8 : 1;                                                          \
-    hipLaunchKernelGGL((k_sweep_bf3<PKV>), dim3((unsigned)g), dim3(NT), 0, st, eb, e_pad, n_slice, qb, q_pad,   \
-                       n_query, ktot / 16, n_et, (int)e_begin, ng, pred_kind, margin, d_truth, qn, en, cb,     \
-                       d_counts, hdr, pairs, cap, emajor, bq, be);                                             \
-    MMRE_CHECK_LAUNCH();                                                                                       \
-    }                                                                                                          \
-    hipLaunchKernelGGL((k_bf3_fallback_zero), dim3((unsigned)((n_query + 255) / 256)), dim3(256), 0, st, hdr,  \
-                       d_counts, n_query);                                                                     \
-    if (rows_src) { /* the fallback's k-major planes, only when it runs */                                      \
-      const int rb = stage_rows(ktot);                                                                         \
-      hipLaunchKernelGGL(k_prep_km_gated, dim3((unsigned)((e_cols + rb - 1) / rb)), dim3(256),                  \
-                         sizeof(float) * (size_t)rb * (ktot + 1), st, hdr + 1, model,                          \
-                         d_ent_rows + e_begin * (int64_t)ktot, n_slice, dim, kp, rb, d_ent_km + e_begin, e_pad); \
-    }                                                                                                          \
-    launch_mfma(false, false, pred_kind, margin, d_ent_km + e_begin, n_slice, e_pad, n_et, (int)e_begin,       \
-                d_q_km, q_pad, n_query, ktot, d_truth, nullptr, nullptr, nullptr, nullptr, 0, d_counts,        \
-                nullptr, st, hdr + 1);                                                                         \
-    MMRE_CHECK_LAUNCH();                                                                                       \
-    hipLaunchKernelGGL((k_bf3_rescore<PKV>), dim3(16 * (BF3_SEGS + 1)), dim3(256), 0, st, hdr, pairs, cap,     \
-                       d_q_rows,                                                                               \
-                       d_ent_rows, ktot, pred_kind, margin, d_truth, d_counts);                               \
-    MMRE_CHECK_LAUNCH();                                                                                       \
-  } while (0)
-  if (pred_kind == 2) MMRE_BF3(2);
-  else MMRE_BF3(-1);
-#undef MMRE_BF3
-  return launch_finalize(st, d_counts, n_query, false);
+  return with_bool(C.pred_kind == 2, [&](auto fast_) -> int {
+    constexpr int PK = decltype(fast_)::value ? 2 : -1;  // -S compiled into the epilogue, or decoded
+    if constexpr (PK == 2) {  // (the wide sweep has no other epilogue)
+      if (!wide) launch_bf3<PK>(C, W, nkb, cb, emajor, blocked);
+      else if (q_pad % 256 == 0 && wide_qt == 256) launch_bf3w<256>(C, W, nkb, emajor, blocked);
+      else launch_bf3w<128>(C, W, nkb, emajor, blocked);
+    } else {
+      launch_bf3<PK>(C, W, nkb, cb, emajor, blocked);
+    }
+    MMRE_CHECK_LAUNCH();
+    hipLaunchKernelGGL((k_bf3_fallback_zero), dim3((unsigned)((C.n_query + 255) / 256)), dim3(256), 0, st, W.hdr,
+                       C.counts, C.n_query);
+    if (rows_src) {  // the fallback's k-major planes, only when it runs
+      const int rb = stage_rows(ktot);
+      hipLaunchKernelGGL(k_prep_km_gated, dim3((unsigned)((C.e_cols + rb - 1) / rb)), dim3(256),
+                         sizeof(float) * (size_t)rb * (ktot + 1), st, W.hdr + 1, model,
+                         d_ent_rows + e_begin * (int64_t)ktot, C.n_slice, dim, kp, rb, d_ent_km + e_begin, e_pad);
+    }
+    const int r = launch_mfma(C, W.hdr + 1, false);  // the exact sweep, gated on the overflow flag
+    if (r) return r;
+    hipLaunchKernelGGL((k_bf3_rescore<PK>), dim3(16 * (BF3_SEGS + 1)), dim3(256), 0, st, W.hdr, W.pairs, W.cap,
+                       d_q_rows, d_ent_rows, ktot, C.pred_kind, C.margin, C.truth, C.counts);
+    MMRE_CHECK_LAUNCH();
+    return launch_finalize(st, C.counts, C.n_query, false);
+  });
 }
 
 extern "C" int mmre_link_sweep_bf3(int model, int pred_kind, float margin, const float* d_ent_km,
@@ -4819,9 +4845,10 @@ extern "C" int mmre_link_sweep_bf3(int model, int pred_kind, float margin, const
                                    const int32_t* d_q_true, const int64_t* d_qr, const int8_t* d_qmode,
                                    int64_t n_query, int64_t q_pad, int dim, int32_t* d_counts, const float* d_truth,
                                    void* d_work, int64_t work_bytes, void* stream) {
-  return sweep_bf3_impl(model, pred_kind, margin, const_cast<float*>(d_ent_km), d_ent_rows, n_ent, e_pad, e_begin,
-                        e_end, d_q_km, d_q_rows, d_q_true, d_qr, d_qmode, n_query, q_pad, dim, d_counts, d_truth,
-                        d_work, work_bytes, stream, false);
+  return sweep_bf3_impl(model, {(hipStream_t)stream, d_ent_km, e_pad, d_q_km, q_pad, n_query, pred_kind, margin,
+                                d_truth, d_q_true, d_qr, d_qmode, nullptr, nullptr, d_counts},
+                        const_cast<float*>(d_ent_km), d_ent_rows, d_q_rows, n_ent, e_begin, e_end, dim, d_work,
+                        work_bytes, false);
 }
 
 extern "C" int mmre_link_sweep_bf3_rows(int model, int pred_kind, float margin, const float* d_ent_rows,
@@ -4833,19 +4860,9 @@ extern "C" int mmre_link_sweep_bf3_rows(int model, int pred_kind, float margin, 
   // the row-major table must be the plane layout itself: DistMult with d a multiple of 16 (K = d)
   if (model != MMRE_DISTMULT || plane_rows(model, dim) != dim) return MMRE_ERR_SHAPE;
   if (!d_ent_rows || !d_ent_km || (reinterpret_cast<uintptr_t>(d_ent_rows) & 15)) return MMRE_ERR_ARG;
-  return sweep_bf3_impl(model, pred_kind, margin, d_ent_km, d_ent_rows, n_ent, e_pad, e_begin, e_end, d_q_km,
-                        d_q_rows, d_q_true, d_qr, d_qmode, n_query, q_pad, dim, d_counts, d_truth, d_work,
-                        work_bytes, stream, true);
-}
-
-extern "C" int mmre_link_sweep_range(int model, int pred_kind, float margin, const float* d_ent_km, int64_t n_ent,
-                                     int64_t e_pad, int64_t e_begin, int64_t e_end, const float* d_q_km,
-                                     const int32_t* d_q_true, const int64_t* d_qr, const int8_t* d_qmode,
-                                     int64_t n_query, int64_t q_pad, int dim, const uint32_t* d_type_head,
-                                     const uint32_t* d_type_tail, int32_t* d_counts, const float* d_truth,
-                                     void* stream) {
-  return sweep_impl(model, pred_kind, margin, d_ent_km, n_ent, e_pad, e_begin, e_end, d_q_km, d_q_true, d_qr, d_qmode,
-                    n_query, q_pad, dim, d_type_head, d_type_tail, d_counts, d_truth, nullptr, (hipStream_t)stream);
+  return sweep_bf3_impl(model, {(hipStream_t)stream, d_ent_km, e_pad, d_q_km, q_pad, n_query, pred_kind, margin,
+                                d_truth, d_q_true, d_qr, d_qmode, nullptr, nullptr, d_counts}, d_ent_km, d_ent_rows,
+                        d_q_rows, n_ent, e_begin, e_end, dim, d_work, work_bytes, true);
 }
 
 // ---------------------------------------- fused TransE L1 evaluation (round 5) ---
@@ -4853,21 +4870,34 @@ extern "C" int mmre_link_sweep_range(int model, int pred_kind, float margin, con
 // same LDS, 16 rows of kt + 1 floats at C2 (12.9 KB)
 static int eval_rb(int kp) { return stage_rows(kp); }
 static int eval_rbq(int kp) { return std::max(1, eval_rb(kp) / 2); }
-static int64_t eval_blocks(int dim, int64_t e_pad, int64_t q_pad) {
+// The fused evaluation's workspace: the L1Q workspace | tickets (256 bytes, zero before the first call:
+// the caller zeroes the workspace once; words 8-9 the row counts K1's block 0 writes) | K1's per-block
+// statistics | the grouped sweep's row map (q_pad each: rows <= queries) and tile_m (per query tile).
+struct EvalWork {
+  L1QWork q;
+  uint32_t* ticket;
+  int32_t* n_rows;
+  float* pstat;
+  int32_t *row_off, *row_cnt, *row_of_q, *tile_m;
+};
+static int64_t eval_layout(EvalWork& W, int dim, int64_t e_pad, int64_t q_pad, void* base) {
+  Carver w{(char*)base, l1q_layout(W.q, dim, e_pad, q_pad, base)};
   const int kp = plane_rows(MMRE_TRANSE_L1, dim);
-  return (e_pad + eval_rb(kp) - 1) / eval_rb(kp) + (q_pad + eval_rbq(kp) - 1) / eval_rbq(kp);
-}
-static int64_t eval_stat_bytes(int dim, int64_t e_pad, int64_t q_pad) {
-  return 256 + round_up(8 * eval_blocks(dim, e_pad, q_pad), 256);  // tickets (+ the row counts), K1's per-block statistics
-}
-static int64_t eval_extra_bytes(int dim, int64_t e_pad, int64_t q_pad) {
-  // + the grouped sweep's row map: row_off, row_cnt, row_of_q (q_pad each: rows <= queries), tile_m
-  return eval_stat_bytes(dim, e_pad, q_pad) + 3 * 4 * q_pad + round_up(4 * (q_pad / TQ), 256);
+  const int64_t blocks = (e_pad + eval_rb(kp) - 1) / eval_rb(kp) + (q_pad + eval_rbq(kp) - 1) / eval_rbq(kp);
+  W.ticket = w.take<uint32_t>(256);
+  W.n_rows = base ? (int32_t*)W.ticket + 8 : nullptr;
+  W.pstat = w.take<float>(round_up(8 * blocks, 256));
+  W.row_off = w.take<int32_t>(4 * q_pad);
+  W.row_cnt = w.take<int32_t>(4 * q_pad);
+  W.row_of_q = w.take<int32_t>(4 * q_pad);
+  W.tile_m = w.take<int32_t>(round_up(4 * (q_pad / TQ), 256));
+  return w.off;
 }
 
 extern "C" int64_t mmre_link_evaluate_l1q_workspace(int dim, int64_t e_pad, int64_t q_pad) {
-  const int64_t base = mmre_link_l1q_workspace(dim, e_pad, q_pad);
-  return base > 0 ? base + eval_extra_bytes(dim, e_pad, q_pad) : 0;
+  if (dim <= 0 || e_pad <= 0 || q_pad <= 0) return 0;
+  EvalWork W;
+  return eval_layout(W, dim, e_pad, q_pad, nullptr);
 }
 
 extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t n_ent, const float* d_rel,
@@ -4885,30 +4915,20 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   if (n_ent <= 0 || n_rel <= 0 || dim <= 0 || n_query <= 0 || n_groups <= 0 || n_groups > n_query || n_entries < 0)
     return MMRE_ERR_ARG;
   if (e_pad < n_ent || e_pad % TE || q_pad < n_query || q_pad % TQ) return MMRE_ERR_ARG;
-  if (e_begin < 0 || e_begin % TE || e_end <= e_begin || e_end > n_ent) return MMRE_ERR_ARG;
+  const int kp = plane_rows(MMRE_TRANSE_L1, dim), kt = kp;
+  // the f32 call (prediction = the score, no type masks); the code sweeps run over planes() of it
+  SweepCall C{(hipStream_t)stream, d_ent_km, e_pad, d_q_km, q_pad, n_query, 0, 0.0f, d_truth, d_q_true, d_qr, d_qmode};
+  C.counts = d_counts;
+  if (int rc = sweep_slice(C, n_ent, e_begin, e_end, kp); rc) return rc;
   if (n_entries > 0 && (!d_filt_ids || !d_entry_q || !d_list_scores)) return MMRE_ERR_WORKSPACE;
   if (n_ent > (int64_t)INT32_MAX - 256 || n_query >= (int64_t)INT32_MAX) return MMRE_ERR_SHAPE;
-  if (!d_work || work_bytes < mmre_link_evaluate_l1q_workspace(dim, e_pad, q_pad)) return MMRE_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const int kp = plane_rows(MMRE_TRANSE_L1, dim), kt = kp, k2 = l1q_rows(dim), k4 = l1q_rows8(dim);
+  EvalWork W;
+  if (!d_work || work_bytes < eval_layout(W, dim, e_pad, q_pad, d_work)) return MMRE_ERR_WORKSPACE;
+  hipStream_t st = C.st;
   const int rb = eval_rb(kp), rbq = eval_rbq(kp);
   const size_t lds1 = sizeof(float) * (size_t)std::max(rb, 3 * rbq) * (kt + 1);
   if (lds1 > 64 * 1024) return MMRE_ERR_SHAPE;
-  char* w = (char*)d_work;
-  uint32_t* hdr = (uint32_t*)w;
-  uint32_t* uq = (uint32_t*)(w + L1Q_HDR);
-  uint32_t* ue = uq + (int64_t)k2 * q_pad;
-  uint32_t* vq = ue + (int64_t)k2 * e_pad;
-  uint32_t* ve = vq + (int64_t)k4 * q_pad;
-  float* q_l1c = (float*)(ve + (int64_t)k4 * e_pad);
-  char* extra = w + mmre_link_l1q_workspace(dim, e_pad, q_pad);
-  uint32_t* ticket = (uint32_t*)extra;  // zero before the first call (the caller zeroes the workspace once)
-  float* pstat = (float*)(extra + 256);
-  int32_t* n_rows = (int32_t*)extra + 8;  // {rows, rows padded to tiles}: written by K1's block 0
-  int32_t* row_off = (int32_t*)(extra + eval_stat_bytes(dim, e_pad, q_pad));
-  int32_t* row_cnt = row_off + q_pad;
-  int32_t* row_of_q = row_cnt + q_pad;
-  int32_t* tile_m = row_of_q + q_pad;
+  const L1QWork& WQ = W.q;
   // Grouped or not. The grouped sweep shares a SAD chain among a row's members but pays for it:
   // K1's row-map block and K2's map blocks on every call, a longer unit per row, fewer units.
   // It runs when the rows (bounded from the group count: a group of n members is ceil(n / 8)
@@ -4921,19 +4941,13 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   int row_cap = cap_env ? std::min(L1Q_GS, std::max(1, atoi(cap_env))) : L1Q_GS;
   if (!cap_env) {
     const int64_t res = resident_groups((const void*)k_sweep_valu<6, false, false, 0, 1, L1Q_GS>, NT);
-    const int64_t n_et0 = (e_end - e_begin + TE - 1) / TE;
     const int64_t rows8 = std::min<int64_t>(n_query, n_groups + n_query / L1Q_GS);
-    if ((rows8 + TQ - 1) / TQ * n_et0 < res || (double)rows8 > L1Q_GROUP_FRAC * (double)n_query) row_cap = 0;
+    if ((rows8 + TQ - 1) / TQ * C.n_et < res || (double)rows8 > L1Q_GROUP_FRAC * (double)n_query) row_cap = 0;
   }
   const bool grouped = row_cap > 0;
   const int64_t rows_max = grouped ? std::min<int64_t>(n_query, n_groups + n_query / row_cap) : n_query;
-  const int64_t e_cols = round_up(e_end, TE) - e_begin;
-  const int64_t n_slice = e_end - e_begin;
-  const int n_et = (int)((n_slice + TE - 1) / TE);
-  static const char* ratio_env = getenv("MMRE_L1Q_RATIO");
-  static const char* tight_env = getenv("MMRE_L1_TIGHT");
-  const char* bits_env = getenv("MMRE_L1_BITS");
-  const int bits = bits_env ? atoi(bits_env) : 0;
+  static const char* tight_env = getenv("MMRE_L1_TIGHT");  // (once per process here)
+  const int bits = l1q_bits();
   const bool tight = kt <= 1984 && !(tight_env && tight_env[0] == '0');
   EvalL1 P{};
   P.ent = d_ent;
@@ -4958,33 +4972,33 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   P.q_true = d_q_true;
   P.truth = d_truth;
   P.e_begin = e_begin;
-  P.e_cols = e_cols;
+  P.e_cols = C.e_cols;
   P.n_eblk = (int)((e_pad + rb - 1) / rb);
   P.n_qblk = (int)((q_pad + rbq - 1) / rbq);
-  P.pstat = pstat;
+  P.pstat = W.pstat;
   P.und_q = d_undecided_q;
-  P.ticket = ticket;
-  P.hdr = hdr;
-  P.n_elem = (double)kp * (double)(q_pad + e_cols);
-  P.ratio = ratio_env ? (float)atof(ratio_env) : 128.0f;
+  P.ticket = W.ticket;
+  P.hdr = WQ.hdr;
+  P.n_elem = (double)kp * (double)(q_pad + C.e_cols);
+  P.ratio = l1q_ratio();
   P.grp_qoff = d_grp_qoff;
   P.n_groups = n_groups;
   P.row_cap = row_cap;
-  P.row_off = row_off;
-  P.row_cnt = row_cnt;
-  P.tile_m = tile_m;
-  P.n_rows = n_rows;
+  P.row_off = W.row_off;
+  P.row_cnt = W.row_cnt;
+  P.tile_m = W.tile_m;
+  P.n_rows = W.n_rows;
   // K1: the row map (block 0, grouped) | prep + truths + |x| statistics
   hipLaunchKernelGGL(k_eval_prep, dim3((unsigned)((grouped ? 1 : 0) + P.n_eblk + P.n_qblk)), dim3(256), lds1, st, P);
   MMRE_CHECK_LAUNCH();
   // K2: list scores | codes (8-bit words + error row, 16-bit words)
   EvalQuant Q{};
-  Q.pq = L1QPlane{d_q_km, q_pad, 0, q_pad, vq};
-  Q.pe = L1QPlane{d_ent_km, e_pad, e_begin, e_cols, ve};
-  Q.out16q = uq;
-  Q.out16e = ue;
-  Q.kw = k4;
-  Q.k2 = k2;
+  Q.pq = L1QPlane{d_q_km, q_pad, 0, q_pad, WQ.vq};
+  Q.pe = L1QPlane{d_ent_km, e_pad, e_begin, C.e_cols, WQ.ve};
+  Q.out16q = WQ.uq;
+  Q.out16e = WQ.ue;
+  Q.kw = WQ.k4;
+  Q.k2 = WQ.k2;
   Q.kt = kt;
   const int n_lblk = (int)((n_entries + 255) / 256);
   // quantization blocks per plane: the list blocks and both planes' blocks resident at once (one
@@ -4992,66 +5006,49 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   Q.n_blk = (int)std::min<int64_t>(512, std::max<int64_t>(64, (resident_groups((const void*)k_eval_quant_list, 256) -
                                                               n_lblk) / 2));
   Q.tight = tight ? 1 : 0;
-  Q.q_l1c = q_l1c;  // per sweep row (grouped), per query
-  Q.row_off = row_off;
-  Q.row_cnt = row_cnt;
+  Q.q_l1c = WQ.q_l1c;  // per sweep row (grouped), per query
+  Q.row_off = W.row_off;
+  Q.row_cnt = W.row_cnt;
   Q.grp_q = d_grp_q;
-  Q.n_rows = grouped ? n_rows : nullptr;
-  Q.row_of_q = row_of_q;
-  Q.tile_m = tile_m;
+  Q.n_rows = grouped ? W.n_rows : nullptr;
+  Q.row_of_q = W.row_of_q;
+  Q.tile_m = W.tile_m;
   const int n_mblk = grouped ? (int)((rows_max + 255) / 256) : 0;  // the query -> row map, tile_m: a thread per row
   hipLaunchKernelGGL(k_eval_quant_list, dim3((unsigned)(n_lblk + 2 * Q.n_blk + n_mblk)), dim3(256), 0, st, P, Q, d_filt_ids,
                      d_entry_q, n_entries, d_list_scores, n_lblk);
   MMRE_CHECK_LAUNCH();
   // K3: filter counts | the code-width probe
   const int n_cblk = (int)std::min<int64_t>((n_groups + 3) / 4, 65536);  // four groups (waves) per block
-  const uint32_t probe_max = l1q_probe_max(n_slice);
+  const uint32_t probe_max = l1q_probe_max(C.n_slice);
   hipLaunchKernelGGL(k_eval_count_probe, dim3((unsigned)(n_cblk + L1Q_PROBE_Q / 4)), dim3(256), 0, st, d_grp_qoff, d_grp_q,
                      n_groups, n_cblk, d_filt_off, d_filt_ids, d_list_scores, d_q_true, d_truth, n_query, n_ent,
-                     d_counts, vq, q_pad, ve + e_begin, e_pad, n_slice, k4, kt, tight ? q_l1c : nullptr, hdr,
-                     ticket, probe_max, bits == 8 || bits == 16 ? bits : 0, grouped ? row_of_q : nullptr);
+                     d_counts, WQ.vq, q_pad, WQ.ve + e_begin, e_pad, C.n_slice, WQ.k4, kt, tight ? WQ.q_l1c : nullptr,
+                     WQ.hdr, W.ticket, probe_max, bits == 8 || bits == 16 ? bits : 0, grouped ? W.row_of_q : nullptr);
   MMRE_CHECK_LAUNCH();
   // the sweeps: the one the code-width word names counts, the others' workgroups leave
-  const int64_t tw = (n_ent + 31) / 32;
-  L1Q l1{d_q_rows, d_ent_rows, hdr, (unsigned long long*)((char*)d_work + 256), d_q_km, d_ent_km + e_begin, kp,
-         kt, nullptr, tight ? q_l1c : nullptr, hdr + 4, d_undecided_q};
-  l1.wq = l1q_work_counters(hdr);
-  if (!grouped) {  // a sweep per query: the separate path's launches
-    int rc = launch_valu<6>(false, false, st, (const float*)(ve + e_begin), e_pad, n_slice, n_et, (int)e_begin,
-                            (const float*)vq, q_pad, n_query, k4, 0, 0.0f, d_truth, d_q_true, d_qr, d_qmode, nullptr,
-                            nullptr, tw, d_counts, nullptr, l1, false);
-    if (rc) return rc;
-    L1Q l16 = l1;
-    l16.gate = hdr + 1;
-    rc = launch_valu<5>(false, false, st, (const float*)(ue + e_begin), e_pad, n_slice, n_et, (int)e_begin,
-                        (const float*)uq, q_pad, n_query, k2, 0, 0.0f, d_truth, d_q_true, d_qr, d_qmode, nullptr,
-                        nullptr, tw, d_counts, nullptr, l16, false);
-    if (rc) return rc;
-  } else {
-  l1.row_off = row_off;
-  l1.row_cnt = row_cnt;
-  l1.grp_q = d_grp_q;
-  l1.tile_m = tile_m;
-  l1.n_rows = n_rows;
+  L1Q l1 = l1q_operands(WQ, C, d_q_rows, d_ent_rows, tight, d_undecided_q);
+  if (grouped) {
+    l1.row_off = W.row_off;
+    l1.row_cnt = W.row_cnt;
+    l1.grp_q = d_grp_q;
+    l1.tile_m = W.tile_m;
+    l1.n_rows = W.n_rows;
+  }
+  L1Q l16 = l1;
+  l16.gate = WQ.hdr + 1;
+  const SweepCall C8 = planes(C, WQ.ve, WQ.vq, WQ.k4), C16 = planes(C, WQ.ue, WQ.uq, WQ.k2);
   // the 8-bit sweep (it leaves unless the word names the 8-bit codes) and the gated 16-bit one
   // (one launch for both widths was tried: with both SAD loops in one kernel the allocator
-  // spilled 58-81 VGPRs): grouped, a SAD chain per sweep row, ranked against each member
-  int rc = launch_valu_grp<6>(st, (const float*)(ve + e_begin), e_pad, n_slice, n_et, (int)e_begin, (const float*)vq,
-                              q_pad, n_query, k4, d_truth, d_q_true, d_counts, l1, rows_max);
+  // spilled 58-81 VGPRs): a sweep per query, the separate path's launches, or grouped, a SAD
+  // chain per sweep row, ranked against each member
+  int rc = grouped ? launch_valu_grp<6>(C8, l1, rows_max) : launch_valu<6>(C8, l1, false);
+  if (!rc) rc = grouped ? launch_valu_grp<5>(C16, l16, rows_max) : launch_valu<5>(C16, l16, false);
   if (rc) return rc;
-  L1Q l16 = l1;
-  l16.gate = hdr + 1;
-  rc = launch_valu_grp<5>(st, (const float*)(ue + e_begin), e_pad, n_slice, n_et, (int)e_begin, (const float*)uq,
-                          q_pad, n_query, k2, d_truth, d_q_true, d_counts, l16, rows_max);
-  if (rc) return rc;
-  }
   // the f32 fallback, gated on the word; it also carries the finalize (filtered += raw)
   L1Q gate{};
-  gate.gate = hdr + 1;
+  gate.gate = WQ.hdr + 1;
   gate.fin_counts = d_counts;
   gate.fin_n = n_query;
-  gate.fin_ticket = hdr + 6;
-  return launch_valu<0>(false, false, st, d_ent_km + e_begin, e_pad, n_slice, n_et, (int)e_begin, d_q_km, q_pad,
-                        n_query, kp, 0, 0.0f, d_truth, d_q_true, d_qr, d_qmode, nullptr, nullptr, tw, d_counts,
-                        nullptr, gate, false);
+  gate.fin_ticket = WQ.hdr + 6;
+  return launch_valu<0>(C, gate, false);
 }
