@@ -173,6 +173,17 @@ int64_t mmre_link_l1q_workspace(int dim, int64_t e_pad, int64_t q_pad);
  * defective), d_out[3] = the largest per-entity error offset of the 8-bit codes' tight bound (in
  * code steps; 0 with the uniform bound). d_out holds 4 uint64. */
 int mmre_link_l1q_stats(const void* d_work, int64_t work_bytes, uint64_t* d_out, void* stream);
+/* The per-query route of the last mmre_link_evaluate_l1q on this workspace: queries whose 8-bit
+ * band holds a large share of the entities are counted by an exact f32 sweep of their own instead
+ * of the code sweep and its rescoring (same counts). d_out[0] = queries flagged by the sampled
+ * probe, d_out[1] = queries routed (the first `cap` flagged ones in query order), d_out[2] = sampled
+ * entity columns, d_out[3] = the sampled-pair count that flags a query; all 0 when the route did
+ * not act (small evaluations, 16-bit codes, a code width forced by MMRE_L1_BITS, the f32 fallback,
+ * MMRE_L1_HEAVY=0; MMRE_L1_HEAVY=1 lets it act at any size and with forced 8-bit codes). d_out holds 4
+ * uint64. mmre_link_l1q_route_cap: the routed list's cap for a shape, n_query / 16 (at least 1)
+ * or what the workspace region it lives in holds; 0 on bad arguments. */
+int mmre_link_l1q_route_stats(const void* d_work, int64_t work_bytes, uint64_t* d_out, void* stream);
+int64_t mmre_link_l1q_route_cap(int dim, int64_t e_pad, int64_t q_pad, int64_t n_query);
 int mmre_link_sweep_l1q(int pred_kind, float margin, const float* d_ent_km, const float* d_ent_rows, int64_t n_ent,
                         int64_t e_pad, int64_t e_begin, int64_t e_end, const float* d_q_km, const float* d_q_rows,
                         const int32_t* d_q_true, const int64_t* d_qr, const int8_t* d_qmode, int64_t n_query,

@@ -496,7 +496,16 @@ struct L1Q {
   const int32_t* grp_q;
   const int32_t* tile_m;
   const int32_t* n_rows;
+  // per-query route (the fused evaluation): the 8-bit sweeps leave out a query whose
+  // byte in `routed` is set (nullptr: no route); the indexed f32 sweep (IDX) counts queries
+  // route_list[0 .. *route_n) instead
+  const uint8_t* routed;
+  const int32_t* route_list;
+  const uint32_t* route_n;
 };
+// Header words of the route's record (zeroed with the header by K1, written by k_l1q_route_compact):
+// flagged queries, routed queries (the indexed sweep's row count), sampled columns, flag threshold
+constexpr int L1Q_ROUTE_W = 8;
 // The sweeps' dynamic-scheduling work counters (L1Q::wq): one per XCD group, each on a 128-B
 // line of its own -- the second half of an undecided-pair counter slot (L1Q_SLOT_STRIDE bytes
 // apart from byte 256; the slot's counter uses its first 8 bytes) -- zeroed with the header
@@ -1022,7 +1031,9 @@ struct ValuSmem : ValuSmemGrp<GS> {
 // The sweep body. Counts go to the raw columns only (counts[0][q], counts[2][q]); the filtered
 // columns (initialised to minus the listed entities that beat the truth by the truth pass)
 // receive them in k_counts_finalize, one coalesced pass after the sweep (half the atomics).
-template <int OP, bool TC, bool STORE, int PK, int NPL, int DYNC, int GS = 0>
+// IDX (the per-query route's f32 sweep): query row i of the sweep is query
+// l1.route_list[i], i < *l1.route_n -- the row count is the device's, as the grouped sweep's.
+template <int OP, bool TC, bool STORE, int PK, int NPL, int DYNC, int GS = 0, bool IDX = false>
 __device__ __forceinline__ void sweep_valu_body(
     ValuSmem<NPL, TC, (OP == 5 || OP == 6), GS>& sm, const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent,
     const float* __restrict__ q_km, int64_t q_pad, int64_t n_query, int kp, int n_et, int e_base, int n_groups,
@@ -1039,6 +1050,8 @@ __device__ __forceinline__ void sweep_valu_body(
   // thresholds in turn (the slot loop of the epilogue); see ValuSmemGrp and k_eval_prep's row map
   constexpr bool GRP = GS > 0;
   static_assert(!GRP || (L1F && PK == 0 && !TC && !STORE), "the grouped sweep is the plain integer filter's");
+  static_assert(!IDX || (OP == 0 && PK == 0 && !TC && !STORE && DYNC == 0 && !GRP),
+                "the indexed sweep is the plain f32 one");
   auto& sq = sm.sq;
   auto& se = sm.se;
   auto& s_thr = sm.s_thr;
@@ -1062,7 +1075,11 @@ __device__ __forceinline__ void sweep_valu_body(
   const int grp = blockIdx.x % n_groups, gmem = blockIdx.x / n_groups;
   const int per_grp = gridDim.x / n_groups;
   // (grouped: the row tiles, known on the device only)
-  const int n_qt = GRP ? __builtin_amdgcn_readfirstlane(l1.n_rows[GRP ? 1 : 0]) / TQ : (int)(q_pad / TQ);
+  // (indexed: the routed queries, none when the route did not act)
+  const int n_idx = IDX ? __builtin_amdgcn_readfirstlane((int)*l1.route_n) : 0;
+  const int n_qt = IDX   ? (n_idx + TQ - 1) / TQ
+                   : GRP ? __builtin_amdgcn_readfirstlane(l1.n_rows[GRP ? 1 : 0]) / TQ
+                         : (int)(q_pad / TQ);
   const UnitMap um(grp, n_groups, n_qt, n_et);
   const int nkc = kp / KC;
   // (compiled per mode and chunk: a runtime choice between the modes, or a runtime chunk size,
@@ -1095,8 +1112,12 @@ __device__ __forceinline__ void sweep_valu_body(
   auto load_meta = [&](int qtile, int slot) {
     const int tid = vgpr_opaque(threadIdx.x);
     if (tid < TQ) {
-      const int64_t q = (int64_t)qtile * TQ + tid;
-      const bool v = q < n_query;
+      int64_t q = (int64_t)qtile * TQ + tid;
+      bool v = q < n_query;
+      if constexpr (IDX) {  // row tid of the tile is routed query route_list[q]
+        v = q < (int64_t)n_idx;
+        q = v ? l1.route_list[q] : 0;
+      }
       const float th = v ? thr[q] : -INFINITY;
       s_thr[slot][tid] = th;
       s_true[slot][tid] = v ? qtrue[q] : -1;
@@ -1114,6 +1135,10 @@ __device__ __forceinline__ void sweep_valu_body(
         const float mc = __builtin_fmaf((float)ktm * 1.03f, md, 0x1p-120f);  // = l1c
         l1_int_thresholds(th, tight ? (v ? l1.q_l1c[q] : 0.0f) + 0x1p-120f : mc, md, mf, tight ? 2u * l1.hdr[3] : 0u,
                           t_sure, t_span);
+        if constexpr (w8) {
+          // a routed query (the indexed f32 sweep counts it): no sure pair, no band, as a padding row
+          if (l1.routed != nullptr && v && l1.routed[q]) t_sure = t_span = 0u;
+        }
         sm.s_ts[slot][tid] = t_sure;
         sm.s_tw[slot][tid] = t_span;
       }
@@ -1158,6 +1183,16 @@ __device__ __forceinline__ void sweep_valu_body(
           q[u] = (uint32_t)qq < (uint32_t)n_query ? qq : -1;
         }
       }
+      if constexpr (w8) {
+        // a routed member (the indexed f32 sweep counts it) becomes an empty slot. A round of its
+        // own, before the thresholds': with the bytes in flight beside the thresholds the tile's
+        // 64 accumulators no longer fit (8 VGPRs spilled); once per row tile.
+        if (l1.routed != nullptr) {
+#pragma unroll
+          for (int u = 0; u < GS / 2; ++u)
+            if (q[u] >= 0 && l1.routed[q[u]]) q[u] = -1;
+        }
+      }
 #pragma unroll
       for (int u = 0; u < GS / 2; ++u) th[u] = q[u] >= 0 ? thr[q[u]] : -INFINITY;
 #pragma unroll
@@ -1186,6 +1221,7 @@ __device__ __forceinline__ void sweep_valu_body(
   uint32_t rt0 = 0u, rt1 = 0u;
   bool st_new = false;
   int ld_tpar = 1, st_par = 0, ep_par = 0;
+  [[maybe_unused]] int iq0 = 0, iq1 = 0, iq2 = 0, iq3 = 0;  // indexed sweep: the staged unit's four query ids
   auto gload = [&]() {
     if constexpr (TC) {
       st_new = ld_kc == 0;
@@ -1210,7 +1246,22 @@ __device__ __forceinline__ void sweep_valu_body(
     const int64_t q0 = (int64_t)ld_qt * TQ, e0 = (int64_t)ld_et * TE;
     const float* qp = q_km + (int64_t)k * q_pad + q0 + sc4 * 4;
     const float* ep = ent_km + (int64_t)k * e_pad + e0 + sc4 * 4;
-    rq0 = *reinterpret_cast<const float4*>(qp);
+    if constexpr (IDX) {
+      // the thread's four query columns through the routed list (rows past it: column 0, never
+      // counted); the ids are read at a unit's first stage and kept -- read at every stage they
+      // put a second dependent load in front of each stage's (the sweep 82 us at C2)
+      if (ld_kc == 0) {
+        const int p0 = (int)q0 + sc4 * 4;
+        iq0 = p0 + 0 < n_idx ? l1.route_list[p0 + 0] : 0;
+        iq1 = p0 + 1 < n_idx ? l1.route_list[p0 + 1] : 0;
+        iq2 = p0 + 2 < n_idx ? l1.route_list[p0 + 2] : 0;
+        iq3 = p0 + 3 < n_idx ? l1.route_list[p0 + 3] : 0;
+      }
+      const float* qk = q_km + (int64_t)k * q_pad;
+      rq0 = make_float4(qk[iq0], qk[iq1], qk[iq2], qk[iq3]);
+    } else {
+      rq0 = *reinterpret_cast<const float4*>(qp);
+    }
     re0 = *reinterpret_cast<const float4*>(ep);
     if constexpr (NPL == 2) {
       rq1 = *reinterpret_cast<const float4*>(qp + (int64_t)kp * q_pad);
@@ -1789,8 +1840,13 @@ __device__ __forceinline__ void sweep_valu_body(
               if constexpr (TC) cc += __shfl_xor(cc, sh);
             }
             const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-            const int64_t q = q0 + ql;
-            if (te == 0 && q < n_query) {  // raw columns only: k_counts_finalize adds them to the filtered ones
+            int64_t q = q0 + ql;
+            bool vq = q < n_query;
+            if constexpr (IDX) {
+              vq = q < (int64_t)n_idx;
+              q = (vq && te == 0) ? l1.route_list[q] : 0;
+            }
+            if (te == 0 && vq) {  // raw columns only: k_counts_finalize adds them to the filtered ones
               if (c) atomicAdd(&counts[q], c);
               if constexpr (TC) {
                 if (cc) atomicAdd(&counts[2 * n_query + q], cc);
@@ -1837,7 +1893,7 @@ __device__ __forceinline__ void sweep_valu_body(
   }
 }
 
-template <int OP, bool TC, bool STORE, int PK, int DYNC = 0, int GS = 0>
+template <int OP, bool TC, bool STORE, int PK, int DYNC = 0, int GS = 0, bool IDX = false>
 __global__ __launch_bounds__(NT, (OP == 2) ? 3 : 4) void k_sweep_valu(
     const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent, const float* __restrict__ q_km,
     int64_t q_pad, int64_t n_query, int kp, int n_et, int e_base, int n_groups, int pred_kind, float margin,
@@ -1865,7 +1921,7 @@ __global__ __launch_bounds__(NT, (OP == 2) ? 3 : 4) void k_sweep_valu(
       return;
     }
   }
-  sweep_valu_body<OP, TC, STORE, PK, NPL, DYNC, GS>(sm, ent_km, e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base,
+  sweep_valu_body<OP, TC, STORE, PK, NPL, DYNC, GS, IDX>(sm, ent_km, e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base,
                                           n_groups, pred_kind, margin, thr, qtrue, qr, qmode, type_head, type_tail,
                                           type_words, counts, scores, l1);
   if (l1.gate != nullptr && l1.fin_counts != nullptr) {
@@ -4260,19 +4316,222 @@ __global__ __launch_bounds__(256, 4) void k_eval_quant_list(EvalL1 P, EvalQuant 
   }
 }
 
+// ---- the per-query route. A query whose truth ranks mid-table has a third to a half
+// of the entities inside its 8-bit band; each of those pairs is rescored with the canonical chain at
+// ~90 swept pairs' cost (MMRE_PAIR_COST), 30-50 code sweeps of the row, where an exact f32 sweep of
+// the row costs ~4.3. K3's third block range scores every sweep row against one fixed sample of
+// entity columns and flags a member whose band holds L1Q_HEAVY_FRAC of the sample or more;
+// k_l1q_route_compact lists the flagged queries (query order, capped); the 8-bit sweeps leave a
+// listed query out (load_meta / load_meta_grp) and the indexed f32 sweep counts it. Counts are the
+// same either way: the route only decides which exact method counts a query.
+// The sample: four windows of 64 columns, their starts spread evenly over the slice (lane l: window
+// l / 16, columns 4 (l % 16) .. + 3 of it) -- the same for every row, staged in LDS L1Q_HEAVY_KCH
+// code rows at a time. (mmre.link.l1q_heavy_sample restates it.)
+constexpr int L1Q_HEAVY_KCH = 16;
+constexpr double L1Q_HEAVY_FRAC = 0.10;   // of the sampled columns (measured: DESIGN.md 4e)
+constexpr double L1Q_HEAVY_ROW_COST = 4.3;  // an f32 row sweep in code sweeps (issue slots)
+constexpr double L1Q_PAIR_COST = 90.0;      // a rescored pair in swept pairs (MMRE_PAIR_COST)
+__host__ __device__ __forceinline__ int64_t l1q_heavy_col(int64_t n_slice, int lane) {
+  const int64_t span = n_slice > 64 ? n_slice - 64 : 0;
+  return ((span * (lane >> 4) / 3) & ~(int64_t)3) + 4 * (lane & 15);
+}
+static uint32_t l1q_heavy_sample(int64_t n_slice) {  // sampled columns inside the slice
+  uint32_t n = 0;
+  for (int l = 0; l < 64; ++l)
+    for (int j = 0; j < 4; ++j) n += l1q_heavy_col(n_slice, l) + j < n_slice;
+  return n;
+}
+struct HeavyProbe {
+  int n_blk;                 // blocks of the range (0: no route)
+  int e_base;
+  const int32_t* row_off;    // grouped: the row map (nullptr: a row per query)
+  const int32_t* row_cnt;
+  const int32_t* n_rows;
+  uint8_t* flags;            // per query: its sampled band reached min_count
+  uint32_t min_count;
+};
+
+// One block: the flag bytes -> the routed list (ascending query ids, the first `cap` flagged
+// ones: a scan, no first-come atomics), the bytes rewritten as the routed map, the record in the
+// header; a routed query's und_q entry becomes its f32 row's cost in rescored-pair units, so the
+// sharding's weights stay a cost. Inert (nothing routed, bytes cleared) unless the 8-bit codes count.
+__global__ __launch_bounds__(1024) void k_l1q_route_compact(uint32_t* __restrict__ hdr, uint8_t* __restrict__ flags,
+                                                            int32_t* __restrict__ list, int64_t n_query, int64_t q_pad,
+                                                            uint32_t cap, uint32_t* __restrict__ und_q, uint32_t und_cost,
+                                                            uint32_t n_samp, uint32_t min_count) {
+  __shared__ uint32_t s_w[16];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const bool on = hdr[1] == L1Q_CODES8;
+  // a thread's queries: a run of whole 16-byte words of the flag bytes (q_pad of them, a multiple
+  // of 128), read as uint4 -- byte by byte the block's two passes were 22 us at C2, latency-bound
+  const int64_t chunk = round_up((n_query + 1023) / 1024, 16);
+  const int64_t a = min(q_pad, tid * chunk), b = min(q_pad, a + chunk);
+  uint32_t n = 0u;
+  if (on) {
+#pragma unroll 4
+    for (int64_t o = a; o < b; o += 16) {
+      const uint4 v = *reinterpret_cast<const uint4*>(flags + o);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 16; ++j) n += (uint32_t)((((w[j >> 2] >> (8 * (j & 3))) & 255u) != 0u) & (o + j < n_query));
+    }
+  }
+  uint32_t inc = n;  // inclusive scan over the wave, then over the 16 waves
+#pragma unroll
+  for (int sh = 1; sh < 64; sh <<= 1) {
+    const uint32_t v = __shfl_up(inc, sh);
+    if (lane >= sh) inc += v;
+  }
+  if (lane == 63) s_w[wv] = inc;
+  __syncthreads();
+  uint32_t base = 0u, total = 0u;
+  for (int w = 0; w < 16; ++w) {
+    if (w < wv) base += s_w[w];
+    total += s_w[w];
+  }
+  uint32_t pos = base + inc - n;
+  for (int64_t o = a; o < b; o += 16) {
+    const uint4 v = *reinterpret_cast<const uint4*>(flags + o);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t out[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const bool f = on & (((w[j >> 2] >> (8 * (j & 3))) & 255u) != 0u) & (o + j < n_query);
+      const bool r = f && pos < cap;
+      if (r) {
+        list[pos] = (int32_t)(o + j);
+        if (und_q) und_q[o + j] = und_cost;
+        out[j >> 2] |= 1u << (8 * (j & 3));
+      }
+      pos += f;
+    }
+    *reinterpret_cast<uint4*>(flags + o) = make_uint4(out[0], out[1], out[2], out[3]);
+  }
+  if (tid == 0) {
+    hdr[L1Q_ROUTE_W + 0] = total;
+    hdr[L1Q_ROUTE_W + 1] = total < cap ? total : cap;
+    hdr[L1Q_ROUTE_W + 2] = on ? n_samp : 0u;
+    hdr[L1Q_ROUTE_W + 3] = on ? min_count : 0u;
+  }
+}
+
+// route record -> out[0..3] (mmre_link_l1q_route_stats)
+__global__ void k_l1q_route_stats(const uint32_t* __restrict__ work, unsigned long long* __restrict__ out) {
+  if (threadIdx.x < 4) out[threadIdx.x] = work[L1Q_ROUTE_W + threadIdx.x];
+}
+
 // K3: filter counts (k_filter_count without type masks, one WAVE per filter group, four per
 // block) | the code-width probe (k_l1q_probe's sample, one wave per sampled query: 128 blocks, so
 // the probe's count and ticket take 128 same-address atomics each, not 512), whose last block
 // turns the code-width word to the 16-bit codes when the sample's undecided fraction is over
 // the threshold. force_bits 8 / 16 (MMRE_L1_BITS): no probe; 16 sets the word (unless f32).
+// | the per-query route's probe (H.n_blk blocks, 0 without the route): every sweep row against the
+// fixed sample of entity columns, a flag byte per member query (HeavyProbe, above).
 __global__ __launch_bounds__(256) void k_eval_count_probe(
     const int64_t* __restrict__ grp_qoff, const int32_t* __restrict__ grp_q, int64_t n_groups, int n_cblk,
     const int64_t* __restrict__ off, const int32_t* __restrict__ ids, const float* __restrict__ list_v,
     const int32_t* __restrict__ qtrue, const float* __restrict__ thr, int64_t n_query, int64_t n_ent,
     int32_t* __restrict__ counts, const uint32_t* __restrict__ uq, int64_t q_pad, const uint32_t* __restrict__ ue,
     int64_t e_pad, int64_t n_slice, int kw, int kt, const float* __restrict__ q_l1c, uint32_t* __restrict__ hdr,
-    uint32_t* __restrict__ ticket, uint32_t probe_max, int force_bits, const int32_t* __restrict__ row_of_q) {
+    uint32_t* __restrict__ ticket, uint32_t probe_max, int force_bits, const int32_t* __restrict__ row_of_q,
+    HeavyProbe H) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n_pblk = (int)gridDim.x - n_cblk - H.n_blk;  // the code-width probe's blocks
+  if ((int)blockIdx.x >= n_cblk + n_pblk) {
+    // ---- the per-query route's probe: 32 sweep rows per block, 8 per wave, a lane per four columns
+    __shared__ uint4 s_e[L1Q_HEAVY_KCH][64];
+    if (__builtin_amdgcn_readfirstlane(hdr[1]) != L1Q_CODES8 || force_bits == 16) return;  // no 8-bit sweep
+    const int64_t n_r = H.n_rows ? (int64_t)H.n_rows[0] : n_query;
+    const int64_t row0 = ((int64_t)blockIdx.x - n_cblk - n_pblk) * 32 + __builtin_amdgcn_readfirstlane(wv) * 8;
+    if (row0 - __builtin_amdgcn_readfirstlane(wv) * 8 >= n_r) return;  // uniform over the block
+    const int64_t c = l1q_heavy_col(n_slice, lane);
+    uint32_t acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = 0u;
+    // Both operands of a chunk of code rows go through LDS, zero past the last row (|0 - 0| adds
+    // nothing), so the chunk's 16 steps are unrolled with their LDS reads in flight. (Query words
+    // read from HBM step by step, eight dependent-latency loads per step: K3 16 -> 71 us at C2.)
+    __shared__ __attribute__((aligned(16))) uint32_t s_q[L1Q_HEAVY_KCH][32];
+    const int64_t brow0 = row0 - __builtin_amdgcn_readfirstlane(wv) * 8;  // (32 rows of a block: inside q_pad)
+    const int wq = __builtin_amdgcn_readfirstlane(wv) * 8;
+    for (int r0 = 0; r0 < kw; r0 += L1Q_HEAVY_KCH) {
+      __syncthreads();  // the previous chunk's reads are done
+#pragma unroll
+      for (int rr = wv; rr < L1Q_HEAVY_KCH; rr += 4) {  // (entry (rr, lane): the lane's own columns)
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (r0 + rr < kw && c < n_slice) v = *reinterpret_cast<const uint4*>(ue + (int64_t)(r0 + rr) * e_pad + c);
+        s_e[rr][lane] = v;
+      }
+#pragma unroll
+      for (int i = tid; i < L1Q_HEAVY_KCH * 32; i += 256) {
+        const int rr = i >> 5;
+        s_q[rr][i & 31] = r0 + rr < kw ? uq[(int64_t)(r0 + rr) * q_pad + brow0 + (i & 31)] : 0u;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int rr = 0; rr < L1Q_HEAVY_KCH; ++rr) {
+        const uint4 e = s_e[rr][lane];
+        const uint4 a0 = *reinterpret_cast<const uint4*>(&s_q[rr][wq]);
+        const uint4 a1 = *reinterpret_cast<const uint4*>(&s_q[rr][wq + 4]);
+        const uint32_t a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          acc[i][0] = __builtin_amdgcn_sad_u8(a[i], e.x, acc[i][0]);
+          acc[i][1] = __builtin_amdgcn_sad_u8(a[i], e.y, acc[i][1]);
+          acc[i][2] = __builtin_amdgcn_sad_u8(a[i], e.z, acc[i][2]);
+          acc[i][3] = __builtin_amdgcn_sad_u8(a[i], e.w, acc[i][3]);
+        }
+      }
+    }
+    // every member's own band (the sweep's thresholds: load_meta / load_meta_grp), its truth left out
+    const float l1d = l1q_delta(hdr, 255.0f);
+    const float l1f = (float)(kt + 4) * 0x1p-23f * (1.0f + 0x1p-8f);
+    const float l1c = __builtin_fmaf((float)kt * 1.03f, l1d, 0x1p-120f);
+    const uint32_t om2 = q_l1c ? 2u * hdr[3] : 0u;
+    // The wave's 8 rows x 8 member slots are its 64 lanes: lane l loads slot l % 8 of row l / 8 --
+    // the map entry, the member, its threshold and truth, three dependent rounds once for all of
+    // them (member after member they were ~20 serial round trips per wave: K3 16 -> 68 us at C2).
+    // Then each member's thresholds are broadcast and its band counted over the 64 lanes' columns.
+    const int mi = lane >> 3, ms = lane & 7;
+    const int64_t mrow = row0 + mi;
+    int64_t mq = -1;
+    float rc = l1c;
+    if (mrow < n_r) {
+      const int cnt = H.row_cnt ? min(H.row_cnt[mrow], 8) : 1;
+      if (ms < cnt) mq = H.row_off ? (int64_t)grp_q[(int64_t)H.row_off[mrow] + ms] : mrow;
+      if ((uint64_t)mq >= (uint64_t)n_query) mq = -1;
+      if (q_l1c) rc = q_l1c[mrow] + 0x1p-120f;
+    }
+    uint32_t m_ts = 0u, m_tw = 0u;
+    int m_tr = -1;  // the truth's column of the slice (or outside it)
+    if (mq >= 0) {
+      l1_int_thresholds(thr[mq], rc, l1d, l1f, om2, m_ts, m_tw);
+      const int64_t t = (int64_t)qtrue[mq] - H.e_base;
+      m_tr = t >= 0 && t < n_slice ? (int)t : -1;
+    }
+    const int ci = (int)c;  // (columns are int32 ids: the entry point's check)
+    uint32_t mine = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const uint32_t tw = (uint32_t)__builtin_amdgcn_readlane((int)m_tw, i * 8 + s);
+        if (tw == 0u) continue;  // uniform: no member, or no band
+        const uint32_t ts = (uint32_t)__builtin_amdgcn_readlane((int)m_ts, i * 8 + s);
+        const int tr = __builtin_amdgcn_readlane(m_tr, i * 8 + s);
+        uint32_t und = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          und += (uint32_t)__builtin_popcountll(
+              __ballot((acc[i][j] - ts < tw) & ((int64_t)ci + j < n_slice) & (ci + j != tr)));
+        if (lane == i * 8 + s) mine = und;
+      }
+    }
+    if (mq >= 0) H.flags[mq] = mine >= H.min_count ? 1 : 0;
+    return;
+  }
   if ((int)blockIdx.x < n_cblk) {
     // the wave's own LDS slices: written and read by the same wave (wave barriers, no block sync)
     __shared__ __attribute__((aligned(16))) int32_t s_id[4][64];
@@ -4330,7 +4589,7 @@ __global__ __launch_bounds__(256) void k_eval_count_probe(
     return;
   }
   if (w != L1Q_CODES8) return;  // the f32 fallback: no codes to probe
-  const int pb = ((int)blockIdx.x - n_cblk) * 4 + wv, n_pb = ((int)gridDim.x - n_cblk) * 4;
+  const int pb = ((int)blockIdx.x - n_cblk) * 4 + wv, n_pb = n_pblk * 4;
   const int64_t q = (int64_t)pb * n_query / n_pb;
   // the same sampled queries as the separate path's probe; their codes and error sums sit in
   // their sweep row's column (row_of_q: the grouped planes)
@@ -4369,7 +4628,7 @@ __global__ __launch_bounds__(256) void k_eval_count_probe(
     if (bu) __hip_atomic_fetch_add(hdr + 2, bu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
     s_last = __hip_atomic_fetch_add(&ticket[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-             (uint32_t)(gridDim.x - n_cblk) - 1;
+             (uint32_t)n_pblk - 1;
   }
   __syncthreads();
   if (s_last && tid == 0) {
@@ -4900,6 +5159,35 @@ extern "C" int64_t mmre_link_evaluate_l1q_workspace(int dim, int64_t e_pad, int6
   return eval_layout(W, dim, e_pad, q_pad, nullptr);
 }
 
+// The per-query route's storage: K1's pstat region, dead once K2 has reduced it (the workspace does
+// not grow) -- q_pad flag bytes (K3's probe; then the routed map), then the routed list in what is
+// left. The cap: n_query / 16 (at least 1), or what the list holds.
+struct RouteStore {
+  uint8_t* flags;
+  int32_t* list;
+  int64_t cap_store, cap;
+};
+static RouteStore route_store(float* pstat, int dim, int64_t e_pad, int64_t q_pad, int64_t n_query) {
+  const int kp = plane_rows(MMRE_TRANSE_L1, dim);
+  const int64_t blocks = (e_pad + eval_rb(kp) - 1) / eval_rb(kp) + (q_pad + eval_rbq(kp) - 1) / eval_rbq(kp);
+  const int64_t bytes = round_up(8 * blocks, 256);  // eval_layout's
+  RouteStore R{(uint8_t*)pstat, (int32_t*)((char*)pstat + q_pad), std::max<int64_t>(0, (bytes - q_pad) / 4), 0};
+  R.cap = std::min(R.cap_store, std::max<int64_t>(1, n_query / 16));
+  return R;
+}
+extern "C" int64_t mmre_link_l1q_route_cap(int dim, int64_t e_pad, int64_t q_pad, int64_t n_query) {
+  if (dim <= 0 || e_pad <= 0 || q_pad <= 0 || n_query <= 0 || n_query > q_pad || e_pad % TE || q_pad % TQ) return 0;
+  return route_store(nullptr, dim, e_pad, q_pad, n_query).cap;
+}
+
+extern "C" int mmre_link_l1q_route_stats(const void* d_work, int64_t work_bytes, uint64_t* d_out, void* stream) {
+  if (!d_work || !d_out || work_bytes < L1Q_HDR) return MMRE_ERR_ARG;
+  hipLaunchKernelGGL(k_l1q_route_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, (const uint32_t*)d_work,
+                     (unsigned long long*)d_out);
+  MMRE_CHECK_LAUNCH();
+  return MMRE_OK;
+}
+
 extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t n_ent, const float* d_rel,
                                       int64_t n_rel, int dim, const int64_t* d_qh, const int64_t* d_qr,
                                       const int64_t* d_qt, const int8_t* d_qmode, int64_t n_query,
@@ -5017,14 +5305,52 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   hipLaunchKernelGGL(k_eval_quant_list, dim3((unsigned)(n_lblk + 2 * Q.n_blk + n_mblk)), dim3(256), 0, st, P, Q, d_filt_ids,
                      d_entry_q, n_entries, d_list_scores, n_lblk);
   MMRE_CHECK_LAUNCH();
-  // K3: filter counts | the code-width probe
+  // The per-query route: when the sweep's units fill the resident grid -- grouping's
+  // own test: a small evaluation is launch-bound, and three more launches cost it more than its
+  // rescoring -- and the 8-bit codes may count by the probe's own choice. MMRE_L1_HEAVY=0 / 1: off /
+  // on at any size; MMRE_L1_HEAVY_MIN: the sampled-pair count that flags; MMRE_L1_HEAVY_CAP: the
+  // list's cap (A/B, tests).
+  const RouteStore R = route_store(W.pstat, dim, e_pad, q_pad, n_query);
+  const char* heavy_env = getenv("MMRE_L1_HEAVY");
+  bool heavy = bits != 16 && R.cap > 0;
+  if (heavy && heavy_env) heavy = atoi(heavy_env) != 0;
+  else if (heavy) {  // (the grouping rule's bound on the rows, whichever sweep MMRE_GROUP_CAP forces)
+    const int64_t res = resident_groups((const void*)k_sweep_valu<6, false, false, 0, 1, L1Q_GS>, NT);
+    const int64_t rows8 = std::min<int64_t>(n_query, n_groups + n_query / L1Q_GS);
+    // (a forced code width, MMRE_L1_BITS, is an A/B hook: its record stays the plain sweep's)
+    heavy = bits == 0 && (rows8 + TQ - 1) / TQ * C.n_et >= res;
+  }
+  HeavyProbe H{};
+  uint32_t route_cap = 0;
+  if (heavy) {
+    const char* min_env = getenv("MMRE_L1_HEAVY_MIN");
+    const char* cap_env2 = getenv("MMRE_L1_HEAVY_CAP");
+    const uint32_t n_samp = l1q_heavy_sample(C.n_slice);
+    H.n_blk = (int)((rows_max + 31) / 32);
+    H.e_base = C.e_base;
+    H.row_off = grouped ? W.row_off : nullptr;
+    H.row_cnt = grouped ? W.row_cnt : nullptr;
+    H.n_rows = grouped ? W.n_rows : nullptr;
+    H.flags = R.flags;
+    H.min_count = min_env ? (uint32_t)std::min<long long>(std::max(0LL, atoll(min_env)), UINT32_MAX)
+                          : std::max<uint32_t>(1u, (uint32_t)std::ceil(L1Q_HEAVY_FRAC * (double)n_samp));
+    route_cap = (uint32_t)(cap_env2 ? std::min<long long>(std::max(0LL, atoll(cap_env2)), R.cap_store) : R.cap);
+  }
+  // K3: filter counts | the code-width probe | the route's probe
   const int n_cblk = (int)std::min<int64_t>((n_groups + 3) / 4, 65536);  // four groups (waves) per block
   const uint32_t probe_max = l1q_probe_max(C.n_slice);
-  hipLaunchKernelGGL(k_eval_count_probe, dim3((unsigned)(n_cblk + L1Q_PROBE_Q / 4)), dim3(256), 0, st, d_grp_qoff, d_grp_q,
-                     n_groups, n_cblk, d_filt_off, d_filt_ids, d_list_scores, d_q_true, d_truth, n_query, n_ent,
-                     d_counts, WQ.vq, q_pad, WQ.ve + e_begin, e_pad, C.n_slice, WQ.k4, kt, tight ? WQ.q_l1c : nullptr,
-                     WQ.hdr, W.ticket, probe_max, bits == 8 || bits == 16 ? bits : 0, grouped ? W.row_of_q : nullptr);
+  hipLaunchKernelGGL(k_eval_count_probe, dim3((unsigned)(n_cblk + L1Q_PROBE_Q / 4 + H.n_blk)), dim3(256), 0, st,
+                     d_grp_qoff, d_grp_q, n_groups, n_cblk, d_filt_off, d_filt_ids, d_list_scores, d_q_true, d_truth,
+                     n_query, n_ent, d_counts, WQ.vq, q_pad, WQ.ve + e_begin, e_pad, C.n_slice, WQ.k4, kt,
+                     tight ? WQ.q_l1c : nullptr, WQ.hdr, W.ticket, probe_max, bits == 8 || bits == 16 ? bits : 0,
+                     grouped ? W.row_of_q : nullptr, H);
   MMRE_CHECK_LAUNCH();
+  if (heavy) {  // after the width decision: the routed list, the routed map and the record
+    const double cost = std::ceil(L1Q_HEAVY_ROW_COST * (double)C.n_slice / L1Q_PAIR_COST);
+    hipLaunchKernelGGL(k_l1q_route_compact, dim3(1), dim3(1024), 0, st, WQ.hdr, R.flags, R.list, n_query, q_pad,
+                       route_cap, d_undecided_q, (uint32_t)cost, l1q_heavy_sample(C.n_slice), H.min_count);
+    MMRE_CHECK_LAUNCH();
+  }
   // the sweeps: the one the code-width word names counts, the others' workgroups leave
   L1Q l1 = l1q_operands(WQ, C, d_q_rows, d_ent_rows, tight, d_undecided_q);
   if (grouped) {
@@ -5034,6 +5360,7 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
     l1.tile_m = W.tile_m;
     l1.n_rows = W.n_rows;
   }
+  if (heavy) l1.routed = R.flags;
   L1Q l16 = l1;
   l16.gate = WQ.hdr + 1;
   const SweepCall C8 = planes(C, WQ.ve, WQ.vq, WQ.k4), C16 = planes(C, WQ.ue, WQ.uq, WQ.k2);
@@ -5044,6 +5371,20 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   int rc = grouped ? launch_valu_grp<6>(C8, l1, rows_max) : launch_valu<6>(C8, l1, false);
   if (!rc) rc = grouped ? launch_valu_grp<5>(C16, l16, rows_max) : launch_valu<5>(C16, l16, false);
   if (rc) return rc;
+  // the routed queries' exact f32 sweep, before the launch that carries the finalize: the grid from
+  // the cap, the row tiles from the device's count (workgroups without a unit leave at once)
+  if (heavy && route_cap > 0) {
+    L1Q lr{};
+    lr.route_list = R.list;
+    lr.route_n = WQ.hdr + L1Q_ROUTE_W + 1;
+    const void* kh = (const void*)k_sweep_valu<0, false, false, 0, 0, 0, true>;
+    const int64_t units = sweep_units(((int64_t)route_cap + TQ - 1) / TQ, C.n_et);
+    const int g = (int)std::max<int64_t>(1, std::min<int64_t>(resident_groups(kh, NT), units));
+    hipLaunchKernelGGL((k_sweep_valu<0, false, false, 0, 0, 0, true>), dim3((unsigned)g), dim3(NT), 0, st, C.ent, C.e_pad,
+                       C.n_slice, C.q, C.q_pad, C.n_query, C.kp, C.n_et, C.e_base, xcd_groups(g, C.n_et), 0, 0.0f,
+                       C.truth, C.q_true, nullptr, nullptr, nullptr, nullptr, (int64_t)0, C.counts, nullptr, lr);
+    MMRE_CHECK_LAUNCH();
+  }
   // the f32 fallback, gated on the word; it also carries the finalize (filtered += raw)
   L1Q gate{};
   gate.gate = WQ.hdr + 1;

@@ -433,6 +433,49 @@ class LinkSweep:
         # undecided-list entries the rescoring refused as out of range (0 unless a defect)
         return dict(undecided=u, fallback=w == 1, bits={0: 8, 2: 16}.get(w), guarded=g, max_offset=o)
 
+    def l1q_route_stats(self, buffers):
+        """The per-query route's record of the last fused run() on `buffers`
+        (mmre_link_l1q_route_stats): dict(flagged=queries whose sampled band reached
+        the threshold, routed=queries the exact f32 sweep counted instead of the 8-bit codes -- the
+        first `cap` flagged ones in query order, sample=sampled entity columns, threshold=the
+        sampled-pair count that flags), all 0 when the route did not act; None if that run did not
+        use the integer filter. Synchronises the stream."""
+        if not buffers.get("l1q_used"):
+            return None
+        wk = buffers["l1q_work"]
+        out = buffers.get("l1q_route_stats")
+        if out is None:
+            out = buffers["l1q_route_stats"] = torch.zeros(4, dtype=torch.int64, device=self.device)
+        call("mmre_link_l1q_route_stats", ptr(wk), int(wk.numel()), ptr(out), stream_ptr(self.device))
+        f, r, s, t = (int(v) for v in out.cpu())
+        return dict(flagged=f, routed=r, sample=s, threshold=t)
+
+    def l1q_routed(self, buffers):
+        """The routed query ids of the last fused run() on `buffers`, in list order (tests and
+        probes): read out of the workspace -- the flag bytes and the list sit in the region after
+        the L1Q workspace and the 256 ticket bytes (csrc/link.hip: eval_layout, route_store)."""
+        st = self.l1q_route_stats(buffers)
+        if st is None:
+            return None
+        q_pad = int(buffers["q_pad"])
+        at = int(_lib.lib().mmre_link_l1q_workspace(self.spec.dim, self.e_pad, q_pad)) + 256 + q_pad
+        raw = buffers["l1q_work"][at:at + 4 * st["routed"]].cpu().numpy()
+        return raw.view(np.int32).astype(np.int64)
+
+
+def l1q_heavy_sample(n_slice):
+    """The entity columns (slice-relative) the per-query route's probe scores every sweep row
+    against: four windows of 64 columns whose starts are spread evenly over the slice (multiples
+    of 4), cut at the slice's end -- the device's rule (k_eval_count_probe), restated for tests
+    and probes. A short slice repeats columns; each repeat counts, as on the device."""
+    n_slice = int(n_slice)
+    span = max(n_slice - 64, 0)
+    cols = []
+    for w in range(4):
+        s = (span * w // 3) & ~3
+        cols.extend(c for c in range(s, s + 64) if c < n_slice)
+    return np.asarray(cols, np.int64)
+
 
 def _rows_view(c):
     """(4, n) int32 with unit element stride (row stride free): column slices of one

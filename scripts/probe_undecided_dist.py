@@ -39,6 +39,13 @@ def main():
         k = int(np.searchsorted(np.cumsum(s), f * s.sum())) + 1
         print(f"{int(f * 100)} % of the pairs in the top {k} queries")
     print("raw count of the top-5 queries:", c[0][np.argsort(u)[::-1][:5]].tolist())
+    # the per-query route's candidates: queries whose undecided pairs exceed a share
+    # of the entities, and the share of all undecided pairs they hold (run with MMRE_L1_HEAVY=0:
+    # a routed query's entry is its heavy-sweep cost, not a pair count)
+    print("share of the entities | queries above it | their share of the undecided pairs")
+    for pct in (2, 5, 10, 20, 40):
+        sel = u > pct / 100.0 * w["n_ent"]
+        print(f"{pct:3d} % | {int(sel.sum()):6d} | {u[sel].sum() / max(1, u.sum()):.4f}")
 
 
 if __name__ == "__main__":
