@@ -326,6 +326,98 @@ int mmre_rel_evaluate(int model, int norm_flag, int pred_kind, float margin, con
 int mmre_rel_metrics(const int32_t* h_counts, int64_t n, int64_t stride, float* h_out);
 
 /* ====================================================================== *
+ *  Triple classification: one corrupted copy of every test triple         *
+ *  (getNegTest / getTestBatch, Test.h:393-422), model.predict on both in   *
+ *  'normal' mode, and the score threshold that separates them best         *
+ *  (Tester.py:93-151 get_best_threshlod / run_triple_classification).      *
+ *  Every entry: explicit stream, no allocation or synchronisation inside,  *
+ *  every argument checked before any launch, n == 0 a successful no-op.    *
+ * ====================================================================== */
+
+/* getNegTest on the GPU, bit-exact with Base.so. For test triple i, in testList order, thread 0's
+ * LCG (Random.h:18-29) is drawn exactly twice: the coin `randd(0) % 1000 < 500` (true: the TAIL is
+ * replaced by corrupt_head(0, h, r); false: the HEAD by corrupt_tail(0, t, r)) and the corruption's
+ * one rand_max, filtered against the TRAIN lists only. Triple i therefore starts from `state`
+ * advanced by 2 i draws and all triples are sampled in parallel; the state after the call is
+ * mmre_tc_advance(state, n). `state`: thread 0's state before the call. Index arrays: the
+ * Reader.h:53-160 train index as mmre_sampler_openke takes it (int64 rows (h, r, t); head_hrt
+ * sorted (h, r, t), tail_hrt (t, r, h); lef / rig per entity, rig = -1 for an entity absent from
+ * that side). Outputs int64 d_neg_h[n], d_neg_t[n]; the negative's relation is the positive's.
+ * Pinned where the reference is undefined: when the kept entity never occurs on that side of a train
+ * triple, Corrupt.h computes ll = -1, rr = 0 and reads trainHead[-1]; here nothing is read, the
+ * modulus is the one the reference computes (n_ent - 2) and the draw is returned unchanged. Every
+ * other quirk of Corrupt.h is reproduced (a relation between, below or above the kept entity's
+ * relations; that includes the one draw Corrupt.h shifts to n_ent itself, when the relation falls
+ * into an empty block whose neighbouring rows' values descend -- mmre_tc_scores gives such a row
+ * NaN). A test triple whose h or t is outside [0, n_ent) gives neg_h = neg_t = -1.
+ * MMRE_ERR_ARG: a null index / triple / output array, train_total < 1, n_ent < 3, n < 0;
+ * MMRE_ERR_SHAPE: n > INT32_MAX. */
+int mmre_tc_negatives(const int64_t* d_head_hrt, const int64_t* d_tail_hrt, const int64_t* d_lef_head,
+                      const int64_t* d_rig_head, const int64_t* d_lef_tail, const int64_t* d_rig_tail,
+                      int64_t train_total, int64_t n_ent, const int64_t* d_test_h, const int64_t* d_test_r,
+                      const int64_t* d_test_t, int64_t n, uint64_t state, int64_t* d_neg_h, int64_t* d_neg_t,
+                      void* stream);
+/* Host: thread 0's state after getNegTest over n test triples (2 n draws). */
+uint64_t mmre_tc_advance(uint64_t state, int64_t n);
+
+/* model.predict ('normal' mode) of n positive rows and their n negative rows: bit for bit the score
+ * chain of mmre_ns_forward for each row followed by the pred_kind / margin transform of
+ * mmre_link_truth -- the contract of mmre_rel_evaluate. One wave per pair of rows; a table row the
+ * two share is loaded once. d_neg_r NULL: the negatives' relations are the positives'. Tables as
+ * mmre_ns_forward takes them (RotatE entities (E, 2 dim)). A row with an id out of range reads
+ * nothing and scores NaN. MMRE_ERR_MODEL: unknown model; MMRE_ERR_SHAPE: dim > 512, n > INT32_MAX;
+ * MMRE_ERR_ARG: dim < 1, a null table / triple / output array, ComplEx without its imaginary tables,
+ * RotatE with phase_denom 0 or NaN, n_ent < 1, n_rel < 1, n < 0, pred_kind outside 0..4. */
+int mmre_tc_scores(int model, int norm_flag, int pred_kind, float margin, const float* d_ent, const float* d_ent_im,
+                   const float* d_rel, const float* d_rel_im, int64_t n_ent, int64_t n_rel, int dim,
+                   float phase_denom, const int64_t* d_pos_h, const int64_t* d_pos_r, const int64_t* d_pos_t,
+                   const int64_t* d_neg_h, const int64_t* d_neg_r, const int64_t* d_neg_t, int64_t n,
+                   float* d_pos_scores, float* d_neg_scores, void* stream);
+
+/* Bytes of d_work for a threshold search over n_pos + n_neg scores (16 + 8 per score); negative for
+ * sizes mmre_tc_threshold refuses. */
+int64_t mmre_tc_threshold_workspace(int64_t n_pos, int64_t n_neg);
+/* The threshold search of get_best_threshlod, without a sort. For a candidate c among the scores
+ * P(c) = #{positives <= c}, A(c) = P(c) + #{negatives <= c}; the rule `score <= c` classifies
+ * (2 P + F - A) of the T = n_pos + n_neg scores correctly (F = n_neg), so the winner maximises the
+ * integer 2 P - A and, among equal maxima, is the smallest c (the reference's strict `>`).
+ *   have_threshold == 0: d_out = {bits of the best threshold (float, low 32 bits), P, A, n_nan}
+ *   have_threshold != 0: the same at `threshold`; no search runs, d_work may be NULL.
+ * The accuracy is mmre_tc_accuracy(P, A, n_pos, n_neg) on the host. (n_pos + n_neg)^2 compares:
+ * quadratic, meant for test sets up to some 10^5 scores. Integer atomics only: identical every run.
+ * Pinned where the reference is undefined or unstable:
+ *   ties   numpy's argsort is unstable, so inside a group of equal scores the reference's running
+ *          value depends on the sort and its res_mx may exceed what any threshold attains; here a
+ *          group counts at its end only. With pairwise-distinct scores both agree exactly. -0 and +0
+ *          are one group, reported as +0.
+ *   NaN    a NaN score is never <= anything: classified negative, never a candidate, counted in T and
+ *          in F or the positives' total, and in n_nan. No non-NaN score at all: threshold NaN, P = A = 0.
+ *   no score above the threshold (the reference's loop leaves `acc` unbound): A = all non-NaN scores.
+ * The lengths may differ (get_best_threshlod is generic in `ans`); either may be 0.
+ * MMRE_ERR_ARG: a negative length, a null array of positive length, a null d_out, a null d_work for a
+ * search; MMRE_ERR_SHAPE: n_pos + n_neg > 2^30; MMRE_ERR_WORKSPACE: work_bytes too small.
+ * n_pos + n_neg == 0: no-op, d_out untouched. */
+int mmre_tc_threshold(const float* d_pos_scores, int64_t n_pos, const float* d_neg_scores, int64_t n_neg,
+                      int have_threshold, float threshold, int64_t* d_out, void* d_work, int64_t work_bytes,
+                      void* stream);
+/* Host: (2 P + F - A) / T in double -- the reference's Python float, bit for bit. NaN for T == 0. */
+double mmre_tc_accuracy(int64_t p, int64_t a, int64_t n_pos, int64_t n_neg);
+
+/* The three stages enqueued in one call: mmre_tc_negatives on the test triples, mmre_tc_scores on
+ * them and their negatives, mmre_tc_threshold over the two score arrays (n_pos = n_neg = n;
+ * d_work >= mmre_tc_threshold_workspace(n, n) unless a threshold is given). Outputs: d_neg_h,
+ * d_neg_t, d_pos_scores, d_neg_scores (n each) and d_out[4]. Checks, in order: mmre_tc_scores',
+ * mmre_tc_negatives', mmre_tc_threshold's. */
+int mmre_tc_evaluate(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                     const float* d_ent_im, const float* d_rel, const float* d_rel_im, int64_t n_ent, int64_t n_rel,
+                     int dim, float phase_denom, const int64_t* d_head_hrt, const int64_t* d_tail_hrt,
+                     const int64_t* d_lef_head, const int64_t* d_rig_head, const int64_t* d_lef_tail,
+                     const int64_t* d_rig_tail, int64_t train_total, const int64_t* d_test_h,
+                     const int64_t* d_test_r, const int64_t* d_test_t, int64_t n, uint64_t state,
+                     int have_threshold, float threshold, int64_t* d_neg_h, int64_t* d_neg_t, float* d_pos_scores,
+                     float* d_neg_scores, int64_t* d_out, void* d_work, int64_t work_bytes, void* stream);
+
+/* ====================================================================== *
  *  OpenKE negative sampler (Base.cpp:78-197 sampling/getBatch,           *
  *  Corrupt.h:7-163 corrupt_head/tail/rel, Random.h:11-29).               *
  *  Bit-exact: each positive's LCG state is reached by affine jump-ahead  *

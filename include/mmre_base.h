@@ -4,11 +4,11 @@
  * absent openke.data loaders call `sampling`). libmmre_base.so exports the same names,
  * argument types (INT = int64 `long`, REAL = float, Setting.h:3-4) and global-state
  * semantics, so a caller switches by loading this library instead of release/Base.so.
- * `sampling` runs the bit-exact GPU sampler (mmre_sampler_openke) and testHead/testTail/testRel
- * rank the caller's score vector on the GPU; everything else is host bookkeeping.
+ * `sampling` runs the bit-exact GPU sampler (mmre_sampler_openke), testHead/testTail/testRel
+ * rank the caller's score vector on the GPU and getNegTest/getTestBatch corrupt the test triples
+ * there (mmre_tc_negatives); everything else is host bookkeeping.
  * Errors the reference would crash on (missing files, out-of-range index) print a message
- * to stderr and abort. Not exported (outside the evaluation path): triple
- * classification (getNegTest/getTestBatch).
+ * to stderr and abort.
  *
  * Deviation from Base.so, on purpose: initTest here ALSO resets the relation-prediction
  * accumulators (with lastRel). The reference's initTest declares shadowing locals for them (Test.h:29), so its
@@ -98,14 +98,27 @@ void test_relation_prediction(void);
  * while an error is latched. */
 void mmre_base_get_rel_metrics(float* out10);
 
+/* Triple classification. Test.h:399-409 -- negTestList: every test triple, in testList order, with
+ * its tail replaced by corrupt_head(0, h, r) when `randd(0) % 1000 < 500`, else its head by
+ * corrupt_tail(0, t, r), filtered against the train lists. Uses work thread 0's state and leaves it
+ * advanced by 2 x testTotal draws, so a second call gives Base.so's second list. Needs
+ * importTrainFiles, importTestFiles and randReset first (an error otherwise). Bit-identical to
+ * Base.so except where Base.so reads outside trainHead / trainTail: a kept entity that never occurs
+ * on that side of a train triple (Corrupt.h then reads row -1) draws rand_max(entityTotal - 2) and
+ * returns the draw unchanged (mmre.h, mmre_tc_negatives). */
+void getNegTest(void);
+/* Test.h:411-422 -- getNegTest, then the testTotal positives and their negatives into caller arrays
+ * of length testTotal each; nr[i] = pr[i]. On an error all six are poisoned with -1. */
+void getTestBatch(int64_t* ph, int64_t* pt, int64_t* pr, int64_t* nh, int64_t* nt, int64_t* nr);
+
 /* Not in Base.so, whose void API crashes on bad input (Reader.h:59-90 ignores fopen
  * failures; OpenKE/README.md:129). Here a failure -- a file that cannot be opened, a test
  * index out of range, type_constrain without importTypeFiles, a HIP error -- prints its
  * message and, by default, abort()s: an unmodified OpenKE caller never checks for errors.
  * mmre_base_set_error_mode(1) (or MMRE_BASE_LATCH_ERRORS=1 in the environment) latches it
  * instead: the failing call returns, every entry point above returns at once while the latch
- * is set, and their outputs are poisoned (sampling / getHeadBatch / getTailBatch / getRelBatch
- * ids -1, batch_y NaN, getTestLink* and mmre_base_get_rel_metrics NaN). mmre_base_last_error returns the code (0: none; mmre.h
+ * is set, and their outputs are poisoned (sampling / getHeadBatch / getTailBatch / getRelBatch /
+ * getTestBatch ids -1, batch_y NaN, getTestLink* and mmre_base_get_rel_metrics NaN). mmre_base_last_error returns the code (0: none; mmre.h
  * MMRE_ERR_*, HIP errors as MMRE_ERR_HIP_BASE + hipError_t) and copies the message into
  * msg[cap]; mmre_base_clear_error resets the latch. */
 void mmre_base_set_error_mode(int latch);

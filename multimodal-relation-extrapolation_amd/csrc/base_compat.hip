@@ -21,12 +21,14 @@
 //                                                              relations of (h, t); advances lastRel
 //   Test.h:329-354     test_relation_prediction                one D2H of the counts, the float accumulation
 //                                                              in call order, the reference's printout
+//   Test.h:393-422     getNegTest, getTestBatch                GPU: mmre_tc_negatives (bit-exact corrupted
+//                                                              copies of the test triples from thread 0's
+//                                                              seed), then D2H into negTestList
 //
 // The per-query rank of Test.h walks all E scores and binary-searches the known-triple
 // list for every better entity (~0.55 ms per query on the host); here it is one small
 // kernel per call whose launch overlaps the caller's next predict. State is global, as in
-// the reference (the ctypes caller owns nothing but its arrays). Triple classification
-// (getNegTest/getTestBatch) is not part of the evaluation path and is not exported.
+// the reference (the ctypes caller owns nothing but its arrays).
 // One deliberate deviation: initTest resets lastRel AND the relation-prediction accumulators
 // (Test.h:29 declares shadowing locals instead, so the reference's rel_* sums survive initTest
 // and a second evaluation in one process adds to stale sums).
@@ -92,6 +94,8 @@ struct State {
   INT last_rel = 0;
   int64_t rel_calls = 0;
   REAL rel_metrics[10] = {};
+  // triple classification: negTestList (Test.h:396), filled by getNegTest
+  std::vector<Trip> neg_test_list;
   REAL hit10 = 0, hit3 = 0, hit1 = 0, mr = 0, mrr = 0;
   REAL hit10_tc = 0, hit3_tc = 0, hit1_tc = 0, mr_tc = 0, mrr_tc = 0;
 };
@@ -124,6 +128,9 @@ struct Device {
   hipEvent_t ev[kRing] = {};
   int32_t* d_counts = nullptr;  // [slot][4]
   int64_t slot_cap = 0;
+  // triple classification: the test list as columns h, r, t and the negatives' h, t
+  bool tc_ready = false;
+  int64_t *d_tc_test = nullptr, *d_tc_neg = nullptr;
 };
 Device D;
 
@@ -572,6 +579,7 @@ static void importTestFiles_impl() {
   printf("The total of test triples is %ld.\n", (long)S.test_total);
   printf("The total of valid triples is %ld.\n", (long)S.valid_total);
   D.test_ready = false;
+  D.tc_ready = false;
 }
 
 static void importTypeFiles_impl() {
@@ -704,6 +712,47 @@ static void test_relation_prediction_impl() {
   const int f_of[5] = {4, 3, 0, 1, 2};  // mrr, mr, hit10, hit3, hit1
   for (int g = 0; g < 2; ++g)            // filter, raw
     for (int m = 0; m < 5; ++m) S.rel_metrics[5 * g + m] = acc[1 - g][f_of[m]];
+}
+
+// getNegTest (Test.h:399-409): one corrupted copy of every test triple from thread 0's seed, which
+// advances by two draws per triple. The kernel samples all triples in parallel (mmre_tc_negatives).
+static void getNegTest_impl() {
+  if (S.train_head.empty()) fail(MMRE_ERR_ARG, "getNegTest: call importTrainFiles() first");
+  if (S.test_list.empty()) fail(MMRE_ERR_ARG, "getNegTest: call importTestFiles() first");
+  if (S.seeds.empty()) fail(MMRE_ERR_ARG, "getNegTest: call randReset() first");
+  if (S.lef_head.size() != (size_t)S.ent_total)
+    fail(MMRE_ERR_ARG, "getNegTest: the train and test files disagree on the total of entities");
+  train_device();
+  const int64_t n = (int64_t)S.test_list.size();
+  if (!D.tc_ready) {
+    HIP_OR_DIE(hipStreamSynchronize(D.st));
+    release(D.d_tc_test);
+    release(D.d_tc_neg);
+    D.d_tc_test = D.d_tc_neg = nullptr;
+    std::vector<int64_t> cols((size_t)(3 * n));
+    for (int64_t i = 0; i < n; ++i) {
+      cols[(size_t)i] = S.test_list[(size_t)i].h;
+      cols[(size_t)(n + i)] = S.test_list[(size_t)i].r;
+      cols[(size_t)(2 * n + i)] = S.test_list[(size_t)i].t;
+    }
+    D.d_tc_test = upload(cols);
+    HIP_OR_DIE(hipMalloc(&D.d_tc_neg, sizeof(int64_t) * 2 * n));
+    HIP_OR_DIE(hipStreamSynchronize(D.st));
+    D.tc_ready = true;
+  }
+  const int rc = mmre_tc_negatives(D.d_head, D.d_tail, D.d_lh, D.d_rh, D.d_lt, D.d_rt, (int64_t)S.train_head.size(),
+                                   S.ent_total, D.d_tc_test, D.d_tc_test + n, D.d_tc_test + 2 * n, n,
+                                   (uint64_t)S.seeds[0], D.d_tc_neg, D.d_tc_neg + n, D.st);
+  if (rc != MMRE_OK) fail(rc, "mmre_tc_negatives failed (" + std::to_string(rc) + ")");
+  std::vector<int64_t> neg((size_t)(2 * n));
+  HIP_OR_DIE(hipMemcpyAsync(neg.data(), D.d_tc_neg, sizeof(int64_t) * 2 * n, hipMemcpyDeviceToHost, D.st));
+  HIP_OR_DIE(hipStreamSynchronize(D.st));
+  S.neg_test_list = S.test_list;
+  for (int64_t i = 0; i < n; ++i) {
+    S.neg_test_list[(size_t)i].h = neg[(size_t)i];
+    S.neg_test_list[(size_t)i].t = neg[(size_t)(n + i)];
+  }
+  S.seeds[0] = (unsigned long long)mmre_tc_advance((uint64_t)S.seeds[0], n);
 }
 
 static void getHeadBatch_impl(INT* ph, INT* pt, INT* pr) {
@@ -885,6 +934,26 @@ extern "C" void testRel(REAL* con) {
 
 extern "C" void test_relation_prediction() {
   guarded([&] { test_relation_prediction_impl(); });
+}
+
+extern "C" void getNegTest() {
+  guarded([&] { getNegTest_impl(); });
+}
+
+extern "C" void getTestBatch(INT* ph, INT* pt, INT* pr, INT* nh, INT* nt, INT* nr) {
+  const bool ok = guarded([&] {
+    getNegTest_impl();
+    for (size_t i = 0; i < S.test_list.size(); ++i) {
+      ph[i] = S.test_list[i].h;
+      pt[i] = S.test_list[i].t;
+      pr[i] = S.test_list[i].r;
+      nh[i] = S.neg_test_list[i].h;
+      nt[i] = S.neg_test_list[i].t;
+      nr[i] = S.neg_test_list[i].r;
+    }
+  });
+  if (!ok)
+    for (INT* p : {ph, pt, pr, nh, nt, nr}) poison<INT>(p, S.test_total, -1);
 }
 
 extern "C" void mmre_base_get_rel_metrics(float* out10) {

@@ -151,6 +151,18 @@ static uint64_t lcg_pow_apply(uint64_t x, uint64_t n) {
   return A * x + C;
 }
 
+// getNegTest (Test.h:399-409) draws thread 0's LCG twice per test triple: the coin, the corruption.
+extern "C" uint64_t mmre_tc_advance(uint64_t state, int64_t n) {
+  return n > 0 ? lcg_pow_apply(state, 2ULL * (uint64_t)n) : state;
+}
+
+// Tester.py:108 / :146: (2 * total_current + total_false - index) / total_all in Python floats;
+// every operand is an integer a double holds exactly, so one double division reproduces it.
+extern "C" double mmre_tc_accuracy(int64_t p, int64_t a, int64_t n_pos, int64_t n_neg) {
+  const double total = (double)(n_pos + n_neg);
+  return (2.0 * (double)p + (double)n_neg - (double)a) / total;
+}
+
 extern "C" int mmre_sampler_advance(uint64_t* h_seeds, int64_t work_threads, int64_t batch_size, int64_t neg_rate,
                                     int64_t neg_rel_rate, int64_t mode) {
   if (!h_seeds || work_threads <= 0 || batch_size <= 0 || neg_rate < 0 || neg_rel_rate < 0) return MMRE_ERR_ARG;

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("MMRE_LIB") or os.path.join(LIB_DIR, "libmmre_hip.so")
 
 P = ctypes.c_void_p
 I64 = ctypes.c_int64
+U64 = ctypes.c_uint64
 I32 = ctypes.c_int
 F32 = ctypes.c_float
 
@@ -61,6 +62,14 @@ SIGNATURES = {
     "mmre_rel_evaluate": (I32, [I32, I32, I32, F32, P, P, P, P, I64, I64, I32, F32, P, P, P, I64, P, P, P, P, P, P,
                                 I64, P]),
     "mmre_rel_metrics": (I32, [P, I64, I64, P]),
+    "mmre_tc_negatives": (I32, [P, P, P, P, P, P, I64, I64, P, P, P, I64, U64, P, P, P]),
+    "mmre_tc_advance": (U64, [U64, I64]),
+    "mmre_tc_scores": (I32, [I32, I32, I32, F32, P, P, P, P, I64, I64, I32, F32, P, P, P, P, P, P, I64, P, P, P]),
+    "mmre_tc_threshold_workspace": (I64, [I64, I64]),
+    "mmre_tc_threshold": (I32, [P, I64, P, I64, I32, F32, P, P, I64, P]),
+    "mmre_tc_accuracy": (ctypes.c_double, [I64, I64, I64, I64]),
+    "mmre_tc_evaluate": (I32, [I32, I32, I32, F32, P, P, P, P, I64, I64, I32, F32, P, P, P, P, P, P, I64, P, P, P,
+                               I64, U64, I32, F32, P, P, P, P, P, P, I64, P]),
     "mmre_glibc_rand": (I32, [I64, I64, P]),
     "mmre_sampler_advance": (I32, [P, I64, I64, I64, I64, I64]),
     "mmre_sampler_advance_device": (I32, [P, I64, I64, I64, I64, I64, P]),

@@ -33,6 +33,7 @@ SIGNATURES = {
     "getTestLinkMR": (_F, [_I]), "getTestLinkMRR": (_F, [_I]),
     "getRelBatch": (None, [_P, _P, _P]), "testRel": (None, [_P]), "test_relation_prediction": (None, []),
     "mmre_base_get_rel_metrics": (None, [_P]),
+    "getNegTest": (None, []), "getTestBatch": (None, [_P, _P, _P, _P, _P, _P]),
     "mmre_base_last_error": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]), "mmre_base_clear_error": (None, []),
     "mmre_base_set_error_mode": (None, [ctypes.c_int]),
 }

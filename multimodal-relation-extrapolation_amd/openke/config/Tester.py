@@ -6,11 +6,15 @@ tail-batch sweep of the test set against every entity, filtered and type-constra
 counted in the sweep's epilogue, then the Test.h metric reduction (test_link_prediction,
 Test.h:232-327) with the reference's float order. Returns (mrr, mr, hit10, hit3, hit1) like
 the reference. run_relation_prediction does the same for the reference's relation-prediction
-loop (getRelBatch -> predict -> testRel, Test.h:55-62, :194-228, :329-354)."""
+loop (getRelBatch -> predict -> testRel, Test.h:55-62, :194-228, :329-354), and
+run_triple_classification for getTestBatch -> predict on both batches -> get_best_threshlod
+(Test.h:393-422, Tester.py:93-151): negatives, both score arrays and the sort-free threshold search
+in one fused call (mmre.tripleclass)."""
 import numpy as np
 import torch
 
 from mmre.link import evaluate_link_prediction, evaluate_relation_prediction
+from mmre.tripleclass import best_threshold, evaluate_triple_classification
 
 
 class Tester(object):
@@ -83,5 +87,29 @@ class Tester(object):
         grp = metrics["filter"]
         return grp["mrr"], grp["mr"], grp["hit10"], grp["hit3"], grp["hit1"]
 
+    def get_best_threshlod(self, score, ans):
+        """Tester.py:93-112 (the reference's spelling): the threshold of the best accuracy of the rule
+        `score <= threshlod`, and that accuracy. score, ans: arrays of equal length, ans == 1 marking the
+        positives. The search runs on the GPU (mmre_tc_threshold); with tied scores the accuracy is
+        the one the rule attains (include/mmre.h). (None, 0.0), as the reference's walk from res_mx = 0.0
+        gives, when no threshold classifies anything correctly."""
+        score = np.asarray(score, np.float32).reshape(-1)
+        ans = np.asarray(ans).reshape(-1)
+        res = best_threshold(score[ans == 1], score[ans != 1])
+        if res["threshold"] != res["threshold"] or not res["accuracy"] > 0.0:
+            return None, 0.0
+        return res["threshold"], res["accuracy"]
+
     def run_triple_classification(self, threshlod=None):
-        raise NotImplementedError("triple classification is outside the MI355X hot path (SURVEY.md §2 row 7)")
+        """Tester.py:114-151 as ONE fused evaluation (mmre.tripleclass.evaluate_triple_classification):
+        the loader's test list, its negatives from the loader's thread-0 state (which advances as a
+        'classification' pass of the loader does), predict on both, and the best threshold -- or the
+        accuracy at the given one. Returns (acc, threshlod); self.last keeps the negatives, both score
+        arrays and the counts."""
+        dl = self.data_loader
+        dl.set_sampling_mode("classification")
+        res = evaluate_triple_classification(self.model.score_spec(), dl.test_h, dl.test_r, dl.test_t,
+                                             dl.train_index(), dl.get_seed_state(), threshold=threshlod)
+        dl.set_seed_state(res["seed_state_after"])
+        self.last = res
+        return res["accuracy"], res["threshold"]
