@@ -497,14 +497,14 @@ struct L1Q {
   const int32_t* tile_m;
   const int32_t* n_rows;
   // per-query route (the fused evaluation): the 8-bit sweeps leave out a query whose
-  // byte in `routed` is set (nullptr: no route); the indexed f32 sweep (IDX) counts queries
-  // route_list[0 .. *route_n) instead
+  // byte in `routed` is set (nullptr: no route); k_heavy_rows counts the routed list's queries
+  // instead
   const uint8_t* routed;
-  const int32_t* route_list;
-  const uint32_t* route_n;
+  const int32_t* route_list;  // (unused since k_heavy_rows takes the list itself; kept so that the
+  const uint32_t* route_n;    // sweeps' kernel argument, and with it their code, stays as measured)
 };
 // Header words of the route's record (zeroed with the header by K1, written by k_l1q_route_compact):
-// flagged queries, routed queries (the indexed sweep's row count), sampled columns, flag threshold
+// flagged queries, routed queries (k_heavy_rows' query count), sampled columns, flag threshold
 constexpr int L1Q_ROUTE_W = 8;
 // The sweeps' dynamic-scheduling work counters (L1Q::wq): one per XCD group, each on a 128-B
 // line of its own -- the second half of an undecided-pair counter slot (L1Q_SLOT_STRIDE bytes
@@ -1031,9 +1031,7 @@ struct ValuSmem : ValuSmemGrp<GS> {
 // The sweep body. Counts go to the raw columns only (counts[0][q], counts[2][q]); the filtered
 // columns (initialised to minus the listed entities that beat the truth by the truth pass)
 // receive them in k_counts_finalize, one coalesced pass after the sweep (half the atomics).
-// IDX (the per-query route's f32 sweep): query row i of the sweep is query
-// l1.route_list[i], i < *l1.route_n -- the row count is the device's, as the grouped sweep's.
-template <int OP, bool TC, bool STORE, int PK, int NPL, int DYNC, int GS = 0, bool IDX = false>
+template <int OP, bool TC, bool STORE, int PK, int NPL, int DYNC, int GS = 0>
 __device__ __forceinline__ void sweep_valu_body(
     ValuSmem<NPL, TC, (OP == 5 || OP == 6), GS>& sm, const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent,
     const float* __restrict__ q_km, int64_t q_pad, int64_t n_query, int kp, int n_et, int e_base, int n_groups,
@@ -1050,8 +1048,6 @@ __device__ __forceinline__ void sweep_valu_body(
   // thresholds in turn (the slot loop of the epilogue); see ValuSmemGrp and k_eval_prep's row map
   constexpr bool GRP = GS > 0;
   static_assert(!GRP || (L1F && PK == 0 && !TC && !STORE), "the grouped sweep is the plain integer filter's");
-  static_assert(!IDX || (OP == 0 && PK == 0 && !TC && !STORE && DYNC == 0 && !GRP),
-                "the indexed sweep is the plain f32 one");
   auto& sq = sm.sq;
   auto& se = sm.se;
   auto& s_thr = sm.s_thr;
@@ -1075,11 +1071,7 @@ __device__ __forceinline__ void sweep_valu_body(
   const int grp = blockIdx.x % n_groups, gmem = blockIdx.x / n_groups;
   const int per_grp = gridDim.x / n_groups;
   // (grouped: the row tiles, known on the device only)
-  // (indexed: the routed queries, none when the route did not act)
-  const int n_idx = IDX ? __builtin_amdgcn_readfirstlane((int)*l1.route_n) : 0;
-  const int n_qt = IDX   ? (n_idx + TQ - 1) / TQ
-                   : GRP ? __builtin_amdgcn_readfirstlane(l1.n_rows[GRP ? 1 : 0]) / TQ
-                         : (int)(q_pad / TQ);
+  const int n_qt = GRP ? __builtin_amdgcn_readfirstlane(l1.n_rows[GRP ? 1 : 0]) / TQ : (int)(q_pad / TQ);
   const UnitMap um(grp, n_groups, n_qt, n_et);
   const int nkc = kp / KC;
   // (compiled per mode and chunk: a runtime choice between the modes, or a runtime chunk size,
@@ -1112,12 +1104,8 @@ __device__ __forceinline__ void sweep_valu_body(
   auto load_meta = [&](int qtile, int slot) {
     const int tid = vgpr_opaque(threadIdx.x);
     if (tid < TQ) {
-      int64_t q = (int64_t)qtile * TQ + tid;
-      bool v = q < n_query;
-      if constexpr (IDX) {  // row tid of the tile is routed query route_list[q]
-        v = q < (int64_t)n_idx;
-        q = v ? l1.route_list[q] : 0;
-      }
+      const int64_t q = (int64_t)qtile * TQ + tid;
+      const bool v = q < n_query;
       const float th = v ? thr[q] : -INFINITY;
       s_thr[slot][tid] = th;
       s_true[slot][tid] = v ? qtrue[q] : -1;
@@ -1136,7 +1124,7 @@ __device__ __forceinline__ void sweep_valu_body(
         l1_int_thresholds(th, tight ? (v ? l1.q_l1c[q] : 0.0f) + 0x1p-120f : mc, md, mf, tight ? 2u * l1.hdr[3] : 0u,
                           t_sure, t_span);
         if constexpr (w8) {
-          // a routed query (the indexed f32 sweep counts it): no sure pair, no band, as a padding row
+          // a routed query (k_heavy_rows counts it): no sure pair, no band, as a padding row
           if (l1.routed != nullptr && v && l1.routed[q]) t_sure = t_span = 0u;
         }
         sm.s_ts[slot][tid] = t_sure;
@@ -1184,7 +1172,7 @@ __device__ __forceinline__ void sweep_valu_body(
         }
       }
       if constexpr (w8) {
-        // a routed member (the indexed f32 sweep counts it) becomes an empty slot. A round of its
+        // a routed member (k_heavy_rows counts it) becomes an empty slot. A round of its
         // own, before the thresholds': with the bytes in flight beside the thresholds the tile's
         // 64 accumulators no longer fit (8 VGPRs spilled); once per row tile.
         if (l1.routed != nullptr) {
@@ -1221,7 +1209,6 @@ __device__ __forceinline__ void sweep_valu_body(
   uint32_t rt0 = 0u, rt1 = 0u;
   bool st_new = false;
   int ld_tpar = 1, st_par = 0, ep_par = 0;
-  [[maybe_unused]] int iq0 = 0, iq1 = 0, iq2 = 0, iq3 = 0;  // indexed sweep: the staged unit's four query ids
   auto gload = [&]() {
     if constexpr (TC) {
       st_new = ld_kc == 0;
@@ -1246,22 +1233,7 @@ __device__ __forceinline__ void sweep_valu_body(
     const int64_t q0 = (int64_t)ld_qt * TQ, e0 = (int64_t)ld_et * TE;
     const float* qp = q_km + (int64_t)k * q_pad + q0 + sc4 * 4;
     const float* ep = ent_km + (int64_t)k * e_pad + e0 + sc4 * 4;
-    if constexpr (IDX) {
-      // the thread's four query columns through the routed list (rows past it: column 0, never
-      // counted); the ids are read at a unit's first stage and kept -- read at every stage they
-      // put a second dependent load in front of each stage's (the sweep 82 us at C2)
-      if (ld_kc == 0) {
-        const int p0 = (int)q0 + sc4 * 4;
-        iq0 = p0 + 0 < n_idx ? l1.route_list[p0 + 0] : 0;
-        iq1 = p0 + 1 < n_idx ? l1.route_list[p0 + 1] : 0;
-        iq2 = p0 + 2 < n_idx ? l1.route_list[p0 + 2] : 0;
-        iq3 = p0 + 3 < n_idx ? l1.route_list[p0 + 3] : 0;
-      }
-      const float* qk = q_km + (int64_t)k * q_pad;
-      rq0 = make_float4(qk[iq0], qk[iq1], qk[iq2], qk[iq3]);
-    } else {
-      rq0 = *reinterpret_cast<const float4*>(qp);
-    }
+    rq0 = *reinterpret_cast<const float4*>(qp);
     re0 = *reinterpret_cast<const float4*>(ep);
     if constexpr (NPL == 2) {
       rq1 = *reinterpret_cast<const float4*>(qp + (int64_t)kp * q_pad);
@@ -1840,12 +1812,8 @@ __device__ __forceinline__ void sweep_valu_body(
               if constexpr (TC) cc += __shfl_xor(cc, sh);
             }
             const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-            int64_t q = q0 + ql;
-            bool vq = q < n_query;
-            if constexpr (IDX) {
-              vq = q < (int64_t)n_idx;
-              q = (vq && te == 0) ? l1.route_list[q] : 0;
-            }
+            const int64_t q = q0 + ql;
+            const bool vq = q < n_query;
             if (te == 0 && vq) {  // raw columns only: k_counts_finalize adds them to the filtered ones
               if (c) atomicAdd(&counts[q], c);
               if constexpr (TC) {
@@ -1893,7 +1861,7 @@ __device__ __forceinline__ void sweep_valu_body(
   }
 }
 
-template <int OP, bool TC, bool STORE, int PK, int DYNC = 0, int GS = 0, bool IDX = false>
+template <int OP, bool TC, bool STORE, int PK, int DYNC = 0, int GS = 0>
 __global__ __launch_bounds__(NT, (OP == 2) ? 3 : 4) void k_sweep_valu(
     const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent, const float* __restrict__ q_km,
     int64_t q_pad, int64_t n_query, int kp, int n_et, int e_base, int n_groups, int pred_kind, float margin,
@@ -1921,9 +1889,9 @@ __global__ __launch_bounds__(NT, (OP == 2) ? 3 : 4) void k_sweep_valu(
       return;
     }
   }
-  sweep_valu_body<OP, TC, STORE, PK, NPL, DYNC, GS, IDX>(sm, ent_km, e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base,
-                                          n_groups, pred_kind, margin, thr, qtrue, qr, qmode, type_head, type_tail,
-                                          type_words, counts, scores, l1);
+  sweep_valu_body<OP, TC, STORE, PK, NPL, DYNC, GS>(sm, ent_km, e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base,
+                                                    n_groups, pred_kind, margin, thr, qtrue, qr, qmode, type_head, type_tail,
+                                                    type_words, counts, scores, l1);
   if (l1.gate != nullptr && l1.fin_counts != nullptr) {
     // open (the rare f32 fallback): the finalize after every workgroup's counts, by the last
     // workgroup (each wave's count atomics drained, then ONE ticket add per workgroup)
@@ -1953,6 +1921,84 @@ __global__ __launch_bounds__(256) void k_counts_finalize(int32_t* __restrict__ c
   if (q >= n_query) return;
   counts[n_query + q] += counts[q];
   if (tc) counts[3 * n_query + q] += counts[2 * n_query + q];
+}
+
+// ---------------------------------------------------------- routed rows ---
+// The per-query route's exact kernel: queries route_list[0 .. *route_n) against
+// every entity of the slice, the canonical chain per pair (op_step<0>, k ascending over the kp
+// rows from 0.0f), the sweep epilogue's three conditions, raw counts by integer atomics. The
+// routed queries are few (C2: 122), so the 128 x 128 unit of the sweep left most of the machine
+// idle and cost by the row tile; here a unit is HR_QB routed queries x HR_TE entity columns:
+// a thread owns one column (the k-major loads coalesce along the entity axis) and HR_QB chains,
+// so a loaded entity value feeds HR_QB chains. The query operand comes from the row-major
+// q_rows through wave-uniform ids: scalar loads, no LDS stage. The host sizes the grid from the
+// list's cap; the units come from the device's count, a workgroup without one leaves, and an
+// inert route (count 0) changes nothing.
+constexpr int HR_TE = 128;  // entity columns per unit (= TE: e_cols is whole units)
+constexpr int HR_QB = 16;   // routed queries per unit
+constexpr int HR_KU = 8;    // k rows per stage (= KC: kp is whole stages), the next stage's loads in flight
+static_assert(HR_TE == TE && HR_KU == KC && HR_TE % 64 == 0 && HR_QB <= HR_TE, "routed rows' unit");
+__global__ __launch_bounds__(HR_TE) void k_heavy_rows(
+    const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent, int n_et, int e_base,
+    const float* __restrict__ q_rows, int kp, const float* __restrict__ thr, const int32_t* __restrict__ qtrue,
+    const int32_t* __restrict__ route_list, const uint32_t* __restrict__ route_n, int32_t* __restrict__ counts) {
+  __shared__ int s_cnt[HR_TE / 64][HR_QB];
+  const int tid = threadIdx.x;
+  const int n_idx = __builtin_amdgcn_readfirstlane((int)*route_n);
+  const int n_qb = (n_idx + HR_QB - 1) / HR_QB;
+  const int64_t units = (int64_t)n_qb * n_et;
+  // entity-tile major: neighbouring workgroups read the same columns
+  for (int64_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
+    const int et = (int)(unit / n_qb), p0 = (int)(unit % n_qb) * HR_QB;
+    // the unit's queries (uniform); a slot past the list repeats the unit's first query and
+    // never counts (threshold -inf)
+    const float* qp[HR_QB];
+    float th[HR_QB];
+    int32_t tr[HR_QB];
+#pragma unroll
+    for (int i = 0; i < HR_QB; ++i) {
+      const bool v = p0 + i < n_idx;
+      const int q = __builtin_amdgcn_readfirstlane(route_list[v ? p0 + i : p0]);
+      qp[i] = q_rows + (int64_t)q * kp;
+      th[i] = v ? thr[q] : -INFINITY;
+      tr[i] = qtrue[q];
+    }
+    const int e = et * HR_TE + tid;
+    const float* ep = ent_km + e;
+    float acc[HR_QB];
+#pragma unroll
+    for (int i = 0; i < HR_QB; ++i) acc[i] = 0.0f;
+    float ev[HR_KU], en[HR_KU];
+#pragma unroll
+    for (int u = 0; u < HR_KU; ++u) ev[u] = en[u] = ep[(int64_t)u * e_pad];
+    for (int k0 = 0; k0 < kp; k0 += HR_KU) {
+      if (k0 + HR_KU < kp) {
+#pragma unroll
+        for (int u = 0; u < HR_KU; ++u) en[u] = ep[(int64_t)(k0 + HR_KU + u) * e_pad];
+      }
+#pragma unroll
+      for (int u = 0; u < HR_KU; ++u)
+#pragma unroll
+        for (int i = 0; i < HR_QB; ++i) acc[i] = op_step<0>(acc[i], qp[i][k0 + u], 0.0f, ev[u], 0.0f);
+#pragma unroll
+      for (int u = 0; u < HR_KU; ++u) ev[u] = en[u];
+    }
+    // the sweep epilogue's conditions; a wave's count per query is one ballot
+#pragma unroll
+    for (int i = 0; i < HR_QB; ++i) {
+      const bool better = (op_final<0>(acc[i]) < th[i]) & (e + e_base != tr[i]) & (e < n_ent);
+      const int c = __popcll(__ballot(better));
+      if ((tid & 63) == 0) s_cnt[tid >> 6][i] = c;
+    }
+    __syncthreads();
+    if (tid < HR_QB && p0 + tid < n_idx) {  // one add per (workgroup, query), raw column only
+      int c = 0;
+#pragma unroll
+      for (int w = 0; w < HR_TE / 64; ++w) c += s_cnt[w][tid];
+      if (c) atomicAdd(&counts[route_list[p0 + tid]], c);
+    }
+    __syncthreads();  // the next unit's ballots overwrite s_cnt
+  }
 }
 
 // ------------------------------------------------------------ MFMA sweep ---
@@ -4322,7 +4368,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_quant_list(EvalL1 P, EvalQuant 
 // the row costs ~4.3. K3's third block range scores every sweep row against one fixed sample of
 // entity columns and flags a member whose band holds L1Q_HEAVY_FRAC of the sample or more;
 // k_l1q_route_compact lists the flagged queries (query order, capped); the 8-bit sweeps leave a
-// listed query out (load_meta / load_meta_grp) and the indexed f32 sweep counts it. Counts are the
+// listed query out (load_meta / load_meta_grp) and k_heavy_rows counts it exactly. Counts are the
 // same either way: the route only decides which exact method counts a query.
 // The sample: four windows of 64 columns, their starts spread evenly over the slice (lane l: window
 // l / 16, columns 4 (l % 16) .. + 3 of it) -- the same for every row, staged in LDS L1Q_HEAVY_KCH
@@ -5371,18 +5417,16 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   int rc = grouped ? launch_valu_grp<6>(C8, l1, rows_max) : launch_valu<6>(C8, l1, false);
   if (!rc) rc = grouped ? launch_valu_grp<5>(C16, l16, rows_max) : launch_valu<5>(C16, l16, false);
   if (rc) return rc;
-  // the routed queries' exact f32 sweep, before the launch that carries the finalize: the grid from
-  // the cap, the row tiles from the device's count (workgroups without a unit leave at once)
+  // the routed queries' exact kernel, before the launch that carries the finalize: the grid from
+  // the cap (eight two-wave workgroups per CU at most; a workgroup walks the units of its stride),
+  // the units from the device's count (workgroups without a unit leave at once)
   if (heavy && route_cap > 0) {
-    L1Q lr{};
-    lr.route_list = R.list;
-    lr.route_n = WQ.hdr + L1Q_ROUTE_W + 1;
-    const void* kh = (const void*)k_sweep_valu<0, false, false, 0, 0, 0, true>;
-    const int64_t units = sweep_units(((int64_t)route_cap + TQ - 1) / TQ, C.n_et);
-    const int g = (int)std::max<int64_t>(1, std::min<int64_t>(resident_groups(kh, NT), units));
-    hipLaunchKernelGGL((k_sweep_valu<0, false, false, 0, 0, 0, true>), dim3((unsigned)g), dim3(NT), 0, st, C.ent, C.e_pad,
-                       C.n_slice, C.q, C.q_pad, C.n_query, C.kp, C.n_et, C.e_base, xcd_groups(g, C.n_et), 0, 0.0f,
-                       C.truth, C.q_true, nullptr, nullptr, nullptr, nullptr, (int64_t)0, C.counts, nullptr, lr);
+    const int64_t units = (((int64_t)route_cap + HR_QB - 1) / HR_QB) * C.n_et;
+    const int g = (int)std::max<int64_t>(
+        1, std::min<int64_t>(2 * (int64_t)resident_groups((const void*)k_heavy_rows, HR_TE), units));
+    hipLaunchKernelGGL(k_heavy_rows, dim3((unsigned)g), dim3(HR_TE), 0, st, C.ent, C.e_pad, C.n_slice, C.n_et, C.e_base,
+                       d_q_rows, C.kp, C.truth, C.q_true, (const int32_t*)R.list,
+                       (const uint32_t*)(WQ.hdr + L1Q_ROUTE_W + 1), C.counts);
     MMRE_CHECK_LAUNCH();
   }
   // the f32 fallback, gated on the word; it also carries the finalize (filtered += raw)
