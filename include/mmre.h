@@ -247,8 +247,13 @@ int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t n_ent, con
  * model without the filter). */
 int64_t mmre_link_bf3_workspace(int model, int dim, int64_t e_pad, int64_t q_pad);
 /* The filter's record of the last mmre_link_sweep_bf3 on d_work (one tiny launch, no
- * synchronisation): d_out[0] = pairs listed for exact rescoring, d_out[1] = 1 if the list
- * overflowed and the exact f32 sweep counted instead. */
+ * synchronisation), four words: d_out[0] = pairs listed for exact rescoring, d_out[1] = 1 if the
+ * list overflowed and the exact f32 sweep counted instead, d_out[2] = the appends a full segment
+ * sent to the list's shared half (those past its end included: they set d_out[1]), d_out[3] = the
+ * path record of that sweep as launched: bits 0-15 the wide sweep's query tile (256 / 128; 0: the
+ * 128 x 128 sweep), bit 16 set if it ran the lock-step windows (env MMRE_BF3_BLOCKED=1 / 0 asks
+ * for them or not, read per call; they need >= 8 entity tiles and a resident grid that is a
+ * multiple of 8). */
 int mmre_link_bf3_stats(const void* d_work, int64_t work_bytes, uint64_t* d_out, void* stream);
 int mmre_link_sweep_bf3(int model, int pred_kind, float margin, const float* d_ent_km, const float* d_ent_rows,
                         int64_t n_ent, int64_t e_pad, int64_t e_begin, int64_t e_end, const float* d_q_km,

@@ -1784,7 +1784,11 @@ __device__ __forceinline__ void sweep_valu_body(
         const bool last = unit_next >= u1;
         int next_qt = cur_qt, next_et = cur_et;
         if (!last) um.at(unit_next, next_qt, next_et);
-        // (TC: 16-bit counters -- flush every unit where a group's query tile could exceed them)
+        // (TC: 16-bit counters, up to 8 per unit, so 8,191 units -- flush every unit where the units
+        // of one query tile that an XCD group owns, all of which one workgroup may sweep back to
+        // back, could exceed them: um.m = n_et / n_groups whole tiles and, when the leftover units
+        // that follow start in that query tile, up to 7 more (UnitMap); n_groups is 1 for a grid
+        // that is no multiple of 8)
         if constexpr (GRP) {
           if (last || next_qt != cur_qt) {  // uniform: flush this row tile's member counts
             __syncthreads();  // every wave's adds of this unit are in, and its threshold reads done
@@ -1800,7 +1804,7 @@ __device__ __forceinline__ void sweep_valu_body(
             if (!last) cur_m = load_meta_grp(next_qt);  // visible after the stage's barrier below
           }
         } else
-        if (last || next_qt != cur_qt || (TC && n_et > 8 * 8190)) {  // uniform: flush this query tile's counts
+        if (last || next_qt != cur_qt || (TC && um.m > 8184)) {  // uniform: flush this query tile's counts
           const int tid = vgpr_opaque(threadIdx.x);  // (see load_meta)
           const int tq = tid >> 4, te = tid & 15;
 #pragma unroll
@@ -2642,8 +2646,10 @@ static int l1q_rows8(int dim) { return (int)round_up((plane_rows(MMRE_TRANSE_L1,
 // in the list. A list that overflows its capacity sets a flag on the device: the raw counts
 // are reset and the exact f32 sweep runs instead (gated launches, no host round trip).
 // Workspace: header (BF3_HDR bytes of 32-bit words: word 1 the overflow flag, word 4 the segment
-// capacity, the list's append counters from word BF3_SEG_W0 on, one per 128-B line: segment s at
-// BF3_SEG_W0 + 32 s, the shared half's at s = BF3_SEGS) | pair list (bf3_cap int2) | |q| (q_pad
+// capacity, word 5 the path record of the sweep as launched (bits 0-15 the wide sweep's query
+// tile, 0 for the 128 x 128 sweep; bit 16 the lock-step windows: Bf3Grid::blk), the list's append
+// counters from word BF3_SEG_W0 on, one per 128-B line: segment s at BF3_SEG_W0 + 32 s, the shared
+// half's at s = BF3_SEGS) | pair list (bf3_cap int2, padded to 16 B) | |q| (q_pad
 // floats) | |e| (e_pad floats) | split query planes (K/16 blocks x q_pad rows x 64 B: hi[16] |
 // lo[16]) | split entity planes (K/16 x e_pad x 64 B) | the wide sweep's operands (Bf3Work).
 // The list: half of it cut into BF3_SEGS segments of cap / (2 BF3_SEGS) pairs, each with its own
@@ -3483,10 +3489,11 @@ __global__ __launch_bounds__(256) void k_bf3_rescore(const uint32_t* __restrict_
   }
 }
 
-// the list header zeroed, with word 4 = the segment capacity (read by k_bf3_stats)
-__global__ __launch_bounds__(256) void k_bf3_hdr_init(uint32_t* __restrict__ hdr, int64_t cap) {
+// the list header zeroed, with word 4 = the segment capacity and word 5 = the path record (both
+// read by k_bf3_stats)
+__global__ __launch_bounds__(256) void k_bf3_hdr_init(uint32_t* __restrict__ hdr, int64_t cap, uint32_t path) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < BF3_HDR / 4; i += gridDim.x * blockDim.x)
-    hdr[i] = i == 4 ? (uint32_t)(cap / (2 * BF3_SEGS)) : 0u;
+    hdr[i] = i == 4 ? (uint32_t)(cap / (2 * BF3_SEGS)) : i == 5 ? path : 0u;
 }
 
 __global__ void k_bf3_stats(const uint32_t* __restrict__ hdr, unsigned long long* __restrict__ out) {
@@ -3503,6 +3510,8 @@ __global__ void k_bf3_stats(const uint32_t* __restrict__ hdr, unsigned long long
   if (threadIdx.x == 0) {
     out[0] = t + hdr[BF3_SEG_W0 + 32 * BF3_SEGS];
     out[1] = hdr[1];
+    out[2] = hdr[BF3_SEG_W0 + 32 * BF3_SEGS];  // the shared half's appends
+    out[3] = hdr[5];                           // the path record (k_bf3_hdr_init)
   }
 }
 
@@ -5001,7 +5010,7 @@ static int64_t bf3_layout(Bf3Work& W, int64_t ktot, int64_t e_pad, int64_t q_pad
   Carver w{(char*)base};
   W.cap = bf3_cap(q_pad, e_pad);
   W.hdr = w.take<uint32_t>(BF3_HDR);
-  W.pairs = w.take<int2>(8 * W.cap);
+  W.pairs = w.take<int2>((8 * W.cap + 15) & ~(int64_t)15);  // (an odd MMRE_BF3_CAP: the planes stay 16-B aligned)
   W.qn = w.take<float>(4 * q_pad);
   W.en = w.take<float>(4 * e_pad);
   W.qb = w.take<uint4>(4 * ktot * q_pad);
@@ -5030,13 +5039,18 @@ extern "C" int mmre_link_bf3_stats(const void* d_work, int64_t work_bytes, uint6
 // lock-step windows where the planes overflow the caches (as k_sweep_bf3's), else contiguous
 // unit ranges.
 template <int QT>
-static void launch_bf3w(const SweepCall& C, const Bf3Work& W, int nkb, int emajor, bool blocked) {
+static Bf3Grid grid_bf3w(const SweepCall& C, bool blocked) {
   using G = W3Geom<QT>;
   const int n_etw = (int)((C.n_slice + W3E - 1) / W3E);
   const int res = resident_groups((const void*)k_sweep_bf3w<2, QT, true>, G::NT);
   const int64_t units = (C.q_pad / QT) * (int64_t)n_etw;
   const int g_ranges = (int)std::min<int64_t>(8LL * res, std::max<int64_t>((int64_t)res, units / 16)) & ~7;
-  const Bf3Grid B = bf3_grid(g_ranges, res, blocked, (int)(C.q_pad / QT), n_etw);
+  return bf3_grid(g_ranges, res, blocked, (int)(C.q_pad / QT), n_etw);
+}
+template <int QT>
+static void launch_bf3w(const SweepCall& C, const Bf3Work& W, int nkb, int emajor, const Bf3Grid& B) {
+  using G = W3Geom<QT>;
+  const int n_etw = (int)((C.n_slice + W3E - 1) / W3E);
   const int g = std::max(1, B.g);
   with_bool(B.blk, [&](auto blk_) {
     hipLaunchKernelGGL((k_sweep_bf3w<2, QT, decltype(blk_)::value>), dim3((unsigned)g), dim3(G::NT), 0, C.st, W.eb,
@@ -5051,11 +5065,14 @@ static void launch_bf3w(const SweepCall& C, const Bf3Work& W, int nkb, int emajo
 // static ranges of ~12 units left the list-heavy units' workgroups last (C3, 8,900 units at 768
 // resident: 4 rounds 0.454 ms against 0.479 for one, profiles/r6) -- or the lock-step windows.
 template <int PK>
-static void launch_bf3(const SweepCall& C, const Bf3Work& W, int nkb, float cb, int emajor, bool blocked) {
+static Bf3Grid grid_bf3(const SweepCall& C, bool blocked) {
   const int res = resident_groups((const void*)k_sweep_bf3<PK>, NT);
   const int64_t units = C.q_tiles() * (int64_t)C.n_et;
   const int64_t rounds = std::max<int64_t>(1, std::min<int64_t>(8, units / (3LL * res)));
-  const Bf3Grid B = bf3_grid((int)(rounds * res) & ~7, res, blocked, (int)C.q_tiles(), C.n_et);
+  return bf3_grid((int)(rounds * res) & ~7, res, blocked, (int)C.q_tiles(), C.n_et);
+}
+template <int PK>
+static void launch_bf3(const SweepCall& C, const Bf3Work& W, int nkb, float cb, int emajor, const Bf3Grid& B) {
   hipLaunchKernelGGL((k_sweep_bf3<PK>), dim3((unsigned)B.g), dim3(NT), 0, C.st, W.eb, C.e_pad, C.n_slice, W.qb, C.q_pad,
                      C.n_query, nkb, C.n_et, C.e_base, xcd_groups(B.g, C.n_et), C.pred_kind, C.margin, C.truth, W.qn,
                      W.en, cb, C.counts, W.hdr, W.pairs, W.cap, emajor, B.bq, B.be);
@@ -5084,13 +5101,6 @@ static int sweep_bf3_impl(int model, SweepCall C, float* d_ent_km, const float* 
   const float cb = (float)(1.02 * (7.0 * K * std::ldexp(1.0, -24) * (1.0 + std::ldexp(1.0, -7)) +
                                    3.02 * std::ldexp(1.0, -16) + std::ldexp(1.0, -29) * std::sqrt(K)));
   static_assert(BF3_SEGS == 64, "k_bf3_stats sums one segment per lane of a wave");
-  hipLaunchKernelGGL(k_bf3_hdr_init, dim3((BF3_HDR / 4 + 255) / 256), dim3(256), 0, st, W.hdr, W.cap);
-  const int nkb = ktot / 16;
-  hipLaunchKernelGGL(k_bf3_split, dim3((unsigned)((q_pad * nkb + 255) / 256)), dim3(256), 0, st, C.q, q_pad,
-                     (int64_t)0, q_pad, nkb, W.qb, q_pad);
-  if (!rows_src)
-    hipLaunchKernelGGL(k_bf3_split, dim3((unsigned)((C.e_cols * nkb + 255) / 256)), dim3(256), 0, st, d_ent_km, e_pad,
-                       e_begin, C.e_cols, nkb, W.eb, e_pad);
   const int emajor = mfma_emajor(e_pad, ktot);
   // the wide sweep (k_sweep_bf3w, prediction -S) where the planes overflow the caches (C5: 15.9
   // -> 14.5 ms per evaluation); on cache-resident planes the 128 x 128 one is faster (C3: 0.74 vs
@@ -5099,7 +5109,25 @@ static int sweep_bf3_impl(int model, SweepCall C, float* d_ent_km, const float* 
   const char* wide_env = getenv("MMRE_BF3_WIDE");  // read per call: tests switch it
   const bool wide = C.pred_kind == 2 && (wide_env ? wide_env[0] != '0' : emajor != 0);
   const char* qt_env = getenv("MMRE_BF3_QT");  // the wide sweep's query tile, 256 or 128
-  const int wide_qt = qt_env ? atoi(qt_env) : 256;
+  const int wide_qt = !wide ? 0 : (q_pad % 256 == 0 && (qt_env ? atoi(qt_env) : 256) == 256) ? 256 : 128;
+  // the lock-step windows pay where the planes overflow the caches (C5, 1 GB: 16.45 -> 16.24 ms);
+  // on planes that stay L2 / MALL resident the contiguous ranges are faster (C3, 20 MB: 0.75 vs
+  // 0.85 ms, profiles/r5) -- the emajor threshold; MMRE_BF3_BLOCKED=0 / 1 forces either (tests, A/B)
+  const char* blk_env = getenv("MMRE_BF3_BLOCKED");  // read per call, as MMRE_BF3_WIDE
+  const bool blocked = blk_env ? blk_env[0] != '0' : emajor != 0;
+  // the sweep's grid, decided here so that the header records the path as launched (word 5)
+  const Bf3Grid B = wide_qt == 256   ? grid_bf3w<256>(C, blocked)
+                    : wide_qt == 128 ? grid_bf3w<128>(C, blocked)
+                    : C.pred_kind == 2 ? grid_bf3<2>(C, blocked)
+                                       : grid_bf3<-1>(C, blocked);
+  hipLaunchKernelGGL(k_bf3_hdr_init, dim3((BF3_HDR / 4 + 255) / 256), dim3(256), 0, st, W.hdr, W.cap,
+                     (uint32_t)wide_qt | (B.blk ? 1u << 16 : 0u));
+  const int nkb = ktot / 16;
+  hipLaunchKernelGGL(k_bf3_split, dim3((unsigned)((q_pad * nkb + 255) / 256)), dim3(256), 0, st, C.q, q_pad,
+                     (int64_t)0, q_pad, nkb, W.qb, q_pad);
+  if (!rows_src)
+    hipLaunchKernelGGL(k_bf3_split, dim3((unsigned)((C.e_cols * nkb + 255) / 256)), dim3(256), 0, st, d_ent_km, e_pad,
+                       e_begin, C.e_cols, nkb, W.eb, e_pad);
   hipLaunchKernelGGL(k_bf3_norms, dim3((unsigned)((q_pad + 3) / 4)), dim3(256), 0, st, d_q_rows, C.n_query, (int64_t)0,
                      q_pad, ktot, W.qn, C.truth, wide ? W.thr_pad : nullptr, W.qbf, cb);
   if (rows_src)  // split planes, norms and block maxima in one read of the rows (e_cols: whole tiles)
@@ -5112,19 +5140,14 @@ static int sweep_bf3_impl(int model, SweepCall C, float* d_ent_km, const float* 
     hipLaunchKernelGGL(k_bf3_norms, dim3((unsigned)((C.e_cols + 3) / 4)), dim3(256), 0, st, d_ent_rows, n_ent, e_begin,
                        C.e_cols, ktot, W.en, nullptr, nullptr, nullptr, 0.0f);
   MMRE_CHECK_LAUNCH();
-  // the lock-step windows pay where the planes overflow the caches (C5, 1 GB: 16.45 -> 16.24 ms);
-  // on planes that stay L2 / MALL resident the contiguous ranges are faster (C3, 20 MB: 0.75 vs
-  // 0.85 ms, profiles/r5) -- the emajor threshold; MMRE_BF3_BLOCKED=0 / 1 forces either (A/B)
-  static const char* blk_env = getenv("MMRE_BF3_BLOCKED");
-  const bool blocked = blk_env ? blk_env[0] != '0' : emajor != 0;
   return with_bool(C.pred_kind == 2, [&](auto fast_) -> int {
     constexpr int PK = decltype(fast_)::value ? 2 : -1;  // -S compiled into the epilogue, or decoded
     if constexpr (PK == 2) {  // (the wide sweep has no other epilogue)
-      if (!wide) launch_bf3<PK>(C, W, nkb, cb, emajor, blocked);
-      else if (q_pad % 256 == 0 && wide_qt == 256) launch_bf3w<256>(C, W, nkb, emajor, blocked);
-      else launch_bf3w<128>(C, W, nkb, emajor, blocked);
+      if (!wide) launch_bf3<PK>(C, W, nkb, cb, emajor, B);
+      else if (wide_qt == 256) launch_bf3w<256>(C, W, nkb, emajor, B);
+      else launch_bf3w<128>(C, W, nkb, emajor, B);
     } else {
-      launch_bf3<PK>(C, W, nkb, cb, emajor, blocked);
+      launch_bf3<PK>(C, W, nkb, cb, emajor, B);
     }
     MMRE_CHECK_LAUNCH();
     hipLaunchKernelGGL((k_bf3_fallback_zero), dim3((unsigned)((C.n_query + 255) / 256)), dim3(256), 0, st, W.hdr,

@@ -393,17 +393,19 @@ class LinkSweep:
     def bf3_stats(self, buffers):
         """The split-bf16 MFMA filter's record of the last run() on `buffers` (mmre_link_bf3_stats):
         dict(undecided=pairs rescored with the canonical chain, fallback=True if the pair list
-        overflowed and the exact f32 sweep counted instead), or None if that run did not use the
-        filter. Synchronises the stream."""
+        overflowed and the exact f32 sweep counted instead, spilled=appends a full segment sent to
+        the list's shared half, wide=the wide sweep's query tile (256 / 128) or 0 for the 128 x 128
+        sweep, blocked=True if the sweep ran its lock-step windows), or None if that run did not
+        use the filter. Synchronises the stream."""
         if not buffers.get("bf3_used"):
             return None
         wk = buffers["bf3_work"]
         out = buffers.get("bf3_stats")
         if out is None:
-            out = buffers["bf3_stats"] = torch.zeros(2, dtype=torch.int64, device=self.device)
+            out = buffers["bf3_stats"] = torch.zeros(4, dtype=torch.int64, device=self.device)
         call("mmre_link_bf3_stats", ptr(wk), int(wk.numel()), ptr(out), stream_ptr(self.device))
-        u, f = (int(x) for x in out.cpu())
-        return dict(undecided=u, fallback=bool(f))
+        u, f, s, path = (int(x) for x in out.cpu())
+        return dict(undecided=u, fallback=bool(f), spilled=s, wide=path & 0xFFFF, blocked=bool(path >> 16))
 
     def filter_stats(self, buffers):
         """Whichever count-only filter the last run() on `buffers` used: dict(kind="l1q" | "bf3",

@@ -336,7 +336,9 @@ def test_mfma_filter_counts_equal_exact_sweep_and_oracle(oracle_mod, monkeypatch
 def test_wide_sweep_lockstep_windows(oracle_mod, monkeypatch, model):
     """The wide split-bf16 sweep with its lock-step windows (MMRE_BF3_BLOCKED=1: BlockMap, the C5
     default above 64 MB of planes, which the small tables above never reach): counts bit-equal to
-    the exact sweep, entity slices summing to the whole table."""
+    the exact sweep, entity slices summing to the whole table. The filter's path record
+    (LinkSweep.bf3_stats) says that the wide sweep and its windows ran, on the whole table and on
+    the slices (9 and 10 wide tiles)."""
     import torch
     from mmre.link import FilterIndex, LinkSweep
     monkeypatch.setenv("MMRE_BF3_WIDE", "1")
@@ -363,9 +365,11 @@ def test_wide_sweep_lockstep_windows(oracle_mod, monkeypatch, model):
 
     fast, st = run()
     assert not st["fallback"] and st["undecided"] >= len(qh), st
+    assert st["blocked"] and st["wide"] != 0, st
     assert np.array_equal(fast[:2], exact["counts"][:2])
     total = np.zeros_like(fast)
     for e0, e1 in ((0, 2304), (2304, E)):
-        c, _ = run((e0, e1))
+        c, st_s = run((e0, e1))
+        assert st_s["blocked"] and st_s["wide"] != 0, st_s
         total += c
     assert np.array_equal(total[:2], fast[:2])
