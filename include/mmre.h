@@ -510,7 +510,15 @@ int mmre_sampler_openke_p(const int64_t* d_train_list, int64_t train_total, cons
  * (d_local_to_global, NULL = identity) is a known head of (t, r) (key t*n_rel+r in
  * the d_hf_* CSR over sorted keys) or a known tail of (h, r) (d_tf_*), distinct
  * within the positive. Counter-based (SplitMix64) draws from `seed` replace the
- * reference's unseeded Python `random` (P13). Output [pos | neg_1 | ... | neg_k]. */
+ * reference's unseeded Python `random` (P13). Output [pos | neg_1 | ... | neg_k],
+ * head corruptions first, then tails.
+ * Exhaustion: a negative whose 4,096 draws were all rejected is found by one scan of
+ * [0, n_local) from its last draw. A filtered node is never emitted while an
+ * allowed local node exists; the same-side negatives of a positive are distinct
+ * whenever that side has at least as many allowed nodes as negatives, otherwise
+ * every allowed node of the side is used once before any repeats (the reference
+ * resamples until it has enough, :333-347). With no allowed node at all -- where
+ * the reference never returns -- the last draw is emitted. */
 int mmre_sampler_repo(const int64_t* d_eh, const int64_t* d_et, const int64_t* d_er, int64_t batch, int64_t neg,
                       int64_t n_local, const int64_t* d_local_to_global, int64_t n_rel, const int64_t* d_hf_keys,
                       const int64_t* d_hf_off, const int64_t* d_hf_vals, int64_t hf_n, const int64_t* d_tf_keys,
@@ -838,12 +846,22 @@ int mmre_generator_backward(const float* d_gout, int64_t n_rows, int in0, int ou
  * ====================================================================== */
 /* main.evaluate (main.py:232-250): TransE L1, no normalisation
  * (module/NegativeSampling.py:294-302): score = |(h + r) - t|_1 for each
- * candidate of query i (CSR, true tail first); rank = #(s<p) + #(s==p)//2 + 1. */
+ * candidate of query i (CSR, true tail first); rank = #(s<p) + #(s==p)//2 + 1
+ * with IEEE compares (a NaN score is neither less nor equal). dim <= 1024, else
+ * MMRE_ERR_SHAPE and nothing is written. d_scores may be NULL.
+ * Empty list (d_cand_off[i] == d_cand_off[i+1]): d_rank[i] = 0, no candidate is
+ * read and no score is written (as mmre_rank_desc); this holds for
+ * mmre_cosine_rank too. */
 int mmre_candidate_rank_transe(const float* d_ent, const float* d_rel, int dim, const int64_t* d_qh,
                                const int64_t* d_qr, int64_t n_query, const int64_t* d_cand_off,
                                const int64_t* d_cand_ids, float* d_scores, int32_t* d_rank, void* stream);
 /* ZSLmodule.eval (zsl_module.py:699-706): score = mean_s cos(cand, rel_vec[s]);
- * rank = 1 + #(score > score[true]) with the true candidate first (tie-free). */
+ * rank = 1 + #(score > score[true]) with the true candidate first. Tie-free
+ * inputs are the contract (the reference's argsort leaves tie order unspecified);
+ * a copy of the true row scores bit-equal to it and is not counted. A zero-norm
+ * candidate scores 0 and a zero-norm relation sample contributes 0 (sklearn's
+ * normalisation). n_samples <= 64 and n_samples * dim * 4 <= 98,304 bytes of
+ * dynamic LDS, else MMRE_ERR_SHAPE and nothing is written. */
 int mmre_cosine_rank(const float* d_cand, int dim, const int64_t* d_cand_off, int64_t n_query,
                      const float* d_rel_vecs, int n_samples, const int64_t* d_rel_of_query, float* d_scores,
                      int32_t* d_rank, void* stream);

@@ -7,8 +7,10 @@
 //   rank = #(s_j < s_0) + #(s_j == s_0) // 2 + 1 over j >= 1.
 // k_cosine_rank: ZSLmodule.eval (zsl_module.py:699-706): score_c = mean_s cos(cand_c, rel_s)
 //   (sklearn cosine_similarity: rows L2-normalised, then dot products); rank of the true
-//   candidate (row 0) in descending order = 1 + #(score_j > score_0) (tie-free inputs).
-// One workgroup per query; the query-side vectors are staged in LDS.
+//   candidate (row 0) in descending order = 1 + #(score_j > score_0) (tie-free inputs: a copy of
+//   the true row scores bit-equal to it and is not counted).
+// One workgroup per query; the query-side vectors are staged in LDS. In both kernels an empty
+// list (off[q] == off[q + 1]) ranks 0, reads no candidate and writes no score (k_rank_desc's rule).
 #include "mmre_common.h"
 
 namespace mmre {
@@ -39,6 +41,10 @@ __global__ __launch_bounds__(256) void k_candidate_rank_transe(const float* __re
   __shared__ int red[8];
   for (int64_t q = blockIdx.x; q < n_query; q += gridDim.x) {
     const int64_t a = off[q], b = off[q + 1];
+    if (b <= a) {  // empty list (uniform over the workgroup): rank 0, no candidate read, no score written
+      if (threadIdx.x == 0) rank[q] = 0;
+      continue;
+    }
     __syncthreads();
     const float* hv = ent + qh[q] * dim;
     const float* rv = rel + qr[q] * dim;
@@ -64,7 +70,7 @@ __global__ __launch_bounds__(256) void k_candidate_rank_transe(const float* __re
     }
     less = block_reduce_int(less, red);
     eq = block_reduce_int(eq, red);
-    if (threadIdx.x == 0 && b > a) rank[q] = less + eq / 2 + 1;
+    if (threadIdx.x == 0) rank[q] = less + eq / 2 + 1;
   }
 }
 
@@ -81,6 +87,10 @@ __global__ __launch_bounds__(256) void k_cosine_rank(const float* __restrict__ c
   __shared__ float ynorm[CS_MAXS];
   for (int64_t q = blockIdx.x; q < n_query; q += gridDim.x) {
     const int64_t a = off[q], b = off[q + 1];
+    if (b <= a) {  // empty list (uniform over the workgroup): rank 0, no candidate read, no score written
+      if (threadIdx.x == 0) rank[q] = 0;
+      continue;
+    }
     const float* Y = rel_vecs + rel_of_query[q] * (int64_t)n_samples * dim;
     __syncthreads();
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -122,7 +132,7 @@ __global__ __launch_bounds__(256) void k_cosine_rank(const float* __restrict__ c
       better += v > s0;
     }
     better = block_reduce_int(better, red);
-    if (threadIdx.x == 0 && b > a) rank[q] = better + 1;
+    if (threadIdx.x == 0) rank[q] = better + 1;
   }
 }
 

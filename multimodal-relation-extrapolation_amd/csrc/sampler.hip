@@ -14,7 +14,10 @@
 //    when their global id is a known head of (t, r) / tail of (h, r) (filter_flag), distinct
 //    within a positive. The reference's draws come from the unseeded Python `random` (P13),
 //    so parity is distributional; this kernel uses a counter-based generator (SplitMix64) so
-//    a given seed is reproducible.
+//    a given seed is reproducible. After 4,096 rejected draws a negative falls back to a scan of
+//    the local nodes: a filtered node is never emitted while an allowed one exists, and a side
+//    with fewer allowed nodes than negatives uses each once before it repeats any (the
+//    reference resamples until it has enough, :333-347).
 #include "mmre_common.h"
 #include "sampler_openke.h"
 
@@ -89,21 +92,43 @@ __global__ void k_sampler_repo(const int64_t* __restrict__ eh, const int64_t* __
   const int64_t gt = local_to_global ? local_to_global[t] : t;
   for (int64_t k = 0; k < neg; ++k) {
     const bool corrupt_h = k < n_head;
+    // is local node c a known head of (t, r) / tail of (h, r)?
+    auto filtered = [&](int64_t c) {
+      if (!filter_flag) return false;
+      const int64_t g = local_to_global ? local_to_global[c] : c;
+      return corrupt_h ? in_filter(hf_keys, hf_off, hf_vals, hf_n, gt * n_rel + r, g)
+                       : in_filter(tf_keys, tf_off, tf_vals, tf_n, gh * n_rel + r, g);
+    };
+    // is c already a negative of this positive on the same side? (random.sample: distinct)
+    auto used = [&](int64_t c) {
+      bool u = false;
+      for (int64_t j = 0; j < k && !u; ++j) {
+        const bool same_side = (j < n_head) == corrupt_h;
+        if (same_side) u = (corrupt_h ? out_h[b + (j + 1) * B] : out_t[b + (j + 1) * B]) == c;
+      }
+      return u;
+    };
     int64_t cand = 0;
-    for (int tries = 0; tries < 4096; ++tries) {
+    bool bad = true;
+    for (int tries = 0; tries < 4096 && bad; ++tries) {
       ctr = splitmix(ctr);
       cand = (int64_t)(ctr % (uint64_t)n_local);
-      const int64_t g = local_to_global ? local_to_global[cand] : cand;
-      bool bad = false;
-      if (filter_flag) {
-        bad = corrupt_h ? in_filter(hf_keys, hf_off, hf_vals, hf_n, gt * n_rel + r, g)
-                        : in_filter(tf_keys, tf_off, tf_vals, tf_n, gh * n_rel + r, g);
+      bad = filtered(cand) || used(cand);
+    }
+    if (bad) {
+      // Rejection budget spent (few allowed nodes, or all of them used): one deterministic scan of
+      // [0, n_local) from the last draw takes the first allowed node not used yet, else -- every
+      // allowed node of this side is used -- repeats the first allowed one, as the reference's
+      // resampling does. A filtered node is emitted only when no local node is allowed at all.
+      int64_t first_allowed = -1, pick = -1;
+      for (int64_t i = 0; i < n_local && pick < 0; ++i) {
+        const int64_t c = cand + i < n_local ? cand + i : cand + i - n_local;
+        if (filtered(c)) continue;
+        if (first_allowed < 0) first_allowed = c;
+        if (!used(c)) pick = c;
       }
-      for (int64_t j = 0; j < k && !bad; ++j) {  // distinct within a positive (random.sample)
-        const bool same_side = (j < n_head) == corrupt_h;
-        if (same_side) bad = (corrupt_h ? out_h[b + (j + 1) * B] : out_t[b + (j + 1) * B]) == cand;
-      }
-      if (!bad) break;
+      if (pick >= 0) cand = pick;
+      else if (first_allowed >= 0) cand = first_allowed;
     }
     const int64_t row = b + (k + 1) * B;
     out_h[row] = corrupt_h ? cand : h;

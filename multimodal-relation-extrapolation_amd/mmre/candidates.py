@@ -8,29 +8,43 @@ import torch
 from ._lib import call, ptr, require_cuda, stream_ptr
 
 
+def _ids(t):
+    """int64, contiguous: what the C ABI reads through the raw pointer."""
+    return t.long().contiguous()
+
+
+def _table(t):
+    """float32, contiguous."""
+    return t.float().contiguous()
+
+
 def candidate_rank_transe(ent, rel, qh, qr, cand_off, cand_ids, return_scores=False):
-    """ranks (Q,) int32 = #(s < p) + #(s == p) // 2 + 1, true candidate first in each list."""
+    """ranks (Q,) int32 = #(s < p) + #(s == p) // 2 + 1, true candidate first in each list
+    (an empty list ranks 0 and owns no score slot)."""
     require_cuda(ent, rel, qh, qr, cand_off, cand_ids)
     n = int(qh.shape[0])
     dev = ent.device
     rank = torch.empty(n, dtype=torch.int32, device=dev)
     scores = torch.empty(int(cand_ids.shape[0]), dtype=torch.float32, device=dev) if return_scores else None
-    call("mmre_candidate_rank_transe", ptr(ent.contiguous()), ptr(rel.contiguous()), int(ent.shape[1]),
-         ptr(qh.contiguous()), ptr(qr.contiguous()), n, ptr(cand_off.contiguous()), ptr(cand_ids.contiguous()),
-         ptr(scores), ptr(rank), stream_ptr(dev))
+    ent, rel = _table(ent), _table(rel)
+    qh, qr, cand_off, cand_ids = _ids(qh), _ids(qr), _ids(cand_off), _ids(cand_ids)
+    call("mmre_candidate_rank_transe", ptr(ent), ptr(rel), int(ent.shape[1]), ptr(qh), ptr(qr), n, ptr(cand_off),
+         ptr(cand_ids), ptr(scores), ptr(rank), stream_ptr(dev))
     return (rank, scores) if return_scores else rank
 
 
 def cosine_rank(cand, cand_off, rel_vecs, rel_of_query, return_scores=False):
-    """cand (C, d), rel_vecs (n_rel_sets, S, d) -> ranks (Q,) int32 of the first candidate."""
+    """cand (C, d), rel_vecs (n_rel_sets, S, d) -> ranks (Q,) int32 of the first candidate
+    (an empty list ranks 0 and owns no score slot)."""
     require_cuda(cand, cand_off, rel_vecs, rel_of_query)
     n = int(rel_of_query.shape[0])
     dev = cand.device
     rank = torch.empty(n, dtype=torch.int32, device=dev)
     scores = torch.empty(int(cand.shape[0]), dtype=torch.float32, device=dev) if return_scores else None
-    call("mmre_cosine_rank", ptr(cand.contiguous()), int(cand.shape[1]), ptr(cand_off.contiguous()), n,
-         ptr(rel_vecs.contiguous()), int(rel_vecs.shape[1]), ptr(rel_of_query.contiguous()), ptr(scores), ptr(rank),
-         stream_ptr(dev))
+    cand, rel_vecs = _table(cand), _table(rel_vecs)
+    cand_off, rel_of_query = _ids(cand_off), _ids(rel_of_query)
+    call("mmre_cosine_rank", ptr(cand), int(cand.shape[1]), ptr(cand_off), n, ptr(rel_vecs), int(rel_vecs.shape[1]),
+         ptr(rel_of_query), ptr(scores), ptr(rank), stream_ptr(dev))
     return (rank, scores) if return_scores else rank
 
 

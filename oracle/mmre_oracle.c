@@ -494,7 +494,8 @@ int orc_sampling(const int64_t *train_list, int64_t train_total, const int64_t *
 /* -------------------------------------------------- candidate-list ranks -- */
 /* main.evaluate (main.py:232-250): TransE L1 without normalisation
  * (module/NegativeSampling.py:294-302), score = |(h + r) - t|_1 per candidate,
- * rank = #(n < p) + #(n == p) // 2 + 1 ; candidates CSR, true tail first. */
+ * rank = #(n < p) + #(n == p) // 2 + 1 ; candidates CSR, true tail first.
+ * An empty list (cand_off[q] == cand_off[q + 1]) ranks 0 and touches no score. */
 int orc_candidate_rank_transe(const float *ent, const float *rel, int dim, const int64_t *qh,
                               const int64_t *qr, const int64_t *cand_off, const int64_t *cand_ids,
                               int64_t n_query, float *scores_out, int64_t *rank_out) {
@@ -514,7 +515,7 @@ int orc_candidate_rank_transe(const float *ent, const float *rel, int dim, const
             if (c == a) p = s;
             else { less += (s < p); eq += (s == p); }
         }
-        rank_out[q] = less + eq / 2 + 1;
+        rank_out[q] = b > a ? less + eq / 2 + 1 : 0; /* an empty list has no true tail: rank 0 */
     }
     free(hr);
     return 0;

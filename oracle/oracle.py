@@ -247,7 +247,7 @@ def candidate_rank_transe(ent, rel, qh, qr, cand_off, cand_ids):
 def cosine_rank(cand_vecs, cand_off, rel_vecs, rel_of_query):
     """ZSLmodule.eval ranking (zsl_module.py:699-706): mean cosine similarity of each
     candidate against the relation's generated vectors; rank = 1 + #(score > true score).
-    Float64 restatement (sklearn normalises rows, then X @ Y.T)."""
+    Float64 restatement (sklearn normalises rows, then X @ Y.T). An empty list ranks 0."""
     X = np.asarray(cand_vecs, np.float64)
     Xn = X / np.maximum(np.linalg.norm(X, axis=1, keepdims=True), 1e-300)
     ranks = np.zeros(len(cand_off) - 1, np.int64)
@@ -256,6 +256,8 @@ def cosine_rank(cand_vecs, cand_off, rel_vecs, rel_of_query):
         Y = np.asarray(rel_vecs[rel_of_query[q]], np.float64)
         Yn = Y / np.maximum(np.linalg.norm(Y, axis=1, keepdims=True), 1e-300)
         a, b = cand_off[q], cand_off[q + 1]
+        if b <= a:
+            continue  # an empty list has no true candidate: rank 0, no score
         s = (Xn[a:b] @ Yn.T).mean(1)
         scores[a:b] = s
         ranks[q] = 1 + int(np.sum(s[1:] > s[0]))

@@ -149,3 +149,25 @@ def test_rank_desc_edge_cases():
     off = torch.tensor([0, 1000, 5000])
     r = rank_desc(x.to(DEV), off.to(DEV)).cpu().tolist()
     assert r == [1 + int((x[1:1000] > x[0]).sum()), 1 + int((x[1001:] > x[1000]).sum())]
+
+
+def test_rank_desc_above_grid_cap():
+    """16,389 queries against the 16,384-workgroup grid cap: the first five workgroups take a
+    second query. Lists of 0-3 entries, the last one empty, one NaN score (never greater)."""
+    from mmre.extractor import rank_desc
+    rng = np.random.default_rng(5)
+    Q = 16389
+    lens = rng.integers(0, 4, Q)
+    lens[-1] = 0
+    lens[:5], lens[16384:16388] = [3, 0, 2, 1, 3], [0, 3, 3, 2]  # q and q + 16384 differ
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    s = rng.random(int(off[-1])).astype(np.float32)
+    s[off[16385] + 1] = np.nan
+    want = np.zeros(Q, np.int64)
+    for q in np.flatnonzero(lens):
+        a, b = off[q], off[q + 1]
+        with np.errstate(invalid="ignore"):
+            want[q] = 1 + int((s[a + 1:b] > s[a]).sum())
+    r = rank_desc(torch.from_numpy(s).to(DEV), torch.from_numpy(off).to(DEV)).cpu().numpy()
+    assert np.array_equal(r, want)
+    assert want[-1] == 0 and len(set(want[16384:].tolist())) > 1

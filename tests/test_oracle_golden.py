@@ -197,6 +197,23 @@ def test_cosine_rank_rule(golden, oracle_mod):
     assert np.array_equal(r, g["zs_ranks"])
 
 
+def test_candidate_rankings_rank_an_empty_list_zero(oracle_mod):
+    """The empty-list contract of both candidate rankings (include/mmre.h): rank 0, no score; the
+    lists around an empty one are untouched by it."""
+    rng = np.random.default_rng(0)
+    ent = rng.uniform(-1, 1, (9, 5)).astype(np.float32)
+    rel = rng.uniform(-1, 1, (2, 5)).astype(np.float32)
+    ids = np.array([3, 4, 5, 6, 7], np.int64)
+    qh, qr = np.array([0, 1, 2, 0]), np.array([0, 1, 1, 0])
+    s, r = oracle_mod.candidate_rank_transe(ent, rel, qh, qr, np.array([0, 0, 3, 3, 5]), ids)
+    s2, r2 = oracle_mod.candidate_rank_transe(ent, rel, qh[[1, 3]], qr[[1, 3]], np.array([0, 3, 5]), ids)
+    assert r.tolist() == [0, r2[0], 0, r2[1]] and r2.min() >= 1 and np.array_equal(s, s2)
+    relv = rng.standard_normal((2, 3, 5)).astype(np.float32)
+    s, r = oracle_mod.cosine_rank(ent[:5], np.array([0, 0, 3, 3, 5]), relv, np.array([0, 1, 1, 0]))
+    s2, r2 = oracle_mod.cosine_rank(ent[:5], np.array([0, 3, 5]), relv, np.array([1, 0]))
+    assert r.tolist() == [0, r2[0], 0, r2[1]] and r2.min() >= 1 and np.array_equal(s, s2)
+
+
 @pytest.mark.parametrize("tag", ["g200_eval", "g200_train", "g256_eval"])
 def test_generator(golden, oracle_mod, tag):
     g = golden("repo")
