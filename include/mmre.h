@@ -974,7 +974,8 @@ int64_t mmre_m3ae_workspace(int64_t n_rows, int64_t n_unique, int d);
  *   attention.fc.{weight, bias}, layer_norm2.{weight,bias}, transformer_mlp.fc1.{weight (4d, d),
  *   bias}, transformer_mlp.fc2.{weight (d, 4d), bias};
  *   encoder.layer_norm.{weight, bias}.
- * n_unique / n_rows / max_rows: the plan's info. */
+ * n_unique / n_rows / max_rows: the plan's info. At most 65,535 unique sequences per call (more:
+ * MMRE_ERR_SHAPE, before anything is launched; encode such a batch in slices). */
 int mmre_m3ae_encode(const float* const* h_params, int depth, int d, int heads, float ln_eps,
                      const int32_t* d_tokens, const float* d_mask, int64_t n_seq, int64_t len, int64_t vocab,
                      const int32_t* d_plan, int64_t n_unique, int64_t n_rows, int max_rows, float* d_work,
@@ -989,6 +990,10 @@ int mmre_m3ae_linear(int epilogue, const float* d_a, int64_t m, int k, const flo
                      const float* d_resid, float* d_out, void* stream);
 int mmre_m3ae_attention(const float* d_qkv, const int32_t* d_off, int64_t n_seq, int max_rows, int heads,
                         int head_dim, float scale, int cls_only, float* d_out, void* stream);
+/* Host only: the output tile width, 64 or 128, that mmre_m3ae_linear uses for an (m, n) output
+ * (128 once ceil(m / 64) * (n / 128) >= 2048 and n % 128 == 0; MMRE_M3AE_TILE = "128" / "64",
+ * read at every call, forces either where n allows it), -1 for a shape it refuses. */
+int mmre_m3ae_linear_tile(int64_t m, int n);
 
 /* ====================================================================== *
  *  Small fp32 GEMM of the GAN step's Discriminator (zsl_module.py:112-138: *

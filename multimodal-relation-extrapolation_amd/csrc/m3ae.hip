@@ -49,6 +49,8 @@ constexpr int M3_MAXLEN = 335;  // tokens per description row (attention keeps 1
 constexpr int M3_AQ = 16;       // query rows per attention workgroup
 constexpr int M3_AKC = 64;      // most keys per staged K / V chunk
 constexpr int M3_MAXR = 336;    // 1 + M3_MAXLEN
+constexpr int M3_MAXSEQ = 65535;   // attention's grid: unique sequences in z,
+constexpr int M3_MAXHEADS = 1024;  // heads in y
 
 // Plan buffer (int32), n = n_seq:
 //   uniq[n]    unique-sequence index of each input row
@@ -503,19 +505,27 @@ void launch_linear_bn(int epi, int64_t mt, hipStream_t st, const float* A, int64
   else hipLaunchKernelGGL((k_m3ae_linear<2, BN>), g, dim3(256), 0, st, A, M, K, W, N, bias, resid, out);
 }
 
+// Tile width (64 or 128) of the linear for an M x N output, -1 for a shape it refuses.
+// 64 x 64 tiles: measured faster than 64 x 128 on every encoder shape at 2,261 rows
+// (scripts/m3ae_gemm_ab.py; an in-workgroup split-K was no faster either); 64 x 128 only
+// once the grid holds 8 tiles per CU. MMRE_M3AE_TILE = "128" / "64" forces either where N allows
+// it (experiments, tests; read per call: tests switch it).
+int linear_tile(int64_t M, int N) {
+  if (M < 0 || N <= 0 || N % 64 || (M + LM - 1) / LM * (N / 64) > 0x7fffff00LL) return -1;
+  const int64_t mt = (M + LM - 1) / LM;
+  const char* force = getenv("MMRE_M3AE_TILE");
+  const bool wide = N % 128 == 0 && (force && force[0] ? force[0] == '1' : mt * (N / 128) >= 2048);
+  return wide ? 128 : 64;
+}
+
 int launch_linear(int epi, const float* A, int64_t M, int K, const float* W, int N, const float* bias,
                   const float* resid, float* out, hipStream_t st) {
-  if (M < 0 || K <= 0 || N <= 0 || K % LK || N % 64 || (M + LM - 1) / LM * (N / 64) > 0x7fffff00LL)
-    return MMRE_ERR_SHAPE;
+  const int bn = linear_tile(M, N);
+  if (bn < 0 || K <= 0 || K % LK) return MMRE_ERR_SHAPE;
   if (epi < 0 || epi > 2 || !A || !W || !bias || !out || (epi == 2 && !resid)) return MMRE_ERR_ARG;
   if (M == 0) return MMRE_OK;
   const int64_t mt = (M + LM - 1) / LM;
-  // 64 x 64 tiles: measured faster than 64 x 128 on every encoder shape at 2,261 rows
-  // (scripts/m3ae_gemm_ab.py; an in-workgroup split-K was no faster either); 64 x 128 only
-  // once the grid holds 8 tiles per CU
-  static const char* force = getenv("MMRE_M3AE_TILE");  // experiments: "128" or "64"
-  const bool wide = N % 128 == 0 && (force && force[0] ? force[0] == '1' : mt * (N / 128) >= 2048);
-  if (wide) launch_linear_bn<128>(epi, mt, st, A, M, K, W, N, bias, resid, out);
+  if (bn == 128) launch_linear_bn<128>(epi, mt, st, A, M, K, W, N, bias, resid, out);
   else launch_linear_bn<64>(epi, mt, st, A, M, K, W, N, bias, resid, out);
   MMRE_CHECK_LAUNCH();
   return MMRE_OK;
@@ -524,7 +534,8 @@ int launch_linear(int epi, const float* A, int64_t M, int K, const float* W, int
 int launch_attn(const float* qkv, const int32_t* off, int64_t n_seq, int max_rows, int heads, int hd, float scale,
                 int cls_only, float* out, hipStream_t st) {
   if (n_seq <= 0) return MMRE_OK;
-  if (max_rows < 1 || max_rows > M3_MAXR || n_seq > 65535 || heads < 1 || heads > 1024) return MMRE_ERR_SHAPE;
+  if (max_rows < 1 || max_rows > M3_MAXR || n_seq > M3_MAXSEQ || heads < 1 || heads > M3_MAXHEADS)
+    return MMRE_ERR_SHAPE;
   const int kc = max_rows >= M3_AKC ? M3_AKC : (int)round_up(max_rows, 16);
   const int rp = (int)round_up(max_rows, 4) + 1;  // odd-ish row pitch: row groups start on different banks
   const size_t lds = (size_t)((M3_AQ + kc) * (hd + 1) + M3_AQ * rp) * sizeof(float);
@@ -593,6 +604,8 @@ extern "C" int mmre_m3ae_linear(int epilogue, const float* d_a, int64_t m, int k
   return launch_linear(epilogue, d_a, m, k, d_w, n, d_bias, d_resid, d_out, (hipStream_t)stream);
 }
 
+extern "C" int mmre_m3ae_linear_tile(int64_t m, int n) { return linear_tile(m, n); }
+
 extern "C" int mmre_m3ae_attention(const float* d_qkv, const int32_t* d_off, int64_t n_seq, int max_rows, int heads,
                                    int head_dim, float scale, int cls_only, float* d_out, void* stream) {
   if (!d_qkv || !d_off || !d_out) return MMRE_ERR_ARG;
@@ -608,6 +621,8 @@ extern "C" int mmre_m3ae_encode(const float* const* h_params, int depth, int d, 
       n_rows < n_unique || max_rows < 1 || max_rows > len + 1 || !d_plan || !d_work || !d_cls || vocab <= 0 ||
       (n_seq > 0 && (!d_tokens || !d_mask)))
     return MMRE_ERR_ARG;
+  // attention's grid is (query blocks, heads, unique sequences): refused here, before any launch
+  if (n_unique > M3_MAXSEQ || heads > M3_MAXHEADS) return MMRE_ERR_SHAPE;
   if (work_floats < mmre_m3ae_workspace(n_rows, n_unique, d)) return MMRE_ERR_WORKSPACE;
   for (int i = 0; i < 4 + 12 * depth + 2; ++i)
     if (!h_params[i]) return MMRE_ERR_ARG;

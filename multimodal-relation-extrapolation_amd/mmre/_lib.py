@@ -154,6 +154,7 @@ SIGNATURES = {
     "mmre_m3ae_layernorm": (I32, [P, I64, I32, P, P, F32, P, P]),
     "mmre_m3ae_linear": (I32, [I32, P, I64, I32, P, I32, P, P, P, P]),
     "mmre_m3ae_attention": (I32, [P, P, I64, I32, I32, I32, F32, I32, P, P]),
+    "mmre_m3ae_linear_tile": (I32, [I64, I32]),
     "mmre_gemm_splits": (I32, [I64, I64, I64]),
     "mmre_gemm_f32": (I32, [P, I64, I64, P, I64, I64, I64, I64, I64, P, P, P]),
     "mmre_sn_weight": (I32, [P, I32, I32, P, P, I32, F32, P, P, P, P, P, P]),

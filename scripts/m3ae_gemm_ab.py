@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""A/B of the M3AE linear's tile modes (MMRE_M3AE_TILE = 128 | 64, read once per
-process) on the encoder's shapes at the FB15K-237-ZS packed row count. Diagnostic only."""
+"""A/B of the M3AE linear's tile modes (MMRE_M3AE_TILE = 128 | 64, read at every
+call) on the encoder's shapes at the FB15K-237-ZS packed row count. Diagnostic only."""
 import os
 import sys
 

@@ -95,7 +95,7 @@ def test_m3ae_c_abi_exports_and_argument_checks():
     from mmre import _lib
     L = ctypes.CDLL(_lib.LIB_PATH)
     for n in ("mmre_m3ae_max_len", "mmre_m3ae_plan_size", "mmre_m3ae_plan", "mmre_m3ae_workspace", "mmre_m3ae_encode",
-              "mmre_m3ae_layernorm", "mmre_m3ae_linear", "mmre_m3ae_attention"):
+              "mmre_m3ae_layernorm", "mmre_m3ae_linear", "mmre_m3ae_attention", "mmre_m3ae_linear_tile"):
         assert hasattr(L, n)
     lib = _lib.lib()
     assert lib.mmre_m3ae_max_len() >= 320
@@ -115,6 +115,89 @@ def test_m3ae_c_abi_exports_and_argument_checks():
                                 dummy, 1, 9, 9, dummy, 10 ** 6, dummy, None) == 3  # d = 200 unsupported
     assert lib.mmre_m3ae_encode(ctypes.cast(params, ctypes.c_void_p), 2, 384, 6, 1e-5, dummy, dummy, 2, 8, 10,
                                 dummy, 3, 9, 9, dummy, 10 ** 6, dummy, None) == 1  # n_unique > n_seq
+
+
+def test_linear_tile_threshold_and_override(monkeypatch):
+    """mmre_m3ae_linear_tile, the launcher's own choice: 128 exactly when n % 128 == 0 and
+    ceil(m / 64) * (n / 128) >= 2048; MMRE_M3AE_TILE is read at every call and cannot force 128
+    on an n that is no multiple of 128; -1 for the shapes mmre_m3ae_linear refuses."""
+    from mmre import _lib
+    tile = _lib.lib().mmre_m3ae_linear_tile
+    monkeypatch.delenv("MMRE_M3AE_TILE", raising=False)
+    assert tile(10880, 1536) == 64 and tile(10881, 1536) == 128
+    assert tile(10 ** 6, 192) == 64
+    for n in (64, 128, 192, 256, 384, 1152, 1536, 5120):
+        for mt in (1, 2047, 2048, -(-2048 * 128 // n) - 1, -(-2048 * 128 // n), 4096):
+            for m in (64 * mt - 63, 64 * mt, 64 * mt + 1):
+                rule = n % 128 == 0 and -(-m // 64) * (n // 128) >= 2048
+                assert tile(m, n) == (128 if rule else 64), (m, n)
+    assert tile(0, 128) == 64  # an empty output is accepted (nothing is launched)
+    for m, n in ((-1, 128), (10, 0), (10, -64), (10, 200), (10, 96), (2 ** 40, 64)):
+        assert tile(m, n) == -1, (m, n)
+    monkeypatch.setenv("MMRE_M3AE_TILE", "128")
+    assert tile(1, 128) == 128 and tile(10880, 1536) == 128
+    assert tile(70, 192) == 64 and tile(10 ** 6, 192) == 64
+    assert tile(10, 200) == -1
+    monkeypatch.setenv("MMRE_M3AE_TILE", "64")
+    assert tile(10881, 1536) == 64 and tile(1, 128) == 64
+    monkeypatch.setenv("MMRE_M3AE_TILE", "")
+    assert tile(10880, 1536) == 64 and tile(10881, 1536) == 128
+    monkeypatch.delenv("MMRE_M3AE_TILE")
+    assert tile(10880, 1536) == 64 and tile(10881, 1536) == 128
+
+
+def test_encode_refuses_too_many_unique_sequences_before_any_launch():
+    """Attention's grid holds 65,535 sequences; an otherwise valid encode of 65,536 is refused in
+    the argument checks (nothing is launched: this passes without a device)."""
+    from mmre import _lib
+    lib = _lib.lib()
+    dummy = ctypes.c_void_p(16)
+    params = (ctypes.c_void_p * 30)(*([16] * 30))
+    n = 65536
+    work = lib.mmre_m3ae_workspace(2 * n, n, 384)
+    assert lib.mmre_m3ae_encode(ctypes.cast(params, ctypes.c_void_p), 2, 384, 6, 1e-5, dummy, dummy, n, 8, 10,
+                                dummy, n, 2 * n, 9, dummy, work, dummy, None) == 3
+    assert lib.mmre_m3ae_encode(ctypes.cast(params, ctypes.c_void_p), 2, 384, 6, 1e-5, dummy, dummy, n + 5, 8, 10,
+                                dummy, n, 2 * n, 9, dummy, work, dummy, None) == 3
+    # the other checks still win where they applied before
+    assert lib.mmre_m3ae_encode(ctypes.cast(params, ctypes.c_void_p), 2, 384, 6, 1e-5, dummy, dummy, n, 8, 10,
+                                dummy, n + 1, 2 * n, 9, dummy, work, dummy, None) == 1  # n_unique > n_seq
+
+
+def test_plan_restatement_on_handwritten_rows():
+    """tests/m3ae_restate.py on the six rows of test_plan_dedupes_adjacent_repeats_and_counts_bad_ids
+    (tests/test_m3ae_gpu.py), whose expected plan is written out by hand."""
+    import m3ae_restate
+    L = 8
+    rows = [([1, 2, 3, 0, 0, 0, 0, 0], 3), ([1, 2, 3, 9, 9, 9, 9, 9], 3), ([1, 2, 3, 0, 0, 0, 0, 0], 4),
+            ([1, 2, 3, 0, 0, 0, 0, 0], 4), ([5, 5, 5, 5, 5, 5, 5, 5], 8), ([1, 2, 3, 0, 0, 0, 0, 0], 3)]
+    tok = np.array([r for r, _ in rows], dtype=np.int32)
+    msk = np.array([[0.0] * n + [1.0] * (L - n) for _, n in rows], dtype=np.float32)
+    p = m3ae_restate.plan(tok, msk, 1, 10)
+    assert list(p["cnt"]) == [4, 4, 5, 5, 9, 4] and list(p["head"]) == [1, 0, 1, 0, 1, 1]
+    assert list(p["uniq"]) == [0, 0, 1, 1, 2, 3]
+    assert list(p["src"]) == [0, 2, 4, 5]
+    assert list(p["off"]) == [0, 4, 9, 18, 22]
+    assert list(p["info"]) == [4, 22, 9, 0]
+    p = m3ae_restate.plan(tok, msk, 0, 5)
+    assert list(p["uniq"]) == list(range(6)) and list(p["src"]) == list(range(6))
+    assert list(p["off"]) == [0, 4, 8, 13, 18, 27, 31]
+    assert list(p["info"]) == [6, 31, 9, 8]
+    # the mask rule is `mask > 0`: -1, -0.0 and NaN are unpadded, a denormal and +inf are padding
+    m = np.array([[-1.0, -0.0, np.nan, 1e-40, np.inf]], dtype=np.float32)
+    assert list(m3ae_restate.plan(np.zeros((1, 5), np.int32), m, 1, 10)["cnt"]) == [4]
+    # no rows / empty rows
+    assert list(m3ae_restate.plan(np.zeros((0, 3), np.int32), np.zeros((0, 3)), 1, 10)["info"]) == [0, 0, 1, 0]
+    p = m3ae_restate.plan(np.zeros((3, 0), np.int32), np.zeros((3, 0)), 1, 10)
+    assert list(p["uniq"]) == [0, 0, 0] and list(p["off"]) == [0, 1] and list(p["info"]) == [1, 1, 1, 0]
+    # split() reads the same fields back out of a plan buffer
+    buf = np.full(6 * 6 + 5, -7, dtype=np.int32)
+    p = m3ae_restate.plan(tok, msk, 1, 10)
+    buf[:6], buf[6:10], buf[12:17], buf[19:23] = p["uniq"], p["src"], p["off"], p["info"]
+    m3ae_restate.assert_plan_equal(buf, 6, p)
+    buf[14] += 1
+    with pytest.raises(AssertionError):
+        m3ae_restate.assert_plan_equal(buf, 6, p)
 
 
 def test_encoder_needs_device_tensors():
