@@ -297,8 +297,8 @@ int64_t mmre_rel_workspace(int model, int64_t n_rel, int dim);
 
 /* For test triple i = (d_qh[i], d_qr[i], d_qt[i]): pred(j) = what model.predict returns for the
  * row (h, j, t) in 'normal' mode, j = 0..n_rel-1 (Test.h:55-62) -- bit for bit the score
- * chain of mmre_ns_forward for that row (lane-strided partials, butterfly wave sum, TransE's
- * three norms and divisions, RotatE's canonical sincos) followed by the pred_kind / margin
+ * chain of mmre_ns_forward for that row (the row-wise chain both are built from,
+ * csrc/row_chain.h) followed by the pred_kind / margin
  * transform of mmre_link_truth (for TransE with a model margin and RotatE, mmre_ns_forward's
  * m - s IS that transform's inner step: pred_kind 1 / 3). Then, Test.h:200-213:
  *   d_counts[0][i] = #{ j != r : pred(j) < pred(r) }   strict: ties favour the truth, and a NaN

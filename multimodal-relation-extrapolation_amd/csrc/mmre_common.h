@@ -25,8 +25,8 @@ constexpr int kWave = 64;
 __host__ __device__ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // Sum over the wave by the xor butterfly: a + b and b + a agree, so every lane ends with the same
-// total, the same every run. The reduction of every row-wise score chain (ns.hip row_score,
-// relpred.hip): two kernels that feed it the same lane partials get the same bits.
+// total, the same every run. The reduction of the row-wise score chain (row_chain.h): two kernels
+// that feed it the same lane partials get the same bits.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);

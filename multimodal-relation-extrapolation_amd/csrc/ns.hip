@@ -16,7 +16,8 @@
 // (integer count atomics only) and one wave per table row sums its slots in slot order, so the
 // gradient tables are bit-identical run to run (the fused paths below; the rows backward of
 // mmre_score_rows_backward / mmre_ns_backward).
-#include "mmre_common.h"
+#include "dispatch.h"
+#include "row_chain.h"
 #include "sampler_openke.h"
 
 namespace mmre {
@@ -54,11 +55,9 @@ __device__ __forceinline__ void ns_adv_stats(const NSArgs& A, const float* __res
   den = wave_sum(den);
 }
 
-// Raw score s of one row (before the model's margin transform) and, optionally, the
-// accumulation of g * d(score)/d(embeddings) into gradient tables.
-// TransE: s = |(h + r) - t|_p with optional F.normalize; forward returns m - s when the model
-// has a margin. DistMult: sum h r t. ComplEx: sum of the four triple products. RotatE:
-// forward = m - sum_k |h o r - t|.
+// The training forward of one row, any model at any dim: the chain of row_chain.h with the
+// elements read from memory as they are used (lane's c-th element is lane + 64 c here too). The
+// forward's transform in apply_pred's kinds: 4 (m - s) for RotatE and TransE with a margin, else 0.
 __device__ float row_score(const NSArgs& A, int64_t row, int lane) {
   const int d = A.dim;
   const int64_t h = A.h[row], t = A.t[row], r = A.r[row];
@@ -69,37 +68,32 @@ __device__ float row_score(const NSArgs& A, int64_t row, int lane) {
     if (A.norm_flag) {
       float a = 0.0f, b = 0.0f, c = 0.0f;
       for (int k = lane; k < d; k += kWave) { a += hv[k] * hv[k]; b += tv[k] * tv[k]; c += rv[k] * rv[k]; }
-      nh = fmaxf(sqrtf(wave_sum(a)), 1e-12f);
-      nt = fmaxf(sqrtf(wave_sum(b)), 1e-12f);
-      nr = fmaxf(sqrtf(wave_sum(c)), 1e-12f);
+      nh = norm_of_sq(wave_sum(a));
+      nt = norm_of_sq(wave_sum(b));
+      nr = norm_of_sq(wave_sum(c));
     }
     for (int k = lane; k < d; k += kWave) {
-      const float x = (hv[k] / nh + rv[k] / nr) - tv[k] / nt;
-      acc += A.model == MMRE_TRANSE_L1 ? fabsf(x) : x * x;
+      const float hq = hv[k] / nh, rq = rv[k] / nr, tq = tv[k] / nt;
+      acc += A.model == MMRE_TRANSE_L1 ? row_term<MMRE_TRANSE_L1>(hq, rq, tq) : row_term<MMRE_TRANSE_L2>(hq, rq, tq);
     }
-    acc = wave_sum(acc);
-    if (A.model == MMRE_TRANSE_L2) acc = sqrtf(acc);
-    return A.use_model_margin ? A.model_margin - acc : acc;
+    return row_finish(acc, A.model == MMRE_TRANSE_L2, A.use_model_margin ? 4 : 0, A.model_margin);
   } else if (A.model == MMRE_DISTMULT) {
     const float *hv = A.ent + h * d, *tv = A.ent + t * d, *rv = A.rel + r * d;
-    for (int k = lane; k < d; k += kWave) acc += (hv[k] * rv[k]) * tv[k];
-    return wave_sum(acc);
+    for (int k = lane; k < d; k += kWave) acc += row_term<MMRE_DISTMULT>(hv[k], rv[k], tv[k]);
+    return row_finish(acc, false, 0, 0.0f);
   } else if (A.model == MMRE_COMPLEX) {
     const float *hr = A.ent + h * d, *hi = A.ent_im + h * d, *tr = A.ent + t * d, *ti = A.ent_im + t * d;
     const float *rr = A.rel + r * d, *ri = A.rel_im + r * d;
-    for (int k = lane; k < d; k += kWave)
-      acc += hr[k] * tr[k] * rr[k] + hi[k] * ti[k] * rr[k] + hr[k] * ti[k] * ri[k] - hi[k] * tr[k] * ri[k];
-    return wave_sum(acc);
+    for (int k = lane; k < d; k += kWave) acc += row_term<MMRE_COMPLEX>(hr[k], hi[k], rr[k], ri[k], tr[k], ti[k]);
+    return row_finish(acc, false, 0, 0.0f);
   } else {
     const float *hv = A.ent + h * 2 * d, *tv = A.ent + t * 2 * d, *rv = A.rel + r * d;
     for (int k = lane; k < d; k += kWave) {
       float s, c;
-      canon_sincos(rv[k] / A.phase_denom, &s, &c);
-      const float re = hv[k] * c - hv[d + k] * s - tv[k];
-      const float im = hv[k] * s + hv[d + k] * c - tv[d + k];
-      acc += sqrtf(re * re + im * im);
+      rel_sincos(rv[k], A.phase_denom, &s, &c);
+      acc += row_term<MMRE_ROTATE>(hv[k], hv[d + k], s, c, tv[k], tv[d + k]);
     }
-    return A.model_margin - wave_sum(acc);
+    return row_finish(acc, false, 4, A.model_margin);
   }
 }
 
@@ -259,20 +253,6 @@ __device__ __forceinline__ void wave_sum3(float& a, float& b, float& c) {
   }
 }
 
-template <int NC>
-struct Vec {
-  float v[NC];  // element lane + 64 c of the row in v[c] (zero past the row's end)
-};
-
-template <int NC>
-__device__ __forceinline__ void vload(Vec<NC>& o, const float* row, int d, int lane) {
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int i = lane + c * kWave;
-    o.v[c] = i < d ? row[i] : 0.0f;
-  }
-}
-
 // Row `row` (wave-uniform) of a [*, d] table through a buffer resource sized to the row: the
 // padding lanes (element >= d) read 0 and their stores are dropped by the hardware range check,
 // so the fast path has no per-element bounds branches.
@@ -295,35 +275,9 @@ __device__ __forceinline__ void vstore_row(float* table, int64_t row, const Vec<
 }
 
 template <int NC>
-__device__ __forceinline__ float vsq(const Vec<NC>& a) {
-  float s = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) s += a.v[c] * a.v[c];
-  return s;
-}
-
-template <int NC>
 __device__ __forceinline__ void vadd(Vec<NC>& a, const Vec<NC>& b, float s) {
 #pragma unroll
   for (int c = 0; c < NC; ++c) a.v[c] += s * b.v[c];
-}
-
-// x = (h / nh + r / nr) - t / nt per element (the forward's association, TransE.py:55-58)
-__device__ __forceinline__ float tx(float h, float r, float t, float nh, float nr, float nt) {
-  return (h / nh + r / nr) - t / nt;
-}
-
-// |x|_1 or |x|_2^2 partial of this lane (padding elements are 0 - 0 = 0)
-template <int NC, bool L2>
-__device__ __forceinline__ float row_partial(const Vec<NC>& h, const Vec<NC>& r, const Vec<NC>& t, float nh, float nr,
-                                             float nt) {
-  float acc = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const float x = tx(h.v[c], r.v[c], t.v[c], nh, nr, nt);
-    acc += L2 ? x * x : fabsf(x);
-  }
-  return acc;
 }
 
 // the per-row inputs of one wave: each of h, r, t is the positive's register copy or a row
@@ -345,29 +299,30 @@ __device__ __forceinline__ void row_ctx_load(RowCtx<NC>& o, const NSArgs& A, int
   o.own_r = r == pr;
   o.own_t = t == pt;
   o.sh = o.sr = o.st = 0.0f;
-  if (o.own_h) o.h = P.h; else vload(o.h, A.ent + h * d, d, lane);
-  if (o.own_r) o.r = P.r; else vload(o.r, A.rel + r * d, d, lane);
-  if (o.own_t) o.t = P.t; else vload(o.t, A.ent + t * d, d, lane);
+  if (o.own_h) o.h = P.h; else vload(o.h.v, A.ent + h * d, d, lane);
+  if (o.own_r) o.r = P.r; else vload(o.r.v, A.rel + r * d, d, lane);
+  if (o.own_t) o.t = P.t; else vload(o.t.v, A.ent + t * d, d, lane);
 }
 
 template <int NC>
 __device__ __forceinline__ void row_ctx_norms(RowCtx<NC>& o, const RowCtx<NC>& P) {
-  float a = o.own_h ? 0.f : vsq(o.h), b = o.own_r ? 0.f : vsq(o.r), c = o.own_t ? 0.f : vsq(o.t);
+  float a = o.own_h ? 0.f : vsq(o.h.v), b = o.own_r ? 0.f : vsq(o.r.v), c = o.own_t ? 0.f : vsq(o.t.v);
   if (!(o.own_h && o.own_r && o.own_t)) wave_sum3(a, b, c);
   o.sh = o.own_h ? P.sh : a;
   o.sr = o.own_r ? P.sr : b;
   o.st = o.own_t ? P.st : c;
 }
 
-__device__ __forceinline__ float norm_of(float sq, int norm_flag) { return norm_flag ? fmaxf(sqrtf(sq), 1e-12f) : 1.0f; }
+__device__ __forceinline__ float norm_of(float sq, int norm_flag) { return norm_flag ? norm_of_sq(sq) : 1.0f; }
 
 template <int NC, bool L2>
 __device__ __forceinline__ float row_fwd(const NSArgs& A, const RowCtx<NC>& R, int lane) {
   const float nh = norm_of(R.sh, A.norm_flag), nr = norm_of(R.sr, A.norm_flag), nt = norm_of(R.st, A.norm_flag);
-  float acc = row_partial<NC, L2>(R.h, R.r, R.t, nh, nr, nt);
-  acc = wave_sum(acc);
-  if (L2) acc = sqrtf(acc);
-  return A.use_model_margin ? A.model_margin - acc : acc;
+  // every slot adds: the rows are zero past their end, where the term is (0 + 0) - 0
+  const float acc = lane_partial<NC>(NC * kWave, lane, [&](int c) {
+    return row_term<L2 ? MMRE_TRANSE_L2 : MMRE_TRANSE_L1>(R.h.v[c] / nh, R.r.v[c] / nr, R.t.v[c] / nt);
+  });
+  return row_finish(acc, L2, A.use_model_margin ? 4 : 0, A.model_margin);
 }
 
 template <int NC, bool L2>
@@ -380,10 +335,10 @@ __global__ __launch_bounds__(256) void k_ns_transe_forward(NSArgs A, float* __re
   const int d = A.dim;
   const int64_t ph = A.h[b], pr = A.r[b], pt = A.t[b];
   RowCtx<NC> P;
-  vload(P.h, A.ent + ph * d, d, lane);
-  vload(P.r, A.rel + pr * d, d, lane);
-  vload(P.t, A.ent + pt * d, d, lane);
-  P.sh = vsq(P.h); P.sr = vsq(P.r); P.st = vsq(P.t);
+  vload(P.h.v, A.ent + ph * d, d, lane);
+  vload(P.r.v, A.rel + pr * d, d, lane);
+  vload(P.t.v, A.ent + pt * d, d, lane);
+  P.sh = vsq(P.h.v); P.sr = vsq(P.r.v); P.st = vsq(P.t.v);
   wave_sum3(P.sh, P.sr, P.st);
   P.own_h = P.own_r = P.own_t = true;
   const float p = row_fwd<NC, L2>(A, P, lane);
@@ -1393,7 +1348,7 @@ __device__ __forceinline__ void transe_owner_row(Ord& ord, bool active, int64_t 
     for (int c = 0; c < NC; ++c) p.v[c] = __builtin_fmaf(-sgd_lr, dy.v[c], v.v[c]);
     vstore_row(is_ent ? pent : prel, id, p, d, lane);
     if (nx.nrm_e) {  // the next step's pre-pass of this row (ns_prepass_block's arithmetic)
-      const float nr = sqrtf(wave_sum(vsq(p)));
+      const float nr = sqrtf(wave_sum(vsq(p.v)));
       if (lane == 0) (is_ent ? nx.nrm_e : nx.nrm_r)[id] = nr;
       if (nx.ent_n) {
         const float cn = fmaxf(nr, 1e-12f);
@@ -1608,35 +1563,25 @@ __device__ __forceinline__ int neg_code(int64_t h, int64_t r, int64_t t, int64_t
   return 4;
 }
 
-// row_score of DistMult / ComplEx / RotatE on rows already in registers (same per-element
-// expressions, elements in the same lane + 64 c order, padding elements adding +0: the same
-// floats bit for bit). RotatE: sn / cs of the relation row (canon_sincos(r / phase_denom)).
+// row_score of DistMult / ComplEx / RotatE on rows already in registers. RotatE: sn / cs of the
+// relation row (rot_sincos). Every slot adds: the rows are zero past their end, and so is the term.
 template <int NC>
 __device__ __forceinline__ float gen_score(const NSArgs& A, const Row2<NC>& H, const Row2<NC>& R, const Row2<NC>& T,
                                            const Vec<NC>& sn, const Vec<NC>& cs) {
-  float acc = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    if (A.model == MMRE_DISTMULT) {
-      acc += (H.a.v[c] * R.a.v[c]) * T.a.v[c];
-    } else if (A.model == MMRE_COMPLEX) {
-      const float hr = H.a.v[c], hi = H.b.v[c], tr = T.a.v[c], ti = T.b.v[c], rr = R.a.v[c], ri = R.b.v[c];
-      acc += hr * tr * rr + hi * ti * rr + hr * ti * ri - hi * tr * ri;
-    } else {
-      const float re = H.a.v[c] * cs.v[c] - H.b.v[c] * sn.v[c] - T.a.v[c];
-      const float im = H.a.v[c] * sn.v[c] + H.b.v[c] * cs.v[c] - T.b.v[c];
-      acc += sqrtf(re * re + im * im);
-    }
-  }
-  acc = wave_sum(acc);
-  return A.model == MMRE_ROTATE ? A.model_margin - acc : acc;
+  const float acc = lane_partial<NC>(NC * kWave, threadIdx.x & 63, [&](int c) {
+    if (A.model == MMRE_DISTMULT) return row_term<MMRE_DISTMULT>(H.a.v[c], R.a.v[c], T.a.v[c]);
+    if (A.model == MMRE_COMPLEX)
+      return row_term<MMRE_COMPLEX>(H.a.v[c], H.b.v[c], R.a.v[c], R.b.v[c], T.a.v[c], T.b.v[c]);
+    return row_term<MMRE_ROTATE>(H.a.v[c], H.b.v[c], sn.v[c], cs.v[c], T.a.v[c], T.b.v[c]);
+  });
+  return row_finish(acc, false, A.model == MMRE_ROTATE ? 4 : 0, A.model_margin);
 }
 
 template <int NC>
 __device__ __forceinline__ void rot_sincos(const NSArgs& A, const Row2<NC>& R, Vec<NC>& sn, Vec<NC>& cs) {
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    if (A.model == MMRE_ROTATE) canon_sincos(R.a.v[c] / A.phase_denom, &sn.v[c], &cs.v[c]);
+    if (A.model == MMRE_ROTATE) rel_sincos(R.a.v[c], A.phase_denom, &sn.v[c], &cs.v[c]);
     else sn.v[c] = cs.v[c] = 0.0f;
   }
 }
@@ -2003,8 +1948,8 @@ __device__ __forceinline__ void gen_owner_row(Ord& ord, bool active, const NSArg
                                                            // instances (rows backward) never step
   if (adagrad) {  // Adagrad (mmre_adagrad_step's arithmetic) on the row and its sum row
     Row2<NC> s, p;
-    vload(s.a, sa, d, lane);
-    if (two) vload(s.b, sb, d, lane); else vzero(s.b);
+    vload(s.a.v, sa, d, lane);
+    if (two) vload(s.b.v, sb, d, lane); else vzero(s.b);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       s.a.v[c] = adagrad_sum(s.a.v[c], dy.a.v[c]);
@@ -2145,7 +2090,7 @@ __device__ __forceinline__ void transe_row_grad(const NSArgs& A, const Row2<NC>&
   if (A.use_model_margin) g = -g;  // forward = m - s
   float nh = 1.0f, nt = 1.0f, nr = 1.0f;
   if (A.norm_flag) {
-    float a = vsq(H.a), b = vsq(T.a), c = vsq(R.a);
+    float a = vsq(H.a.v), b = vsq(T.a.v), c = vsq(R.a.v);
     wave_sum3(a, b, c);
     nh = sqrtf(a); nt = sqrtf(b); nr = sqrtf(c);
   }
@@ -2256,45 +2201,18 @@ __global__ __launch_bounds__(256) void k_rows_slots(NSArgs A, const float* __res
 
 // ---------------------------------------------------------------------------------------
 // Host side. Every kernel above is named in one place, its launcher (launch_*), which picks the
-// instance through with_nc / with_bool / with_gen_model; the dim -> NC rule is nc_for_dim. An entry
-// point fills one NSCall from its C arguments, validates it in the ABI's order and hands it on.
+// instance through with_nc / with_bool (dispatch.h) / with_gen_model; the dim -> NC rule is
+// nc_for_dim. An entry point fills one NSCall from its C arguments, validates it in the ABI's order
+// and hands it on.
 // ---------------------------------------------------------------------------------------
-#include <type_traits>
-
 using namespace mmre;
 
 constexpr int NC_FUSED = 8;  // widest instance of the TransE forward and the fused families (dim <= 512)
-constexpr int NC_ROWS = 32;  // ... of the rows backward (dim <= 2,048)
-
-// 64-float chunks per lane (the kernels' NC: 1, 2, 4, ... max_nc) for rows of `dim` floats; 0: no
-// instance. Up to 2,048 floats per row plane in the rows backward (the reference's examples train
+// ... of the rows backward: up to 2,048 floats per row plane (the reference's examples train
 // TransE at dim 1,024 with SigmoidLoss and cross sampling,
-// OpenKE/examples/train_transe_WN18_adv_sigmoidloss.py): the wide instances keep their rows in
+// OpenKE/examples/train_transe_WN18_adv_sigmoidloss.py). The wide instances keep their rows in
 // more registers (they may spill at NC 32; these rows are not a hot shape).
-static int nc_for_dim(int dim, int max_nc) {
-  for (int nc = 1; nc <= max_nc; nc *= 2)
-    if (dim <= nc * kWave) return nc;
-  return 0;
-}
-
-// The launches f(std::integral_constant<int, NC>) makes for nc == NC in 1, 2, 4, ... MAX_NC (no
-// wider instance is built) and their error; anything else is no shape of the family.
-template <int MAX_NC, int NC = 1, class F>
-static int with_nc(int nc, F&& f) {
-  if constexpr (NC > MAX_NC) {
-    return MMRE_ERR_SHAPE;
-  } else {
-    if (nc != NC) return with_nc<MAX_NC, 2 * NC>(nc, f);
-    f(std::integral_constant<int, NC>{});
-    MMRE_CHECK_LAUNCH();
-    return MMRE_OK;
-  }
-}
-
-template <class F>
-static int with_bool(bool b, F&& f) {
-  return b ? f(std::true_type{}) : f(std::false_type{});
-}
+constexpr int NC_ROWS = 32;
 
 // the models of the generic fused kernels
 template <class F>

@@ -8,20 +8,17 @@
 // on the pair alone) in registers, scores the true relation, then streams the relation rows and
 // counts pred(j) < pred(r) as it goes. Nothing R-sized is staged, so any n_rel >= 1 works.
 //
-// The arithmetic is pinned to ns.hip's row_score (the chain behind model.predict on this
-// library): element lane + 64 c of a row is lane `lane`'s c-th term, the lane partial is the
-// sum of its terms in increasing c starting from 0, the row's score is the butterfly wave_sum of
-// the partials; TransE divides h, r, t by max(sqrt(wave_sum(x^2)), 1e-12) before (h + r) - t
-// (and by 1.0f, exactly, without norm_flag), RotatE rotates by canon_sincos(phase / phase_denom).
-// What is hoisted out of the (pair, relation) loop is the same operations on the same operands,
-// done once: per pair h / |h| and t / |t| (TransE), the four products h* t* (ComplEx); per
+// The arithmetic is the row-wise chain of row_chain.h (the chain behind model.predict on this
+// library). What is hoisted out of the (pair, relation) loop is the same operations on the same
+// operands, done once: per pair h / |h| and t / |t| (TransE), the four products h* t* (ComplEx); per
 // relation r / |r| (TransE, norm_flag) and sin / cos (RotatE), by a prologue into the workspace.
 // So a prediction here and mmre_ns_forward's for the same row agree bit for bit, the fused
 // evaluation and the reference-shaped loop (predict -> testRel) rank identically, and the tests
 // are exact.
 #include <math.h>
 
-#include "mmre_common.h"
+#include "dispatch.h"
+#include "row_chain.h"
 
 namespace mmre {
 namespace {
@@ -44,8 +41,8 @@ struct RelArgs {
   float *truth, *scores;
 };
 
-// Per-relation values, one wave per relation: r / max(|r|, 1e-12) (TransE with norm_flag: the
-// norm row_score forms per row, ns.hip:75-81) or sin / cos of r / phase_denom (RotatE).
+// Per-relation values, one wave per relation: r / |r| (TransE with norm_flag: the chain's norm)
+// or sin / cos of r / phase_denom (RotatE).
 __global__ __launch_bounds__(256) void k_rel_prep(int rotate, const float* __restrict__ rel, int64_t n_rel, int d,
                                                   float phase_denom, float* __restrict__ work) {
   const int lane = threadIdx.x & 63;
@@ -54,37 +51,13 @@ __global__ __launch_bounds__(256) void k_rel_prep(int rotate, const float* __res
   const float* rv = rel + j * d;
   if (rotate) {
     float* o = work + j * 2 * d;
-    for (int k = lane; k < d; k += kWave) {
-      float s, c;
-      canon_sincos(rv[k] / phase_denom, &s, &c);
-      o[k] = s;
-      o[d + k] = c;
-    }
+    for (int k = lane; k < d; k += kWave) rel_sincos(rv[k], phase_denom, &o[k], &o[d + k]);
     return;
   }
   float c = 0.0f;
   for (int k = lane; k < d; k += kWave) c += rv[k] * rv[k];
-  const float nr = fmaxf(sqrtf(wave_sum(c)), 1e-12f);
+  const float nr = norm_of_sq(wave_sum(c));
   for (int k = lane; k < d; k += kWave) work[j * d + k] = rv[k] / nr;
-}
-
-// element lane + 64 c of a row in v[c], 0 past the row's end
-template <int NC>
-__device__ __forceinline__ void rp_load(float (&v)[NC], const float* __restrict__ row, int d, int lane) {
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int k = lane + c * kWave;
-    v[c] = k < d ? row[k] : 0.0f;
-  }
-}
-
-// max(|row|_2, 1e-12) with row_score's partial order
-template <int NC>
-__device__ __forceinline__ float rp_norm(const float (&v)[NC]) {
-  float a = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) a += v[c] * v[c];  // padding adds +0: the sum is unchanged
-  return fmaxf(sqrtf(wave_sum(a)), 1e-12f);
 }
 
 // What a pair contributes to every one of its R rows.
@@ -100,12 +73,12 @@ template <int MODEL, int NC>
 __device__ __forceinline__ void pair_load(PairCtx<MODEL, NC>& P, const RelArgs& A, int64_t h, int64_t t, int lane) {
   const int d = A.dim;
   if constexpr (MODEL == MMRE_TRANSE_L1 || MODEL == MMRE_TRANSE_L2) {
-    rp_load(P.q[0], A.ent + h * d, d, lane);
-    rp_load(P.q[1], A.ent + t * d, d, lane);
+    vload(P.q[0], A.ent + h * d, d, lane);
+    vload(P.q[1], A.ent + t * d, d, lane);
     float nh = 1.0f, nt = 1.0f;
     if (A.norm_flag) {
-      nh = rp_norm(P.q[0]);
-      nt = rp_norm(P.q[1]);
+      nh = row_norm(P.q[0]);
+      nt = row_norm(P.q[1]);
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -113,14 +86,14 @@ __device__ __forceinline__ void pair_load(PairCtx<MODEL, NC>& P, const RelArgs& 
       P.q[1][c] = P.q[1][c] / nt;
     }
   } else if constexpr (MODEL == MMRE_DISTMULT) {
-    rp_load(P.q[0], A.ent + h * d, d, lane);
-    rp_load(P.q[1], A.ent + t * d, d, lane);
+    vload(P.q[0], A.ent + h * d, d, lane);
+    vload(P.q[1], A.ent + t * d, d, lane);
   } else if constexpr (MODEL == MMRE_COMPLEX) {
     float hr[NC], hi[NC], tr[NC], ti[NC];
-    rp_load(hr, A.ent + h * d, d, lane);
-    rp_load(hi, A.ent_im + h * d, d, lane);
-    rp_load(tr, A.ent + t * d, d, lane);
-    rp_load(ti, A.ent_im + t * d, d, lane);
+    vload(hr, A.ent + h * d, d, lane);
+    vload(hi, A.ent_im + h * d, d, lane);
+    vload(tr, A.ent + t * d, d, lane);
+    vload(ti, A.ent_im + t * d, d, lane);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       P.q[0][c] = hr[c] * tr[c];
@@ -129,57 +102,41 @@ __device__ __forceinline__ void pair_load(PairCtx<MODEL, NC>& P, const RelArgs& 
       P.q[3][c] = hi[c] * tr[c];
     }
   } else {
-    rp_load(P.q[0], A.ent + h * 2 * d, d, lane);
-    rp_load(P.q[1], A.ent + h * 2 * d + d, d, lane);
-    rp_load(P.q[2], A.ent + t * 2 * d, d, lane);
-    rp_load(P.q[3], A.ent + t * 2 * d + d, d, lane);
+    vload(P.q[0], A.ent + h * 2 * d, d, lane);
+    vload(P.q[1], A.ent + h * 2 * d + d, d, lane);
+    vload(P.q[2], A.ent + t * 2 * d, d, lane);
+    vload(P.q[3], A.ent + t * 2 * d + d, d, lane);
   }
 }
 
-// This lane's partial of the row (pair, relation j): row_score's terms in row_score's order.
+// This lane's partial of the row (pair, relation j).
 template <int MODEL, int NC>
 __device__ __forceinline__ float rel_partial(const PairCtx<MODEL, NC>& P, const RelArgs& A, int64_t j, int lane) {
   const int d = A.dim;
   float r0[NC], r1[NC];
   if constexpr (MODEL == MMRE_TRANSE_L1 || MODEL == MMRE_TRANSE_L2) {
-    // without norm_flag row_score divides by 1.0f: the raw row is the quotient
-    rp_load(r0, (A.norm_flag ? A.work : A.rel) + j * d, d, lane);
+    // without norm_flag the raw row is the quotient
+    vload(r0, (A.norm_flag ? A.work : A.rel) + j * d, d, lane);
   } else if constexpr (MODEL == MMRE_DISTMULT) {
-    rp_load(r0, A.rel + j * d, d, lane);
+    vload(r0, A.rel + j * d, d, lane);
   } else if constexpr (MODEL == MMRE_COMPLEX) {
-    rp_load(r0, A.rel + j * d, d, lane);
-    rp_load(r1, A.rel_im + j * d, d, lane);
+    vload(r0, A.rel + j * d, d, lane);
+    vload(r1, A.rel_im + j * d, d, lane);
   } else {
-    rp_load(r0, A.work + j * 2 * d, d, lane);      // sin
-    rp_load(r1, A.work + j * 2 * d + d, d, lane);  // cos
+    vload(r0, A.work + j * 2 * d, d, lane);      // sin
+    vload(r1, A.work + j * 2 * d + d, d, lane);  // cos
   }
-  float acc = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    float term;
-    if constexpr (MODEL == MMRE_TRANSE_L1 || MODEL == MMRE_TRANSE_L2) {
-      const float x = (P.q[0][c] + r0[c]) - P.q[1][c];
-      term = MODEL == MMRE_TRANSE_L1 ? fabsf(x) : x * x;
-    } else if constexpr (MODEL == MMRE_DISTMULT) {
-      term = (P.q[0][c] * r0[c]) * P.q[1][c];
-    } else if constexpr (MODEL == MMRE_COMPLEX) {
-      term = P.q[0][c] * r0[c] + P.q[1][c] * r0[c] + P.q[2][c] * r1[c] - P.q[3][c] * r1[c];
-    } else {
-      const float re = P.q[0][c] * r1[c] - P.q[1][c] * r0[c] - P.q[2][c];
-      const float im = P.q[0][c] * r0[c] + P.q[1][c] * r1[c] - P.q[3][c];
-      term = sqrtf(re * re + im * im);
-    }
-    acc = lane + c * kWave < d ? acc + term : acc;  // a lane adds only the elements it owns
-  }
-  return acc;
+  return lane_partial<NC>(d, lane, [&](int c) {
+    if constexpr (MODEL <= MMRE_DISTMULT) return row_term<MODEL>(P.q[0][c], r0[c], P.q[1][c]);
+    else if constexpr (MODEL == MMRE_COMPLEX)
+      return complex_term(P.q[0][c], P.q[1][c], P.q[2][c], P.q[3][c], r0[c], r1[c]);
+    else return row_term<MODEL>(P.q[0][c], P.q[1][c], r0[c], r1[c], P.q[2][c], P.q[3][c]);
+  });
 }
 
-// partial -> the row's raw score s -> predict's value
 template <int MODEL>
 __device__ __forceinline__ float rel_finish(float acc, int pred_kind, float margin) {
-  float s = wave_sum(acc);
-  if constexpr (MODEL == MMRE_TRANSE_L2) s = sqrtf(s);
-  return apply_pred(pred_kind, margin, s);
+  return row_finish(acc, MODEL == MMRE_TRANSE_L2, pred_kind, margin);
 }
 
 template <int MODEL, int NC>
@@ -241,16 +198,13 @@ __global__ __launch_bounds__(256) void k_rel_sweep(RelArgs A) {
   }
 }
 
-template <int MODEL>
-int launch_sweep(const RelArgs& A, hipStream_t st) {
+int launch_sweep(int model, const RelArgs& A, hipStream_t st) {
   const dim3 grid((unsigned)((A.n_query + RP_WAVES - 1) / RP_WAVES)), block(64 * RP_WAVES);
-  const int nc = (A.dim + kWave - 1) / kWave;
-  if (nc <= 1) hipLaunchKernelGGL((k_rel_sweep<MODEL, 1>), grid, block, 0, st, A);
-  else if (nc <= 2) hipLaunchKernelGGL((k_rel_sweep<MODEL, 2>), grid, block, 0, st, A);
-  else if (nc <= 4) hipLaunchKernelGGL((k_rel_sweep<MODEL, 4>), grid, block, 0, st, A);
-  else hipLaunchKernelGGL((k_rel_sweep<MODEL, 8>), grid, block, 0, st, A);
-  MMRE_CHECK_LAUNCH();
-  return MMRE_OK;
+  return with_model(model, [&](auto model_) {
+    return with_nc<RP_MAXDIM / kWave>(nc_for_dim(A.dim, RP_MAXDIM / kWave), [&](auto nc_) {
+      hipLaunchKernelGGL((k_rel_sweep<decltype(model_)::value, decltype(nc_)::value>), grid, block, 0, st, A);
+    });
+  });
 }
 
 }  // namespace
@@ -315,11 +269,5 @@ extern "C" int mmre_rel_evaluate(int model, int norm_flag, int pred_kind, float 
                        model == MMRE_ROTATE ? 1 : 0, d_rel, n_rel, dim, phase_denom, (float*)d_work);
     MMRE_CHECK_LAUNCH();
   }
-  switch (model) {
-    case MMRE_TRANSE_L1: return launch_sweep<MMRE_TRANSE_L1>(A, st);
-    case MMRE_TRANSE_L2: return launch_sweep<MMRE_TRANSE_L2>(A, st);
-    case MMRE_DISTMULT: return launch_sweep<MMRE_DISTMULT>(A, st);
-    case MMRE_COMPLEX: return launch_sweep<MMRE_COMPLEX>(A, st);
-    default: return launch_sweep<MMRE_ROTATE>(A, st);
-  }
+  return launch_sweep(model, A, st);
 }

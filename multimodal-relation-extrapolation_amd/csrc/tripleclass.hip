@@ -11,10 +11,9 @@
 //                   sampler_openke.h's (Corrupt.h:7-83), looked up with key_block: test triples are
 //                   not train rows, so there is no per-row block table to read.
 //   k_tc_score      one wave per test triple scores the positive row and its negative with the
-//                   row-score chain of ns.hip / relpred.hip (lane-strided partials, butterfly
-//                   wave_sum, TransE's norms and quotients, RotatE's canon_sincos) followed by
-//                   apply_pred: bit for bit model.predict in 'normal' mode. A table row the two
-//                   triples share (the relation and the kept entity: two of three) is loaded once.
+//                   row-wise chain of row_chain.h followed by apply_pred: bit for bit
+//                   model.predict in 'normal' mode. A table row the two triples share (the
+//                   relation and the kept entity: two of three) is loaded once.
 //   k_tc_count / k_tc_best / k_tc_result   the threshold search without a sort. For a candidate c
 //                   among the scores, P(c) = #{positives <= c}, A(c) = P(c) + #{negatives <= c};
 //                   the accuracy of the rule `score <= c` is (2 P + F - A) / T (F negatives, T all),
@@ -31,7 +30,8 @@
 // counted in n_nan. -0 and +0 are one group (reported as +0).
 #include <math.h>
 
-#include "mmre_common.h"
+#include "dispatch.h"
+#include "row_chain.h"
 #include "sampler_openke.h"
 
 namespace mmre {
@@ -93,18 +93,8 @@ struct TcScoreArgs {
   float *pos, *neg;
 };
 
-// element lane + 64 c of a row in v[c], 0 past the row's end
-template <int NC>
-__device__ __forceinline__ void tc_load(float (&v)[NC], const float* __restrict__ row, int d, int lane) {
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int k = lane + c * kWave;
-    v[c] = k < d ? row[k] : 0.0f;
-  }
-}
-
 // One table row as the score uses it, a[.] and b[.]:
-//   TransE   a = x / max(|x|, 1e-12) (norm_flag) or x      DistMult a = x
+//   TransE   a = x / |x| (norm_flag) or x                   DistMult a = x
 //   ComplEx  a = re, b = im                                 RotatE   entity a = re, b = im;
 //                                                                    relation a = sin, b = cos
 template <int MODEL, int NC>
@@ -114,11 +104,8 @@ struct TcRow {
 
 template <int MODEL, int NC>
 __device__ __forceinline__ void tc_normalise(TcRow<MODEL, NC>& X, int norm_flag) {
-  if (!norm_flag) return;  // row_score divides by 1.0f: the raw row is the quotient
-  float s = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) s += X.a[c] * X.a[c];  // padding adds +0: the sum is unchanged
-  const float n = fmaxf(sqrtf(wave_sum(s)), 1e-12f);
+  if (!norm_flag) return;  // the raw row is the quotient
+  const float n = row_norm(X.a);
 #pragma unroll
   for (int c = 0; c < NC; ++c) X.a[c] = X.a[c] / n;
 }
@@ -127,64 +114,37 @@ template <int MODEL, int NC>
 __device__ __forceinline__ void tc_load_ent(TcRow<MODEL, NC>& X, const TcScoreArgs& A, int64_t e, int lane) {
   const int d = A.dim;
   if constexpr (MODEL == MMRE_TRANSE_L1 || MODEL == MMRE_TRANSE_L2) {
-    tc_load(X.a, A.ent + e * d, d, lane);
+    vload(X.a, A.ent + e * d, d, lane);
     tc_normalise(X, A.norm_flag);
   } else if constexpr (MODEL == MMRE_DISTMULT) {
-    tc_load(X.a, A.ent + e * d, d, lane);
+    vload(X.a, A.ent + e * d, d, lane);
   } else if constexpr (MODEL == MMRE_COMPLEX) {
-    tc_load(X.a, A.ent + e * d, d, lane);
-    tc_load(X.b, A.ent_im + e * d, d, lane);
+    vload(X.a, A.ent + e * d, d, lane);
+    vload(X.b, A.ent_im + e * d, d, lane);
   } else {
-    tc_load(X.a, A.ent + e * 2 * d, d, lane);
-    tc_load(X.b, A.ent + e * 2 * d + d, d, lane);
+    vload(X.a, A.ent + e * 2 * d, d, lane);
+    vload(X.b, A.ent + e * 2 * d + d, d, lane);
   }
 }
 
 template <int MODEL, int NC>
 __device__ __forceinline__ void tc_load_rel(TcRow<MODEL, NC>& X, const TcScoreArgs& A, int64_t r, int lane) {
   const int d = A.dim;
-  tc_load(X.a, A.rel + r * d, d, lane);
-  if constexpr (MODEL == MMRE_TRANSE_L1 || MODEL == MMRE_TRANSE_L2) {
-    tc_normalise(X, A.norm_flag);
-  } else if constexpr (MODEL == MMRE_COMPLEX) {
-    tc_load(X.b, A.rel_im + r * d, d, lane);
-  } else if constexpr (MODEL == MMRE_ROTATE) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      float s, co;
-      canon_sincos(X.a[c] / A.phase_denom, &s, &co);
-      X.a[c] = s;
-      X.b[c] = co;
-    }
-  }
+  vload(X.a, A.rel + r * d, d, lane);
+  if constexpr (MODEL == MMRE_TRANSE_L1 || MODEL == MMRE_TRANSE_L2) tc_normalise(X, A.norm_flag);
+  else if constexpr (MODEL == MMRE_COMPLEX) vload(X.b, A.rel_im + r * d, d, lane);
+  else if constexpr (MODEL == MMRE_ROTATE) vsincos(X.a, A.phase_denom, X.a, X.b);
 }
 
-// predict's value of the row (H, R, T): row_score's terms in row_score's order, then the transform
+// predict's value of the row (H, R, T)
 template <int MODEL, int NC>
 __device__ __forceinline__ float tc_predict(const TcRow<MODEL, NC>& H, const TcRow<MODEL, NC>& R,
                                             const TcRow<MODEL, NC>& T, const TcScoreArgs& A, int lane) {
-  float acc = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    float term;
-    if constexpr (MODEL == MMRE_TRANSE_L1 || MODEL == MMRE_TRANSE_L2) {
-      const float x = (H.a[c] + R.a[c]) - T.a[c];
-      term = MODEL == MMRE_TRANSE_L1 ? fabsf(x) : x * x;
-    } else if constexpr (MODEL == MMRE_DISTMULT) {
-      term = (H.a[c] * R.a[c]) * T.a[c];
-    } else if constexpr (MODEL == MMRE_COMPLEX) {
-      term = H.a[c] * T.a[c] * R.a[c] + H.b[c] * T.b[c] * R.a[c] + H.a[c] * T.b[c] * R.b[c] -
-             H.b[c] * T.a[c] * R.b[c];
-    } else {
-      const float re = H.a[c] * R.b[c] - H.b[c] * R.a[c] - T.a[c];
-      const float im = H.a[c] * R.a[c] + H.b[c] * R.b[c] - T.b[c];
-      term = sqrtf(re * re + im * im);
-    }
-    acc = lane + c * kWave < A.dim ? acc + term : acc;  // a lane adds only the elements it owns
-  }
-  float s = wave_sum(acc);
-  if constexpr (MODEL == MMRE_TRANSE_L2) s = sqrtf(s);
-  return apply_pred(A.pred_kind, A.margin, s);
+  const float acc = lane_partial<NC>(A.dim, lane, [&](int c) {
+    if constexpr (MODEL <= MMRE_DISTMULT) return row_term<MODEL>(H.a[c], R.a[c], T.a[c]);
+    else return row_term<MODEL>(H.a[c], H.b[c], R.a[c], R.b[c], T.a[c], T.b[c]);
+  });
+  return row_finish(acc, MODEL == MMRE_TRANSE_L2, A.pred_kind, A.margin);
 }
 
 template <int MODEL, int NC>
@@ -217,16 +177,13 @@ __global__ __launch_bounds__(256) void k_tc_score(TcScoreArgs A) {
   }
 }
 
-template <int MODEL>
-int launch_score(const TcScoreArgs& A, hipStream_t st) {
+int run_scores(int model, const TcScoreArgs& A, hipStream_t st) {
   const dim3 grid((unsigned)((A.n + TC_WAVES - 1) / TC_WAVES)), block(64 * TC_WAVES);
-  const int nc = (A.dim + kWave - 1) / kWave;
-  if (nc <= 1) hipLaunchKernelGGL((k_tc_score<MODEL, 1>), grid, block, 0, st, A);
-  else if (nc <= 2) hipLaunchKernelGGL((k_tc_score<MODEL, 2>), grid, block, 0, st, A);
-  else if (nc <= 4) hipLaunchKernelGGL((k_tc_score<MODEL, 4>), grid, block, 0, st, A);
-  else hipLaunchKernelGGL((k_tc_score<MODEL, 8>), grid, block, 0, st, A);
-  MMRE_CHECK_LAUNCH();
-  return MMRE_OK;
+  return with_model(model, [&](auto model_) {
+    return with_nc<TC_MAXDIM / kWave>(nc_for_dim(A.dim, TC_MAXDIM / kWave), [&](auto nc_) {
+      hipLaunchKernelGGL((k_tc_score<decltype(model_)::value, decltype(nc_)::value>), grid, block, 0, st, A);
+    });
+  });
 }
 
 // ----------------------------------------------------------------- threshold search ----
@@ -412,16 +369,6 @@ int run_negatives(const TcNegArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_tc_negatives, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st, a);
   MMRE_CHECK_LAUNCH();
   return MMRE_OK;
-}
-
-int run_scores(int model, const TcScoreArgs& A, hipStream_t st) {
-  switch (model) {
-    case MMRE_TRANSE_L1: return launch_score<MMRE_TRANSE_L1>(A, st);
-    case MMRE_TRANSE_L2: return launch_score<MMRE_TRANSE_L2>(A, st);
-    case MMRE_DISTMULT: return launch_score<MMRE_DISTMULT>(A, st);
-    case MMRE_COMPLEX: return launch_score<MMRE_COMPLEX>(A, st);
-    default: return launch_score<MMRE_ROTATE>(A, st);
-  }
 }
 
 int run_threshold(const float* pos, int64_t n_pos, const float* neg, int64_t n_neg, int have_thr, float thr,
