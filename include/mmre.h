@@ -901,6 +901,18 @@ int mmre_extractor_nodes(int dim, const float* d_pack, const float* d_sym_emb, c
 int mmre_extractor_encode(int dim, const float* d_pack, float ln_eps, const float* d_left, const int64_t* d_li,
                           const float* d_right, const int64_t* d_ri, int64_t n_rows, const float* d_targets,
                           const int64_t* d_row_target, int normalize, float* d_out_g, float* d_score, void* stream);
+/* mmre_extractor_encode with a cap on the launch: the kernel is persistent, its
+ * workgroups walk the 64-row tiles with stride gridDim.x, and the grid is
+ * min(tiles, resident workgroups) -- or, with max_blocks > 0, min(that, max_blocks)
+ * (max_blocks <= 0: exactly mmre_extractor_encode). The results do not depend on the
+ * grid; the cap lets a small input give a workgroup many tiles. */
+int mmre_extractor_encode_capped(int dim, const float* d_pack, float ln_eps, const float* d_left, const int64_t* d_li,
+                                 const float* d_right, const int64_t* d_ri, int64_t n_rows, const float* d_targets,
+                                 const int64_t* d_row_target, int normalize, float* d_out_g, float* d_score,
+                                 int max_blocks, void* stream);
+/* Workgroups mmre_extractor_encode launches for (dim, n_rows) on the current device
+ * (the value the launch itself uses); -1 for an unsupported dim or n_rows <= 0. */
+int64_t mmre_extractor_encode_blocks(int dim, int64_t n_rows);
 /* d_targets[t] = mean_s v[t][s] / (normalize ? |v[t][s]| : 1) for d_vecs (n_sets, n_samples, dim),
  * n_samples <= 64: the sklearn-normalised mean relation vector of ZSL scoring, or
  * the support mean of Extractor.forward (:101). */
@@ -1003,6 +1015,8 @@ int mmre_m3ae_linear_tile(int64_t m, int n);
  *  A(i, k) = d_a[i sam + k sak], B(k, j) = d_b[k sbk + j sbn] (transposes *
  *  are strides). One launch: 32 x 32 MFMA tiles, K split over             *
  *  mmre_gemm_splits(m, n, k) waves of a workgroup, summed in slice order. *
+ *  m == 0 or n == 0 is a no-op (the NULL pointers of empty tensors are    *
+ *  accepted); k == 0 writes the bias rows (or zeros).                     *
  * ====================================================================== */
 int mmre_gemm_splits(int64_t m, int64_t n, int64_t k);
 int mmre_gemm_f32(const float* d_a, int64_t sam, int64_t sak, const float* d_b, int64_t sbk, int64_t sbn, int64_t m,
@@ -1020,10 +1034,12 @@ int mmre_sn_weight(const float* d_w, int out, int in, float* d_u, float* d_v, in
 int mmre_sn_weight_backward(const float* d_g, const float* d_w, int out, int in, const float* d_u, const float* d_v,
                             const float* d_sigma, float* d_gw, void* stream);
 /* LayerNormalization (module/submodule.py:58-77): (z - mean) / (std_unbiased + eps) * a + b
- * per row of d_z (n_rows, d); d == 1 is the identity. */
+ * per row of d_z (n_rows, d); d == 1 is the identity. n_rows == 0 is a no-op (d_z / d_out
+ * may be NULL then). */
 int mmre_layernorm_unbiased(const float* d_z, int64_t n_rows, int d, const float* d_a, const float* d_b, float eps,
                             float* d_out, void* stream);
-/* Its backward for dL/dout = d_g: d_gz (n_rows, d), d_ga, d_gb (d). d_work: n_rows * d floats. */
+/* Its backward for dL/dout = d_g: d_gz (n_rows, d), d_ga, d_gb (d). d_work: n_rows * d floats.
+ * n_rows == 0 zeroes d_ga / d_gb (the row buffers may be NULL then). */
 int mmre_layernorm_unbiased_backward(const float* d_g, const float* d_z, int64_t n_rows, int d, const float* d_a,
                                      float eps, float* d_gz, float* d_ga, float* d_gb, float* d_work, void* stream);
 

@@ -494,12 +494,12 @@ struct XDispatch {
     MMRE_CHECK_LAUNCH();
     return MMRE_OK;
   }
-  static int encode(const float* pack, float ln_eps, const float* left, const int64_t* li, const float* right,
-                    const int64_t* ri, int64_t n_rows, const float* targets, const int64_t* row_target, int normalize,
-                    float* out_g, float* score, hipStream_t st) {
-    const int64_t tiles = (n_rows + 63) / 64;
-    static int resident = 0;
-    if (!resident) {
+  // Workgroups of k_extractor_encode<D> the device holds at once (CUs x occupancy), found on
+  // the first call and kept: the launch and the mmre_extractor_encode_blocks query read this
+  // one value.
+  static int resident() {
+    static int r = 0;
+    if (!r) {
       int dev = 0, cus = 256, per = 0;
       if (hipGetDevice(&dev) == hipSuccess) {
         int v = 0;
@@ -508,9 +508,21 @@ struct XDispatch {
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void*>(k_extractor_encode<D>),
                                                        256, 0) != hipSuccess || per <= 0)
         per = 1;
-      resident = cus * per;
+      r = cus * per;
     }
-    const unsigned blocks = (unsigned)(tiles < resident ? tiles : resident);
+    return r;
+  }
+  // min(tiles, resident), and at most max_blocks when that is positive
+  static int64_t grid(int64_t n_rows, int max_blocks) {
+    const int64_t tiles = (n_rows + 63) / 64, res = resident();
+    int64_t blocks = tiles < res ? tiles : res;
+    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+    return blocks;
+  }
+  static int encode(const float* pack, float ln_eps, const float* left, const int64_t* li, const float* right,
+                    const int64_t* ri, int64_t n_rows, const float* targets, const int64_t* row_target, int normalize,
+                    float* out_g, float* score, int max_blocks, hipStream_t st) {
+    const unsigned blocks = (unsigned)grid(n_rows, max_blocks);
     hipLaunchKernelGGL(k_extractor_encode<D>, dim3(blocks), dim3(256), 0, st, pack, ln_eps, left, li, right, ri,
                        n_rows, targets, row_target, normalize, out_g, score);
     MMRE_CHECK_LAUNCH();
@@ -568,14 +580,35 @@ extern "C" int mmre_extractor_nodes(int dim, const float* d_pack, const float* d
                              (hipStream_t)stream));
 }
 
+extern "C" int mmre_extractor_encode_capped(int dim, const float* d_pack, float ln_eps, const float* d_left,
+                                            const int64_t* d_li, const float* d_right, const int64_t* d_ri,
+                                            int64_t n_rows, const float* d_targets, const int64_t* d_row_target,
+                                            int normalize, float* d_out_g, float* d_score, int max_blocks,
+                                            void* stream) {
+  if (!d_pack || !d_left || !d_li || !d_right || !d_ri || n_rows <= 0 || (!d_out_g && !d_score)) return MMRE_ERR_ARG;
+  if (d_score && !d_targets) return MMRE_ERR_ARG;
+  MMRE_X_DISPATCH(dim, encode(d_pack, ln_eps, d_left, d_li, d_right, d_ri, n_rows, d_targets, d_row_target, normalize,
+                              d_out_g, d_score, max_blocks, (hipStream_t)stream));
+}
+
 extern "C" int mmre_extractor_encode(int dim, const float* d_pack, float ln_eps, const float* d_left,
                                      const int64_t* d_li, const float* d_right, const int64_t* d_ri, int64_t n_rows,
                                      const float* d_targets, const int64_t* d_row_target, int normalize,
                                      float* d_out_g, float* d_score, void* stream) {
-  if (!d_pack || !d_left || !d_li || !d_right || !d_ri || n_rows <= 0 || (!d_out_g && !d_score)) return MMRE_ERR_ARG;
-  if (d_score && !d_targets) return MMRE_ERR_ARG;
-  MMRE_X_DISPATCH(dim, encode(d_pack, ln_eps, d_left, d_li, d_right, d_ri, n_rows, d_targets, d_row_target, normalize,
-                              d_out_g, d_score, (hipStream_t)stream));
+  return mmre_extractor_encode_capped(dim, d_pack, ln_eps, d_left, d_li, d_right, d_ri, n_rows, d_targets,
+                                      d_row_target, normalize, d_out_g, d_score, 0, stream);
+}
+
+extern "C" int64_t mmre_extractor_encode_blocks(int dim, int64_t n_rows) {
+  if (n_rows <= 0) return -1;
+  switch (dim) {
+    case 64: return XDispatch<64>::grid(n_rows, 0);
+    case 100: return XDispatch<100>::grid(n_rows, 0);
+    case 128: return XDispatch<128>::grid(n_rows, 0);
+    case 200: return XDispatch<200>::grid(n_rows, 0);
+    case 256: return XDispatch<256>::grid(n_rows, 0);
+    default: return -1;
+  }
 }
 
 extern "C" int mmre_extractor_targets(const float* d_vecs, int64_t n_sets, int n_samples, int dim, int normalize,

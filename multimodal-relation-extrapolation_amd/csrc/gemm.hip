@@ -115,8 +115,9 @@ extern "C" int mmre_gemm_splits(int64_t m, int64_t n, int64_t k) {
 
 extern "C" int mmre_gemm_f32(const float* d_a, int64_t sam, int64_t sak, const float* d_b, int64_t sbk, int64_t sbn,
                              int64_t m, int64_t n, int64_t k, const float* d_bias, float* d_c, void* stream) {
-  if (m < 0 || n < 0 || k < 0 || m > 0x7fffffe0LL || n > 0x7fffffe0LL || !d_c || (k > 0 && (!d_a || !d_b)))
-    return MMRE_ERR_ARG;
+  if (m < 0 || n < 0 || k < 0 || m > 0x7fffffe0LL || n > 0x7fffffe0LL) return MMRE_ERR_ARG;
+  if (m == 0 || n == 0) return MMRE_OK;  // empty output: no element is touched, empty tensors' NULLs are fine
+  if (!d_c || (k > 0 && (!d_a || !d_b))) return MMRE_ERR_ARG;
   return gemm_launch((hipStream_t)stream, d_a, sam, sak, d_b, sbk, sbn, m, n, k, nullptr, d_bias, d_c, nullptr,
                      nullptr);
 }

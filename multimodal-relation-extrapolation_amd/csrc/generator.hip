@@ -189,14 +189,19 @@ __global__ __launch_bounds__(256) void k_gen_ln_bwd(const float* __restrict__ go
     if (lane == 0) { gz[row] = gr[0]; zhat[row] = 0.0f; }
     return;
   }
-  float s = 0.0f;
-  for (int k = lane; k < D; k += 64) s += zr[k];
+  // The row's arithmetic runs in float64. The two terms of dL/dz cancel down to eps / d of
+  // their size wherever g - mean(g) is parallel to c -- always at D = 2, where both span the
+  // one direction orthogonal to (1, 1) -- so a float32 rounding of either term (1e-7 of it) is
+  // 1e-7 d / eps = 1e-4 d of the result, and every weight gradient behind it inherits that.
+  // A handful of float64 operations per element of a kernel that is bound by its launch.
+  double s = 0.0;
+  for (int k = lane; k < D; k += 64) s += (double)zr[k];
 #pragma unroll
   for (int sh = 32; sh >= 1; sh >>= 1) s += __shfl_xor(s, sh);
-  const float mu = s / (float)D;
-  float v = 0.0f, sg = 0.0f, sgc = 0.0f;
+  const double mu = s / (double)D;
+  double v = 0.0, sg = 0.0, sgc = 0.0;
   for (int k = lane; k < D; k += 64) {
-    const float c = zr[k] - mu, g = gr[k] * ln_a[k];
+    const double c = (double)zr[k] - mu, g = (double)gr[k] * (double)ln_a[k];
     v += c * c;
     sg += g;
     sgc += g * c;
@@ -207,13 +212,13 @@ __global__ __launch_bounds__(256) void k_gen_ln_bwd(const float* __restrict__ go
     sg += __shfl_xor(sg, sh);
     sgc += __shfl_xor(sgc, sh);
   }
-  const float sd = sqrtf(v / (float)(D - 1)), d = sd + eps;
-  const float mg = sg / (float)D;
-  const float coef = sgc / (d * d * sd * (float)(D - 1));
+  const double sd = sqrt(v / (double)(D - 1)), d = sd + (double)eps;
+  const double mg = sg / (double)D;
+  const double coef = sgc / (d * d * sd * (double)(D - 1));
   for (int k = lane; k < D; k += 64) {
-    const float c = zr[k] - mu;
-    gz[row * D + k] = (gr[k] * ln_a[k] - mg) / d - c * coef;
-    zhat[row * D + k] = c / d;
+    const double c = (double)zr[k] - mu;
+    gz[row * D + k] = (float)(((double)gr[k] * (double)ln_a[k] - mg) / d - c * coef);
+    zhat[row * D + k] = (float)(c / d);
   }
 }
 
@@ -432,8 +437,9 @@ extern "C" int mmre_sn_weight_backward(const float* d_g, const float* d_w, int o
 
 extern "C" int mmre_layernorm_unbiased(const float* d_z, int64_t n_rows, int d, const float* d_a, const float* d_b,
                                        float eps, float* d_out, void* stream) {
-  if (!d_z || !d_a || !d_b || !d_out || n_rows < 0 || d <= 0) return MMRE_ERR_ARG;
-  if (n_rows == 0) return MMRE_OK;
+  if (!d_a || !d_b || n_rows < 0 || d <= 0) return MMRE_ERR_ARG;
+  if (n_rows == 0) return MMRE_OK;  // no rows: d_z / d_out may be the NULLs of empty tensors
+  if (!d_z || !d_out) return MMRE_ERR_ARG;
   hipLaunchKernelGGL(k_gen_ln, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_z, d_a, d_b,
                      eps, n_rows, d, d_out);
   MMRE_CHECK_LAUNCH();
@@ -443,8 +449,14 @@ extern "C" int mmre_layernorm_unbiased(const float* d_z, int64_t n_rows, int d, 
 extern "C" int mmre_layernorm_unbiased_backward(const float* d_g, const float* d_z, int64_t n_rows, int d,
                                                 const float* d_a, float eps, float* d_gz, float* d_ga, float* d_gb,
                                                 float* d_work, void* stream) {
-  if (!d_g || !d_z || !d_a || !d_gz || !d_ga || !d_gb || !d_work || n_rows <= 0 || d <= 0) return MMRE_ERR_ARG;
+  if (!d_a || !d_ga || !d_gb || n_rows < 0 || d <= 0) return MMRE_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
+  if (n_rows == 0) {  // no rows (the row buffers may be the NULLs of empty tensors): zero a / b gradients
+    MMRE_CHECK(hipMemsetAsync(d_ga, 0, sizeof(float) * d, st));
+    MMRE_CHECK(hipMemsetAsync(d_gb, 0, sizeof(float) * d, st));
+    return MMRE_OK;
+  }
+  if (!d_g || !d_z || !d_gz || !d_work) return MMRE_ERR_ARG;
   hipLaunchKernelGGL(k_gen_ln_bwd, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, d_g, d_z, d_a, eps, n_rows,
                      d, d_gz, d_work);
   MMRE_CHECK_LAUNCH();

@@ -142,6 +142,8 @@ SIGNATURES = {
     "mmre_extractor_pack": (I32, [I32] + [P] * 15 + [P]),
     "mmre_extractor_nodes": (I32, [I32, P, P, P, P, I32, P, I64, P, P, P]),
     "mmre_extractor_encode": (I32, [I32, P, F32, P, P, P, P, I64, P, P, I32, P, P, P]),
+    "mmre_extractor_encode_capped": (I32, [I32, P, F32, P, P, P, P, I64, P, P, I32, P, P, I32, P]),
+    "mmre_extractor_encode_blocks": (I64, [I32, I64]),
     "mmre_extractor_targets": (I32, [P, I64, I32, I32, I32, P, P]),
     "mmre_rank_desc": (I32, [P, P, I64, P, P]),
     "mmre_extractor_train_inputs": (I32, [I32, P, P, P, P, I32, I64, F32, P, P, P, P, P, P, P, P, P]),

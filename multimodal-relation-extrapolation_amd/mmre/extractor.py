@@ -64,9 +64,13 @@ def node_tables(pack, dim: int, sym_emb, node_sym, conn, deg, want_left=True, wa
 
 
 def encode(pack, dim: int, ln_eps: float, left, li, right, ri, targets=None, row_target=None, normalize=True,
-           want_g=False, want_score=True):
-    """SupportEncoder(left[li] + right[ri]) -> (g (n, dim) or None, score (n,) or None)."""
+           want_g=False, want_score=True, max_blocks=None):
+    """SupportEncoder(left[li] + right[ri]) -> (g (n, dim) or None, score (n,) or None).
+    max_blocks caps the persistent kernel's grid (None: min(tiles, resident workgroups), see
+    `encode_blocks`); the values do not depend on it."""
     require_cuda(pack, left, li, right, ri, targets, row_target)
+    if max_blocks is not None and int(max_blocks) < 1:
+        raise MMREError("max_blocks must be positive (or None for the default grid)")
     n = int(li.shape[0])
     dev = left.device
     g = torch.empty((n, dim), dtype=torch.float32, device=dev) if want_g else None
@@ -75,11 +79,22 @@ def encode(pack, dim: int, ln_eps: float, left, li, right, ri, targets=None, row
         return g, s
     if want_score and targets is None:
         raise MMREError("scores need targets")
-    call("mmre_extractor_encode", dim, ptr(pack), float(ln_eps), ptr(left), ptr(li.contiguous().long()), ptr(right),
-         ptr(ri.contiguous().long()), n, ptr(None if targets is None else _c(targets)),
-         ptr(None if row_target is None else row_target.contiguous().long()), int(bool(normalize)), ptr(g), ptr(s),
-         stream_ptr(dev))
+    args = (dim, ptr(pack), float(ln_eps), ptr(left), ptr(li.contiguous().long()), ptr(right),
+            ptr(ri.contiguous().long()), n, ptr(None if targets is None else _c(targets)),
+            ptr(None if row_target is None else row_target.contiguous().long()), int(bool(normalize)), ptr(g), ptr(s))
+    if max_blocks is None:
+        call("mmre_extractor_encode", *args, stream_ptr(dev))
+    else:
+        call("mmre_extractor_encode_capped", *args, int(max_blocks), stream_ptr(dev))
     return g, s
+
+
+def encode_blocks(dim: int, n_rows: int) -> int:
+    """Workgroups the default `encode` launch uses for n_rows rows of width dim."""
+    b = int(lib().mmre_extractor_encode_blocks(int(dim), int(n_rows)))
+    if b < 0:
+        raise MMREError(f"encode_blocks: dim {dim} not built (supported: {SUPPORTED_DIMS}) or n_rows <= 0")
+    return b
 
 
 def targets(vecs, normalize=True):

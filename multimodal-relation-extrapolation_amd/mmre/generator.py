@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ._lib import call, lib, ptr, require_cuda, stream_ptr
+from ._lib import MMREError, call, lib, ptr, require_cuda, stream_ptr
 
 
 class SNLinear(nn.Module):
@@ -82,7 +82,18 @@ class RelationGenerator(nn.Module):
         L0, L1, L2 = self.generate_fc_layer, self.des_rel_map_layer1, self.des_rel_map_layer2
         return [L0.weight_orig, L0.bias, L1.weight_orig, L1.bias, L2.weight_orig, L2.bias, self.ln_a, self.ln_b]
 
+    def _check_inputs(self, cls, noise):
+        """The kernels index cls / noise by (n, reduced_dim) / (n, noise_dim): anything else
+        would be read out of bounds on the device, so it is refused here (shapes only, no sync)."""
+        if cls.dim() != 2 or cls.shape[1] != self.reduced_dim:
+            raise MMREError(f"generator: cls must be (n, {self.reduced_dim}), got {tuple(cls.shape)}")
+        if noise.dim() != 2 or noise.shape[1] != self.noise_dim:
+            raise MMREError(f"generator: noise must be (n, {self.noise_dim}), got {tuple(noise.shape)}")
+        if cls.shape[0] != noise.shape[0]:
+            raise MMREError(f"generator: cls has {cls.shape[0]} rows, noise {noise.shape[0]}")
+
     def _run(self, cls, noise, acts=None):
+        self._check_inputs(cls, noise)
         n = int(cls.shape[0])
         L0, L1, L2 = self.generate_fc_layer, self.des_rel_map_layer1, self.des_rel_map_layer2
         dev = cls.device

@@ -35,11 +35,13 @@ def test_extractor_symbols_exported():
     from mmre import _lib
     L = ctypes.CDLL(_lib.LIB_PATH)
     for n in ("mmre_extractor_pack_size", "mmre_extractor_pack", "mmre_extractor_nodes", "mmre_extractor_encode",
-              "mmre_extractor_targets", "mmre_rank_desc"):
+              "mmre_extractor_encode_capped", "mmre_extractor_encode_blocks", "mmre_extractor_targets",
+              "mmre_rank_desc"):
         assert hasattr(L, n)
     lib = _lib.lib()
     assert lib.mmre_extractor_pack_size(7) == -1
     assert lib.mmre_extractor_pack_size(200) > 2 * 400 * 200
+    assert lib.mmre_extractor_encode_blocks(7, 100) == -1 and lib.mmre_extractor_encode_blocks(200, 0) == -1
 
 
 def test_extractor_requires_eval_mode():
