@@ -32,7 +32,10 @@ enum {
   MMRE_TRANSE_L2 = 1,
   MMRE_DISTMULT = 2,
   MMRE_COMPLEX = 3,
-  MMRE_ROTATE = 4
+  MMRE_ROTATE = 4,
+  /* TransH (mmre_transh_* only; the entry points above answer MMRE_ERR_MODEL for them) */
+  MMRE_TRANSH_L1 = 5,
+  MMRE_TRANSH_L2 = 6
 };
 enum { MMRE_HEAD_BATCH = 0, MMRE_TAIL_BATCH = 1 };
 /* Loss of the negative-sampling entry points (mmre_ns_opts_t) and the optimizer whose step the
@@ -280,6 +283,58 @@ int mmre_link_sweep_bf3_rows(int model, int pred_kind, float margin, const float
  * h_out[20] = {mrr, mr, hit10, hit3, hit1} x {filter, raw, filter_tc, raw_tc}. */
 int mmre_link_metrics(const int32_t* h_head_counts, const int32_t* h_tail_counts, int64_t n, int64_t stride,
                       float* h_out);
+
+/* ====================================================================== *
+ *  TransH (OpenKE/openke/module/model/TransH.py): link prediction with    *
+ *  entities projected on the hyperplane of the query's relation, and      *
+ *  predict for arbitrary rows. Models MMRE_TRANSH_L1 / MMRE_TRANSH_L2     *
+ *  (p_norm 1 / 2). Tables: entities (E, d), relations (R, d), the         *
+ *  hyperplane normals norm_vector (R, d).                                 *
+ * ====================================================================== */
+
+/* Bytes of d_work for mmre_transh_evaluate: the raw k-major and row-major entity copies, the
+ * normalised relation vectors, the (a, n) table of 2 * n_used * e_pad floats (TransH.py:68-76:
+ * a = e . w_hat, n = max(|e - a w_hat|, 1e-12) of TransH.py:54-56), the query planes of n_tiles
+ * padded tiles and the n_entries listed scores. O(n_used * E + E * d), never O(n_used * E * d).
+ * 0 for a non-positive size. */
+int64_t mmre_transh_workspace(int64_t n_ent, int64_t n_rel, int dim, int64_t n_tiles, int64_t n_used,
+                              int64_t n_entries);
+
+/* One TransH link-prediction evaluation, enqueued on `stream`: replaces the Tester loop
+ * (Tester.py:70-91: getHeadBatch / getTailBatch Test.h:36-53, TransH.predict TransH.py:109-115 =
+ * forward TransH.py:78-93 with _transfer :68-76 and _calc :52-66, testHead / testTail
+ * Test.h:65-192) for every query at once. Prologue (normalised vectors, the (a, n) table, query
+ * vectors), truth and filter pass, the sweep, the finalize pass.
+ * Queries (d_qh, d_qr, d_qt int64, d_qmode int8: MMRE_HEAD_BATCH / MMRE_TAIL_BATCH) in the
+ * caller's order. The plan orders them by relation so that every 128-row sweep tile holds one
+ * relation: d_perm[n_query] (int32) the stable order, d_tiles[n_tiles][3] (int32) = (relation,
+ * first row of d_perm, rows <= 128), d_used[n_used] (int32) the relations that have queries and
+ * d_rel_slot[n_rel] (int32) a relation's index in d_used or -1. A query no tile holds keeps
+ * raw counts of 0.
+ * Filter groups as mmre_link_truth_grouped takes them (d_grp_qoff NULL: no filtering). Type
+ * masks as mmre_link_truth takes them (NULL / NULL disables; Test.h:88-98).
+ * pred_kind 0: s; 1: m - (m - s), a model with a margin (TransH.py:109-115).
+ * Writes d_truth[n_query] = pred(truth) and d_counts int32 [4][n_query] = raw, filt, raw_tc,
+ * filt_tc: #{j != truth : pred(j) < pred(truth)}, strict, ties favour the truth (Test.h:83). */
+int mmre_transh_evaluate(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                         const float* d_rel, const float* d_norm, int64_t n_ent, int64_t n_rel, int dim,
+                         const int64_t* d_qh, const int64_t* d_qr, const int64_t* d_qt, const int8_t* d_qmode,
+                         int64_t n_query, const int32_t* d_perm, const int32_t* d_tiles, int64_t n_tiles,
+                         const int32_t* d_used, int64_t n_used, const int32_t* d_rel_slot,
+                         const int64_t* d_grp_qoff, const int32_t* d_grp_q, int64_t n_groups,
+                         const int64_t* d_filt_off, const int32_t* d_filt_ids, const int32_t* d_entry_q,
+                         int64_t n_entries, const uint32_t* d_type_head, const uint32_t* d_type_tail,
+                         int32_t* d_counts, float* d_truth, void* d_work, int64_t work_bytes, void* stream);
+
+/* TransH.predict / forward values of the rows (d_h[i], d_r[i], d_t[i]) (TransH.py:78-93,
+ * :109-115), bit for bit what mmre_transh_evaluate scores for the same triple and mode (so a
+ * rank recomputed from these values is the sweep's: Test.h:80-86). head_batch != 0: the
+ * grouping h + (r - t) of TransH.py:61-62, else (h + r) - t. pred_kind as apply_pred's 0 .. 4
+ * (4 = m - s, forward() of a model with a margin). A row with an id outside the tables gets NaN. */
+int mmre_transh_score_rows(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                           const float* d_rel, const float* d_norm, int64_t n_ent, int64_t n_rel, int dim,
+                           const int64_t* d_h, const int64_t* d_r, const int64_t* d_t, int64_t n_rows,
+                           int head_batch, float* d_out, void* stream);
 
 /* ====================================================================== *
  *  Relation prediction: every test pair (h, t) against every relation.   *

@@ -58,6 +58,10 @@ SIGNATURES = {
     "mmre_link_sweep_bf3_rows": (I32, [I32, I32, F32, P, I64, I64, I64, I64, P, P, P, P, P, P, I64, I64, I32, P, P,
                                        P, I64, P]),
     "mmre_link_metrics": (I32, [P, P, I64, I64, P]),
+    "mmre_transh_workspace": (I64, [I64, I64, I32, I64, I64, I64]),
+    "mmre_transh_evaluate": (I32, [I32, I32, I32, F32, P, P, P, I64, I64, I32, P, P, P, P, I64, P, P, I64, P, I64, P,
+                                   P, P, I64, P, P, P, I64, P, P, P, P, P, I64, P]),
+    "mmre_transh_score_rows": (I32, [I32, I32, I32, F32, P, P, P, I64, I64, I32, P, P, P, I64, I32, P, P]),
     "mmre_rel_workspace": (I64, [I32, I64, I32]),
     "mmre_rel_evaluate": (I32, [I32, I32, I32, F32, P, P, P, P, I64, I64, I32, F32, P, P, P, I64, P, P, P, P, P, P,
                                 I64, P]),

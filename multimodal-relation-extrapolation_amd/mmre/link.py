@@ -19,7 +19,8 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream_ptr
 
-MODEL_IDS = {"transe": 0, "transe_l2": 1, "distmult": 2, "complex": 3, "rotate": 4}
+MODEL_IDS = {"transe": 0, "transe_l2": 1, "distmult": 2, "complex": 3, "rotate": 4,
+             "transh": 5, "transh_l2": 6}  # TransH: mmre.transh (TransHSweep, score_rows) only
 HEAD, TAIL = 0, 1
 METRIC_NAMES = ["mrr", "mr", "hit10", "hit3", "hit1"]
 GROUPS = ["filter", "raw", "filter_tc", "raw_tc"]
@@ -38,6 +39,7 @@ class ScoreSpec:
     pred_kind: int = 0              # 0 s, 1 m-(m-s), 2 -s, 3 -(m-s)
     margin: float = 0.0
     phase_denom: float = 0.0        # RotatE
+    norm_vec: torch.Tensor | None = None   # TransH: the hyperplane normals (R, d)
 
 
 def rotate_phase_denom(margin: float, epsilon: float, dim: int) -> float:
@@ -197,6 +199,8 @@ class LinkSweep:
     """Device-resident link-prediction evaluator for one model snapshot."""
 
     def __init__(self, spec: ScoreSpec):
+        if spec.model in ("transh", "transh_l2"):
+            raise ValueError("TransH sweeps one relation per query tile: use mmre.transh.TransHSweep")
         self.spec = spec
         self.model_id = MODEL_IDS[spec.model]
         dev = spec.ent.device
@@ -523,9 +527,13 @@ def evaluate_link_prediction(spec: ScoreSpec, test_h, test_r, test_t, index: Fil
         if type_constrain:
             tm = index.type_masks()
             masks = tuple(torch.from_numpy(m).to(dev) for m in tm)
-    sw = LinkSweep(spec)
-    res = sw.run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)), torch.from_numpy(qm).to(dev), filt=filt,
-                 type_masks=masks)
+    if spec.model in ("transh", "transh_l2"):  # one relation per query tile, planned from qr here
+        from .transh import TransHSweep, plan_tiles
+        res = TransHSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
+                                    torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks, plan=plan_tiles(qr))
+    else:
+        res = LinkSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
+                                  torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks)
     counts = res["counts"].cpu().numpy()
     head, tail = counts[:, :n], counts[:, n:]
     return link_metrics(head, tail), (head, tail)
@@ -590,6 +598,9 @@ def evaluate_relation_prediction(spec: ScoreSpec, test_h, test_r, test_t, index:
     test_relation_prediction, as one fused evaluation. Without an index the filtered column
     equals the raw one. Returns (metrics {"filter": {...}, "raw": {...}}, counts (2, n) numpy
     [raw, filt][, scores (n, R) numpy])."""
+    if spec.model in ("transh", "transh_l2"):
+        raise NotImplementedError("relation prediction for TransH: every candidate relation projects both "
+                                  "entities on its own hyperplane; no TransH relation sweep is built yet")
     test_h, test_r, test_t = (np.asarray(x, np.int64) for x in (test_h, test_r, test_t))
     dev = spec.ent.device
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)

@@ -130,7 +130,10 @@ def evaluate_triple_classification(spec: ScoreSpec, test_h, test_r, test_t, trai
     """The whole task in one enqueued call (mmre_tc_evaluate): negatives of the test triples from
     thread 0's `seed_state`, both prediction arrays, and the best threshold (or the counts at a given
     one). Returns dict(accuracy, threshold, P, A, n_nan, n_pos, n_neg, neg_h, neg_t, pos_scores,
-    neg_scores (numpy), seed_state_after)."""
+    neg_scores (numpy), seed_state_after). A TransH spec composes the same result from
+    classification_negatives, mmre.transh.score_rows and best_threshold / accuracy_at."""
+    if spec.model in ("transh", "transh_l2"):
+        return _evaluate_transh(spec, test_h, test_r, test_t, train_index, seed_state, threshold)
     ent, rel, ent_im, rel_im = _tables(spec)
     dev = ent.device
     d = device_index(train_index, dev)
@@ -154,6 +157,21 @@ def evaluate_triple_classification(spec: ScoreSpec, test_h, test_r, test_t, trai
                    A=0, n_nan=0, n_pos=0, n_neg=0)
     else:
         res = _decode(out, n, n)
+    res.update(neg_h=neg_h.cpu().numpy(), neg_t=neg_t.cpu().numpy(), pos_scores=pos.cpu().numpy(),
+               neg_scores=neg.cpu().numpy(), seed_state_after=advance_state(seed_state, n))
+    return res
+
+
+def _evaluate_transh(spec, test_h, test_r, test_t, train_index, seed_state, threshold):
+    from .transh import score_rows
+    _lib.require_cuda(spec.ent)
+    dev = spec.ent.device
+    h, r, t = (_i64(x, dev) for x in (test_h, test_r, test_t))
+    n = int(h.shape[0])
+    neg_h, neg_t = classification_negatives(train_index, h, r, t, seed_state, device=dev)
+    pos = score_rows(spec, h, r, t)
+    neg = score_rows(spec, neg_h, r, neg_t)
+    res = best_threshold(pos, neg) if threshold is None else accuracy_at(pos, neg, threshold)
     res.update(neg_h=neg_h.cpu().numpy(), neg_t=neg_t.cpu().numpy(), pos_scores=pos.cpu().numpy(),
                neg_scores=neg.cpu().numpy(), seed_state_after=advance_state(seed_state, n))
     return res

@@ -129,6 +129,8 @@ class Trainer(object):
         if not (hasattr(m.model, "ns_spec") and hasattr(m.model, "_tables")):
             return None
         spec = m.model.ns_spec()
+        if spec is None:
+            return None  # no fused step for this model (TransH): train_one_step over autograd
         ent, rel, ent_im, rel_im = m.model._tables()
         generic = spec.model in OpenKETrainStep.GENERIC
         if not generic and (not hinge or adagrad is not None):

@@ -3,5 +3,6 @@ from .DistMult import DistMult
 from .Model import Model
 from .RotatE import RotatE
 from .TransE import TransE
+from .TransH import TransH
 
-__all__ = ["Model", "TransE", "DistMult", "ComplEx", "RotatE"]
+__all__ = ["Model", "TransE", "TransH", "DistMult", "ComplEx", "RotatE"]

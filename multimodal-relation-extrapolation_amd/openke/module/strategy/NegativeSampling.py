@@ -37,7 +37,9 @@ class NegativeSampling(Strategy):
 
     def forward(self, data):
         mode = data.get("mode", "normal")
-        if isinstance(self.loss, (MarginLoss, SoftplusLoss, SigmoidLoss)) and mode == "normal":
+        # (a model without a fused step -- ns_spec() None: TransH -- scores through model(data))
+        fused = isinstance(self.loss, (MarginLoss, SoftplusLoss, SigmoidLoss)) and mode == "normal"
+        if fused and self.model.ns_spec() is not None:
             ent, rel, ent_im, rel_im = self.model._tables()
             dev = ent.device
             h = data["batch_h"].to(dev)
