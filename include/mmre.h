@@ -336,6 +336,52 @@ int mmre_transh_score_rows(int model, int norm_flag, int pred_kind, float margin
                            const int64_t* d_h, const int64_t* d_r, const int64_t* d_t, int64_t n_rows,
                            int head_batch, float* d_out, void* stream);
 
+/* ---- TransH negative-sampling training (csrc/transh_train.hip) ----
+ * model(data) of TransH.py:52-107 in 'normal' mode for the B (1 + K) rows of a batch laid out
+ * [pos | neg_1 | ... | neg_K] (row b + (j + 1) B is negative j of positive b,
+ * NegativeSampling.py:23-32), MarginLoss(loss_margin, adv_temperature) of the split (adv_temperature
+ * <= 0: none) + regul_rate (mean h^2 + mean t^2 + mean r^2 + mean w^2) / 4 (TransH.py:98-107).
+ * model: MMRE_TRANSH_L1 / MMRE_TRANSH_L2 only (anything else: MMRE_ERR_MODEL; the mmre_ns_* entry
+ * points keep answering MMRE_ERR_MODEL for these two). use_model_margin: forward = model_margin - s.
+ * The arithmetic is the "TransH training chain" of DESIGN.md §3 (lane partials in increasing
+ * element, wave sums): a score here agrees with mmre_transh_score_rows to rounding, not bit for bit.
+ * Shapes: 1 <= dim <= 512 and 1 <= neg <= 512 (mmre_transh_ns_supported asks first); n_ent and
+ * n_rel below 2^31 and batch (1 + neg) below 2^28; else MMRE_ERR_SHAPE. Checks run before the
+ * first launch, in this order: model, null pointers (MMRE_ERR_ARG), shape. Every call only
+ * enqueues on `stream`: no allocation, no synchronisation, no read-back; the counters a call
+ * needs are zeroed by its own kernels. Ids are trusted to lie inside their tables. */
+
+/* 1 when the kernels exist for (model, dim, neg), else 0. */
+int mmre_transh_ns_supported(int model, int dim, int64_t neg);
+
+/* Floats of d_work for both calls below (the same buffer serves a forward and its gradient);
+ * -1 for a shape the calls answer MMRE_ERR_SHAPE to. Monotone in every argument. It reserves a
+ * record of dim floats for each of the 4 B (1 + K) (row, table) pairs; a sampler-made batch
+ * writes about (K + 4) B of them. */
+int64_t mmre_transh_ns_workspace(int64_t batch, int64_t neg, int64_t n_ent, int64_t n_rel, int dim);
+
+/* d_score[B (1 + K)] <- forward values, d_loss[0] <- the loss (per-positive partials summed in a
+ * fixed order: the same bits every run). Two launches. */
+int mmre_transh_ns_forward(int model, int norm_flag, float model_margin, int use_model_margin,
+                           const float* d_ent, const float* d_rel, const float* d_norm, int64_t n_ent,
+                           int64_t n_rel, int dim, const int64_t* d_h, const int64_t* d_t, const int64_t* d_r,
+                           int64_t batch, int64_t neg, float loss_margin, float adv_temperature,
+                           float regul_rate, float* d_score, float* d_loss, float* d_work, void* stream);
+
+/* d_grad_ent[n_ent x dim], d_grad_rel, d_grad_norm[n_rel x dim] <- d(loss)/d(table) times
+ * d_grad_loss[0], every row written (rows the batch does not touch: exactly 0), no float atomics,
+ * the same bits every run: contribution rows are stored once and summed per table row in an order
+ * fixed by the batch indices alone. d_score: what the forward wrote for the same arguments (the
+ * tables unchanged since). lr != 0: the owner of a touched row also applies plain SGD,
+ * p <- fma(-lr, g, p), in place -- parameters bit-identical to backward() + SGD.step(); the
+ * gradient tables are written all the same. lr == 0: the tables are only read. */
+int mmre_transh_ns_grad(int model, int norm_flag, float model_margin, int use_model_margin, float* d_ent,
+                        float* d_rel, float* d_norm, int64_t n_ent, int64_t n_rel, int dim, const int64_t* d_h,
+                        const int64_t* d_t, const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin,
+                        float adv_temperature, float regul_rate, const float* d_score, const float* d_grad_loss,
+                        float* d_grad_ent, float* d_grad_rel, float* d_grad_norm, float* d_work, float lr,
+                        void* stream);
+
 /* ====================================================================== *
  *  Relation prediction: every test pair (h, t) against every relation.   *
  *  Replaces, per evaluation, the loop getRelBatch (Test.h:55-62) +        *

@@ -1,0 +1,762 @@
+// transh_train.hip -- TransH negative-sampling training (OpenKE TransH.py:52-107 in 'normal' mode
+// under strategy/NegativeSampling.py:23-32 + MarginLoss.py:24-28): the fused loss and its
+// gradient into three dense tables (ent, rel, norm_vector), no float atomics, DESIGN.md §10h.
+//
+// Arithmetic (the "TransH training chain"): f32, -ffp-contract=off, a row's element
+// lane + 64 c in slot c, every sum a lane partial in increasing c then wave_sum (row_chain.h).
+//   w^ = w / max(|w|, 1e-12)   a_e = e . w^   p_e = e - a_e w^           (e = h, t)
+//   norm_flag: p^_e = p_e / max(|p_e|, 1e-12), r^ = r / max(|r|, 1e-12); else p^ = p, r^ = r
+//   x = (p^_h + r^) - p^_t     s = sum |x| (L1) or sqrt(sum x^2) (L2)    forward = s or m - s
+// Not the sequential-in-k chain of transh.hip: a training score need not be predict's bits.
+//
+// Backward, per row with g = d(loss)/d(score) (a model margin flips its sign):
+//   gx = g sign(x) (L1) or g x / s, 0 where s = 0 (L2)
+//   u_e = (+-gx - p^_e (p^_e . +-gx)) / |p_e|, +-gx / 1e-12 where clamped, +-gx without norm_flag
+//   dh = u_h - (u_h . w^) w^, dt likewise;  dw^ = -(u_h . w^) h - a_h u_h - (u_t . w^) t - a_t u_t
+//   dw = (dw^ - w^ (w^ . dw^)) / |w| or dw^ / 1e-12;  dr as u_e with r^ and |r|
+//
+// Forward (mmre_transh_ns_forward): one workgroup of four waves per positive b. Every wave holds
+// the positive's context in registers (its rows, the unit normal, both projections, r^); rows
+// j = wave, wave + 4, ... of [pos | neg_1 .. neg_K] (row b + j B) reuse whatever they share with it
+// -- the relation (and with it the normal), a projected entity when relation and entity both
+// match -- and load and project the rest, so any batch is scored right. Wave 0 then forms the
+// positive's hinge partial from the K + 1 scores in LDS; k_th_reduce sums the partials in a
+// fixed order.
+//
+// Gradient (mmre_transh_ns_grad): store-then-sum.
+//   k_th_coef     d(loss)/d(score) of every row (k_ns_row_coef's margin rule), counters zeroed
+//   k_th_records  same workgroup shape as the forward. Row i has four record slots 4 i + q
+//                 (q = h, t, r, w). Contributions to a row the positive shares are summed on chip
+//                 (registers in j order per wave, the four waves' sums in wave order through LDS)
+//                 into the positive's slots 4 b + q; a negative's slot is written only for a row
+//                 it does not share. Every record carries its rows' regulariser term, so the
+//                 owners read records and never parameters. Keys: ekey[2 i + (0 | 1)] the entity
+//                 of slots 4 i + (0 | 1) or -1, rkey[i] the relation of slots 4 i + (2, 3) or -1.
+//   k_th_scan / k_th_fill   the entity table's inverted index (counts by integer atomics, one
+//                 exclusive scan, lists filled in arrival order)
+//   k_th_owner    entity rows: one wave per row orders its list by slot id and sums it. Relation
+//                 and normal rows keep no list: wave (r, seg) scans rkey over batch rows
+//                 [seg TH_SEG, (seg + 1) TH_SEG) with ballots, in order, and sums the matching
+//                 record pairs into a partial
+//   k_th_rel      one wave per relation adds its partials in segment order
+// Every owner writes its whole gradient row (zeros without a record) and with lr != 0 also
+// p <- fma(-lr, g, p). Every order is a function of the batch indices alone.
+#include <hip/hip_runtime.h>
+
+#include "dispatch.h"
+#include "row_chain.h"
+
+namespace mmre {
+namespace {
+
+constexpr int TH_WPP = 4;       // waves per positive
+constexpr int TH_MAXK = 512;    // negatives per positive
+constexpr int TH_SEG = 1024;    // batch rows one relation-owner wave scans (why)
+constexpr int TH_REGL = 16;     // list entries a lane keeps in registers: lists up to 1024 are ordered on chip
+constexpr float TH_EPS = 1e-12f;
+
+struct THArgs {
+  const float* ent;
+  const float* rel;
+  const float* nv;
+  int64_t n_ent, n_rel;
+  int dim;
+  const int64_t* h;
+  const int64_t* t;
+  const int64_t* r;
+  int64_t B, K;
+  float model_margin;
+  int use_model_margin;
+  float loss_margin, adv_t, regul_rate;
+};
+
+struct THWork {      // d_work carved (th_carve); every region starts on 8 bytes
+  int64_t* elist;    // 2 N: the entity lists (slot ids), CSR by eoff
+  int64_t* eoff;     // n_ent + 1
+  float* part;       // 8 B: per positive hinge partial, sq h, sq t, sq r, sq w
+  float* coef;       // N
+  int32_t* rkey;     // N
+  int32_t* ekey;     // 2 N
+  int32_t* ecount;   // n_ent
+  int32_t* ecur;     // n_ent
+  int32_t* flag;     // n_rel * n_seg: the partial exists
+  float* prel;       // n_rel * n_seg * 2 * dim: (rel, normal) partial pairs
+  float* rec;        // 4 N * dim
+  int64_t n_seg;
+  int64_t floats;
+};
+
+THWork th_carve(float* base, int64_t B, int64_t K, int64_t n_ent, int64_t n_rel, int dim) {
+  const int64_t N = B * (1 + K);
+  THWork W;
+  W.n_seg = (N + TH_SEG - 1) / TH_SEG;
+  int64_t o = 0;
+  auto take = [&](int64_t n_floats) {
+    const int64_t at = o;
+    o += round_up(n_floats, 2);
+    return base + at;
+  };
+  W.elist = reinterpret_cast<int64_t*>(take(4 * N));
+  W.eoff = reinterpret_cast<int64_t*>(take(2 * (n_ent + 1)));
+  W.part = take(8 * B);
+  W.coef = take(N);
+  W.rkey = reinterpret_cast<int32_t*>(take(N));
+  W.ekey = reinterpret_cast<int32_t*>(take(2 * N));
+  W.ecount = reinterpret_cast<int32_t*>(take(n_ent));
+  W.ecur = reinterpret_cast<int32_t*>(take(n_ent));
+  W.flag = reinterpret_cast<int32_t*>(take(n_rel * W.n_seg));
+  W.prel = take(n_rel * W.n_seg * 2 * dim);
+  W.rec = take(4 * N * dim);
+  W.floats = o;
+  return W;
+}
+
+template <int NC>
+__device__ __forceinline__ void vstore(float* __restrict__ row, const float (&v)[NC], int d, int lane) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int k = lane + c * kWave;
+    if (k < d) row[k] = v[c];
+  }
+}
+
+template <int NC>
+__device__ __forceinline__ float vdot(const float (&a)[NC], const float (&b)[NC]) {
+  float s = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) s += a[c] * b[c];
+  return wave_sum(s);
+}
+
+// A relation's side of a row: raw r and w, the unit normal, r^ and the two norms.
+template <int NC>
+struct RelCtx {
+  float r[NC], w[NC], wh[NC], rh[NC];
+  float nw, nr;  // |w|; |r| (1 without norm_flag)
+};
+// An entity projected on a relation's hyperplane.
+template <int NC>
+struct EntCtx {
+  float e[NC], ph[NC];  // raw row; p^
+  float a, np;          // e . w^; |p| (1 without norm_flag)
+};
+
+template <int NC, bool NORM>
+__device__ __forceinline__ void load_rel(const THArgs& A, int64_t r, int lane, RelCtx<NC>& R) {
+  vload(R.r, A.rel + r * A.dim, A.dim, lane);
+  vload(R.w, A.nv + r * A.dim, A.dim, lane);
+  R.nw = sqrtf(wave_sum(vsq(R.w)));
+  const float cw = fmaxf(R.nw, TH_EPS);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) R.wh[c] = R.w[c] / cw;
+  R.nr = 1.0f;
+  if constexpr (NORM) R.nr = sqrtf(wave_sum(vsq(R.r)));
+  const float cr = fmaxf(R.nr, TH_EPS);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) R.rh[c] = NORM ? R.r[c] / cr : R.r[c];
+}
+
+template <int NC, bool NORM>
+__device__ __forceinline__ void load_ent(const THArgs& A, int64_t e, const RelCtx<NC>& R, int lane, EntCtx<NC>& E) {
+  vload(E.e, A.ent + e * A.dim, A.dim, lane);
+  E.a = vdot(E.e, R.wh);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) E.ph[c] = E.e[c] - E.a * R.wh[c];
+  E.np = 1.0f;
+  if constexpr (NORM) {
+    E.np = sqrtf(wave_sum(vsq(E.ph)));
+    const float cp = fmaxf(E.np, TH_EPS);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) E.ph[c] = E.ph[c] / cp;
+  }
+}
+
+// x = (p^_h + r^) - p^_t and the raw score s (padding slots hold 0 in every operand: they add +0)
+template <int NC, bool L2>
+__device__ __forceinline__ float row_x(const EntCtx<NC>& H, const RelCtx<NC>& R, const EntCtx<NC>& T, float (&x)[NC]) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    x[c] = (H.ph[c] + R.rh[c]) - T.ph[c];
+    acc += L2 ? x[c] * x[c] : fabsf(x[c]);
+  }
+  const float s = wave_sum(acc);
+  return L2 ? sqrtf(s) : s;
+}
+
+// Row j of positive b: its ids, what it shares with the positive, and the contexts (the positive's
+// copies or freshly loaded ones).
+template <int NC, bool NORM>
+struct RowCtx {
+  RelCtx<NC> R;
+  EntCtx<NC> H, T;
+  int64_t h, t, r;
+  bool same_r, same_h, same_t;
+};
+template <int NC, bool NORM>
+__device__ __forceinline__ void load_row(const THArgs& A, int64_t i, int lane, int64_t pr, int64_t ph, int64_t pt,
+                                         const RelCtx<NC>& PR, const EntCtx<NC>& PH, const EntCtx<NC>& PT,
+                                         RowCtx<NC, NORM>& X) {
+  X.h = A.h[i]; X.t = A.t[i]; X.r = A.r[i];
+  X.same_r = X.r == pr;
+  X.same_h = X.same_r && X.h == ph;
+  X.same_t = X.same_r && X.t == pt;
+  if (X.same_r) X.R = PR; else load_rel<NC, NORM>(A, X.r, lane, X.R);
+  if (X.same_h) X.H = PH; else load_ent<NC, NORM>(A, X.h, X.R, lane, X.H);
+  if (X.same_t) X.T = PT; else load_ent<NC, NORM>(A, X.t, X.R, lane, X.T);
+}
+
+// ------------------------------------------------------------------------------------------
+// forward
+// ------------------------------------------------------------------------------------------
+template <int NC, bool L2, bool NORM>
+__global__ __launch_bounds__(256) void k_th_forward(THArgs A, float* __restrict__ score, float* __restrict__ part) {
+  __shared__ float s_sc[TH_MAXK + 1];
+  __shared__ float s_sq[TH_WPP][4];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t b = blockIdx.x;
+  const int64_t pr = A.r[b], ph = A.h[b], pt = A.t[b];
+  RelCtx<NC> PR;
+  EntCtx<NC> PH, PT;
+  load_rel<NC, NORM>(A, pr, lane, PR);
+  load_ent<NC, NORM>(A, ph, PR, lane, PH);
+  load_ent<NC, NORM>(A, pt, PR, lane, PT);
+  float sq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int64_t j = w; j <= A.K; j += TH_WPP) {
+    const int64_t i = b + j * A.B;
+    RowCtx<NC, NORM> X;
+    load_row<NC, NORM>(A, i, lane, pr, ph, pt, PR, PH, PT, X);
+    float x[NC];
+    const float s = row_x<NC, L2>(X.H, X.R, X.T, x);
+    const float f = A.use_model_margin ? A.model_margin - s : s;
+    if (lane == 0) { score[i] = f; s_sc[j] = f; }
+    if (A.regul_rate != 0.0f) {
+      sq[0] += vsq(X.H.e); sq[1] += vsq(X.T.e); sq[2] += vsq(X.R.r); sq[3] += vsq(X.R.w);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float v = A.regul_rate != 0.0f ? wave_sum(sq[q]) : 0.0f;
+    if (lane == 0) s_sq[w][q] = v;
+  }
+  __syncthreads();
+  if (w != 0) return;
+  // the positive's hinge partial: sum_j w_j max(p - n_j, -margin), w_j = softmax_j(-T n_j) or 1
+  const float p = s_sc[0];
+  float mx = -INFINITY, den = 0.0f;
+  if (A.adv_t > 0.0f) {
+    for (int64_t j = lane; j < A.K; j += kWave) mx = fmaxf(mx, -s_sc[1 + j] * A.adv_t);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s));
+    for (int64_t j = lane; j < A.K; j += kWave) den += expf(-s_sc[1 + j] * A.adv_t - mx);
+    den = wave_sum(den);
+  }
+  float loss = 0.0f;
+  for (int64_t j = lane; j < A.K; j += kWave) {
+    const float n = s_sc[1 + j];
+    const float hinge = fmaxf(p - n, -A.loss_margin);
+    loss += A.adv_t > 0.0f ? expf(-n * A.adv_t - mx) / den * hinge : hinge;
+  }
+  loss = wave_sum(loss);
+  if (lane == 0) {
+    float* o = part + b * 8;
+    o[0] = loss;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[1 + q] = (s_sq[0][q] + s_sq[1][q]) + (s_sq[2][q] + s_sq[3][q]);
+  }
+}
+
+// Fixed-order reduction of the per-positive partials by one workgroup: strided double sums per
+// thread, butterfly wave sums, the four wave totals in a fixed order.
+__global__ __launch_bounds__(256) void k_th_reduce(THArgs A, const float* __restrict__ part, float* __restrict__ loss) {
+  __shared__ double red[5][4];
+  double acc[5] = {0, 0, 0, 0, 0};
+  for (int64_t b = threadIdx.x; b < A.B; b += 256) {
+#pragma unroll
+    for (int q = 0; q < 5; ++q) acc[q] += (double)part[b * 8 + q];
+  }
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) acc[q] += __shfl_xor(acc[q], s);
+  }
+  if ((threadIdx.x & 63) == 0)
+    for (int q = 0; q < 5; ++q) red[q][threadIdx.x >> 6] = acc[q];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double t[5];
+  for (int q = 0; q < 5; ++q) t[q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
+  const double Bd = (double)A.B, Kd = (double)A.K;
+  double l = A.adv_t > 0.0f ? t[0] / Bd : t[0] / (Bd * Kd);
+  l += (double)A.loss_margin;
+  if (A.regul_rate != 0.0f) {
+    const double nd = Bd * (1.0 + Kd) * (double)A.dim;
+    l += (double)A.regul_rate * ((t[1] / nd + t[2] / nd + t[3] / nd + t[4] / nd) / 4.0);
+  }
+  loss[0] = (float)l;
+}
+
+// ------------------------------------------------------------------------------------------
+// gradient
+// ------------------------------------------------------------------------------------------
+
+// d(loss)/d(score) of every row times the upstream gradient (k_ns_row_coef's margin rule: ties at
+// the kink split the gradient, the self-adversarial weights are detached); the entity counters of
+// this call zeroed.
+__global__ __launch_bounds__(256) void k_th_coef(THArgs A, const float* __restrict__ score,
+                                                  const float* __restrict__ grad_loss, float* __restrict__ coef,
+                                                  int32_t* __restrict__ ecount, int32_t* __restrict__ ecur) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.n_ent; i += (int64_t)gridDim.x * blockDim.x) {
+    ecount[i] = 0;
+    ecur[i] = 0;
+  }
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (b >= A.B) return;
+  const float gl = grad_loss[0];
+  const float p = score[b];
+  float mx = -INFINITY, den = 0.0f;
+  if (A.adv_t > 0.0f) {
+    for (int64_t j = lane; j < A.K; j += kWave) mx = fmaxf(mx, -score[b + (j + 1) * A.B] * A.adv_t);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s));
+    for (int64_t j = lane; j < A.K; j += kWave) den += expf(-score[b + (j + 1) * A.B] * A.adv_t - mx);
+    den = wave_sum(den);
+  }
+  float gp = 0.0f;
+  for (int64_t j = lane; j < A.K; j += kWave) {
+    const float n = score[b + (j + 1) * A.B];
+    const float x = p - n, m = -A.loss_margin;
+    const float ind = x > m ? 1.0f : (x == m ? 0.5f : 0.0f);
+    const float c = A.adv_t > 0.0f ? (expf(-n * A.adv_t - mx) / den) / (float)A.B : 1.0f / (float)(A.B * A.K);
+    coef[b + (j + 1) * A.B] = -(c * ind) * gl;
+    gp += c * ind;
+  }
+  gp = wave_sum(gp);
+  if (lane == 0) coef[b] = gp * gl;
+}
+
+// The exact derivative of one row's score times g, with respect to its four raw rows (file header).
+template <int NC, bool L2, bool NORM>
+__device__ __forceinline__ void row_grad(const RowCtx<NC, NORM>& X, float g, float (&dH)[NC], float (&dT)[NC],
+                                         float (&dR)[NC], float (&dW)[NC]) {
+  float x[NC], gx[NC];
+  const float s = row_x<NC, L2>(X.H, X.R, X.T, x);
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    gx[c] = L2 ? (s > 0.0f ? g * x[c] / s : 0.0f) : g * (float)((x[c] > 0.0f) - (x[c] < 0.0f));
+  float uh[NC], ut[NC];
+  if constexpr (NORM) {
+    float a = 0.0f, b = 0.0f, e = 0.0f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      a += X.H.ph[c] * gx[c];
+      b += X.T.ph[c] * (-gx[c]);
+      e += X.R.rh[c] * gx[c];
+    }
+    a = wave_sum(a); b = wave_sum(b); e = wave_sum(e);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      uh[c] = X.H.np > TH_EPS ? (gx[c] - X.H.ph[c] * a) / X.H.np : gx[c] / TH_EPS;
+      ut[c] = X.T.np > TH_EPS ? (-gx[c] - X.T.ph[c] * b) / X.T.np : -gx[c] / TH_EPS;
+      dR[c] = X.R.nr > TH_EPS ? (gx[c] - X.R.rh[c] * e) / X.R.nr : gx[c] / TH_EPS;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { uh[c] = gx[c]; ut[c] = -gx[c]; dR[c] = gx[c]; }
+  }
+  const float bh = vdot(uh, X.R.wh), bt = vdot(ut, X.R.wh);
+  float dwh[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    dH[c] = uh[c] - bh * X.R.wh[c];
+    dT[c] = ut[c] - bt * X.R.wh[c];
+    dwh[c] = ((-(bh * X.H.e[c]) - X.H.a * uh[c]) - bt * X.T.e[c]) - X.T.a * ut[c];
+  }
+  const float q = vdot(X.R.wh, dwh);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) dW[c] = X.R.nw > TH_EPS ? (dwh[c] - X.R.wh[c] * q) / X.R.nw : dwh[c] / TH_EPS;
+}
+
+template <int NC, bool L2, bool NORM>
+__global__ __launch_bounds__(256) void k_th_records(THArgs A, const float* __restrict__ coef,
+                                                     const float* __restrict__ grad_loss, float reg_unit, THWork W) {
+  __shared__ float s_acc[4][TH_WPP][NC * kWave];
+  __shared__ int s_cnt[TH_WPP][4];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t b = blockIdx.x;
+  const int d = A.dim;
+  const float reg = reg_unit * grad_loss[0];  // the regulariser's weight per gathered row, times the upstream gradient
+  const int64_t pr = A.r[b], ph = A.h[b], pt = A.t[b];
+  RelCtx<NC> PR;
+  EntCtx<NC> PH, PT;
+  load_rel<NC, NORM>(A, pr, lane, PR);
+  load_ent<NC, NORM>(A, ph, PR, lane, PH);
+  load_ent<NC, NORM>(A, pt, PR, lane, PT);
+  // This wave's sums for the positive's h, t, r, w rows, in j order, and how many rows each sums.
+  // The regulariser joins a shared row once, at the end, as (reg * rows) * row: a negative that
+  // repeats its positive then cancels it exactly, as it does in exact arithmetic.
+  float acc[4][NC];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[q][c] = 0.0f;
+  int cnt[4] = {0, 0, 0, 0};
+  for (int64_t j = w; j <= A.K; j += TH_WPP) {
+    const int64_t i = b + j * A.B;
+    float g = coef[i];
+    const bool files = g != 0.0f || reg != 0.0f;  // else the row adds nothing anywhere
+    int32_t kh = -1, kt = -1, kr = -1;
+    if (files) {
+      if (A.use_model_margin) g = -g;  // forward = m - s
+      RowCtx<NC, NORM> X;
+      load_row<NC, NORM>(A, i, lane, pr, ph, pt, PR, PH, PT, X);
+      float dv[4][NC];
+      row_grad<NC, L2, NORM>(X, g, dv[0], dv[1], dv[2], dv[3]);
+      // slot q of row i: into the positive's sum when shared, else a record of its own
+      auto put = [&](int q, bool shared, float (&v)[NC], const float (&raw)[NC]) {
+        if (shared) {
+          ++cnt[q];
+#pragma unroll
+          for (int c = 0; c < NC; ++c) acc[q][c] += v[c];
+        } else {
+#pragma unroll
+          for (int c = 0; c < NC; ++c) v[c] += reg * raw[c];
+          vstore(W.rec + (4 * i + q) * d, v, d, lane);
+        }
+      };
+      put(0, X.same_h, dv[0], X.H.e);
+      put(1, X.same_t, dv[1], X.T.e);
+      put(2, X.same_r, dv[2], X.R.r);
+      put(3, X.same_r, dv[3], X.R.w);
+      if (!X.same_h) kh = (int32_t)X.h;
+      if (!X.same_t) kt = (int32_t)X.t;
+      if (!X.same_r) kr = (int32_t)X.r;
+    }
+    if (j > 0 && lane == 0) {  // (row b's keys: below, once the positive's slots are known live)
+      W.ekey[2 * i] = kh;
+      W.ekey[2 * i + 1] = kt;
+      W.rkey[i] = kr;
+      if (kh >= 0) atomicAdd(&W.ecount[kh], 1);
+      if (kt >= 0) atomicAdd(&W.ecount[kt], 1);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) s_acc[q][w][lane + c * kWave] = acc[q][c];
+    if (lane == 0) s_cnt[w][q] = cnt[q];
+  }
+  __syncthreads();
+  // wave q adds the four waves' sums of slot q in wave order and writes the positive's record
+  const int q = w;
+  const int rows = (s_cnt[0][q] + s_cnt[1][q]) + (s_cnt[2][q] + s_cnt[3][q]);
+  const bool any = rows > 0;
+  if (any) {
+    const float rw = reg * (float)rows;
+    float v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int k = lane + c * kWave;
+      const float raw = q == 0 ? PH.e[c] : q == 1 ? PT.e[c] : q == 2 ? PR.r[c] : PR.w[c];
+      v[c] = (((s_acc[q][0][k] + s_acc[q][1][k]) + s_acc[q][2][k]) + s_acc[q][3][k]) + rw * raw;
+    }
+    vstore(W.rec + (4 * b + q) * d, v, d, lane);
+  }
+  if (lane == 0) {
+    if (q == 0) { W.ekey[2 * b] = any ? (int32_t)ph : -1; if (any) atomicAdd(&W.ecount[ph], 1); }
+    if (q == 1) { W.ekey[2 * b + 1] = any ? (int32_t)pt : -1; if (any) atomicAdd(&W.ecount[pt], 1); }
+    if (q == 2) W.rkey[b] = any ? (int32_t)pr : -1;  // (slots 2 and 3 are live together)
+  }
+}
+
+// eoff <- exclusive scan of ecount, by one workgroup: a contiguous run per thread, the runs' totals
+// scanned inside each wave by shuffles, the sixteen wave totals by every thread.
+__global__ __launch_bounds__(1024) void k_th_scan(const int32_t* __restrict__ ecount, int64_t n_ent,
+                                                   int64_t* __restrict__ eoff) {
+  __shared__ int64_t s_wave[16];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t per = (n_ent + 1023) / 1024;
+  const int64_t lo = threadIdx.x * per, hi = lo + per < n_ent ? lo + per : n_ent;
+  int64_t s = 0;
+  for (int64_t i = lo; i < hi; ++i) s += ecount[i];
+  int64_t incl = s;  // inclusive scan of the runs' totals over the wave
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const int64_t up = __shfl_up(incl, o);
+    if (lane >= o) incl += up;
+  }
+  if (lane == kWave - 1) s_wave[w] = incl;
+  __syncthreads();
+  int64_t run = incl - s, total = 0;
+  for (int i = 0; i < 16; ++i) {
+    if (i < w) run += s_wave[i];
+    total += s_wave[i];
+  }
+  if (threadIdx.x == 0) eoff[n_ent] = total;
+  for (int64_t i = lo; i < hi; ++i) {
+    eoff[i] = run;
+    run += ecount[i];
+  }
+}
+
+// entity slot s = 2 i + (0 | 1) into its row's list, in arrival order (the owner orders it)
+__global__ __launch_bounds__(256) void k_th_fill(THWork W, int64_t n_slots) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_slots) return;
+  const int32_t key = W.ekey[s];
+  if (key < 0) return;
+  const int p = atomicAdd(&W.ecur[key], 1);
+  W.elist[W.eoff[key] + p] = 4 * (s >> 1) + (s & 1);
+}
+
+__device__ __forceinline__ int64_t wave_min(int64_t v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    const int64_t o = __shfl_xor(v, s);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+// g row -> the gradient table, and with lr != 0 the parameter row's plain SGD step
+template <int NC>
+__device__ __forceinline__ void owner_write(const float (&g)[NC], float* __restrict__ grad, float* __restrict__ par,
+                                            float lr, bool touched, int d, int lane) {
+  vstore(grad, g, d, lane);
+  if (lr != 0.0f && touched) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int k = lane + c * kWave;
+      if (k < d) par[k] = __builtin_fmaf(-lr, g[c], par[k]);
+    }
+  }
+}
+
+// Workgroups [0, ent_blocks): one wave per entity row. The rest: one wave per (relation, segment).
+template <int NC>
+__global__ __launch_bounds__(256) void k_th_owner(THArgs A, THWork W, int64_t ent_blocks, float* ent, float lr,
+                                                   float* __restrict__ grad_ent) {
+  __shared__ int64_t s_ord[4][kWave];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int d = A.dim;
+  const int64_t N = A.B * (1 + A.K);
+  constexpr int64_t kNone = INT64_MAX;
+  if ((int64_t)blockIdx.x < ent_blocks) {
+    const int64_t e = (int64_t)blockIdx.x * 4 + w;
+    if (e >= A.n_ent) return;
+    const int64_t off = W.eoff[e], L = W.eoff[e + 1] - off;
+    const int64_t* __restrict__ list = W.elist + off;
+    float g[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) g[c] = 0.0f;
+    if (L <= kWave) {  // rank the slot ids (they are distinct), then sum in rank order
+      const int64_t x = lane < L ? list[lane] : kNone;
+      int rank = 0;
+      for (int m = 0; m < (int)L; ++m) rank += __shfl(x, m) < x ? 1 : 0;
+      if (lane < L) s_ord[w][rank] = x;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int k = 0; k < (int)L; ++k) {
+        float v[NC];
+        vload(v, W.rec + s_ord[w][k] * d, d, lane);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) g[c] += v[c];
+      }
+    } else {  // repeated selection of the next larger slot id
+      const bool in_regs = L <= (int64_t)TH_REGL * kWave;
+      int64_t mine[TH_REGL];
+#pragma unroll
+      for (int u = 0; u < TH_REGL; ++u) {
+        const int64_t at = lane + (int64_t)u * kWave;
+        mine[u] = in_regs && at < L ? list[at] : kNone;
+      }
+      int64_t cur = -1;
+      for (int64_t k = 0; k < L; ++k) {
+        int64_t best = kNone;
+        if (in_regs) {
+#pragma unroll
+          for (int u = 0; u < TH_REGL; ++u) best = (mine[u] > cur && mine[u] < best) ? mine[u] : best;
+        } else {
+          for (int64_t at = lane; at < L; at += kWave) {
+            const int64_t x = list[at];
+            best = (x > cur && x < best) ? x : best;
+          }
+        }
+        cur = wave_min(best);
+        float v[NC];
+        vload(v, W.rec + cur * d, d, lane);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) g[c] += v[c];
+      }
+    }
+    owner_write(g, grad_ent + e * d, ent + e * d, lr, L > 0, d, lane);
+    return;
+  }
+  // relation side: the segment's rows of relation r, in row order
+  const int64_t item = ((int64_t)blockIdx.x - ent_blocks) * 4 + w;
+  if (item >= A.n_rel * W.n_seg) return;
+  const int64_t r = item / W.n_seg, seg = item % W.n_seg;
+  const int64_t lo = seg * TH_SEG, hi = lo + TH_SEG < N ? lo + TH_SEG : N;
+  float gr[NC], gw[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) gr[c] = gw[c] = 0.0f;
+  bool found = false;
+  for (int64_t base = lo; base < hi; base += kWave) {
+    const int64_t i = base + lane;
+    const bool hit = i < hi && (int64_t)W.rkey[i] == r;
+    uint64_t m = __ballot(hit);
+    found = found || m != 0;
+    while (m) {
+      const int64_t row = base + __builtin_ctzll(m);
+      m &= m - 1;
+      float a[NC], c2[NC];
+      vload(a, W.rec + (4 * row + 2) * d, d, lane);
+      vload(c2, W.rec + (4 * row + 3) * d, d, lane);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) { gr[c] += a[c]; gw[c] += c2[c]; }
+    }
+  }
+  if (lane == 0) W.flag[item] = found ? 1 : 0;
+  if (found) {
+    vstore(W.prel + item * 2 * d, gr, d, lane);
+    vstore(W.prel + (item * 2 + 1) * d, gw, d, lane);
+  }
+}
+
+// One wave per relation: its partial pairs added in segment order; both rows written.
+template <int NC>
+__global__ __launch_bounds__(256) void k_th_rel(THArgs A, THWork W, float* rel, float* nv, float lr,
+                                                 float* __restrict__ grad_rel, float* __restrict__ grad_nv) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (r >= A.n_rel) return;
+  const int d = A.dim;
+  float gr[NC], gw[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) gr[c] = gw[c] = 0.0f;
+  bool touched = false;
+  for (int64_t base = 0; base < W.n_seg; base += kWave) {
+    const int64_t s = base + lane;
+    uint64_t m = __ballot(s < W.n_seg && W.flag[r * W.n_seg + s] != 0);
+    touched = touched || m != 0;
+    while (m) {
+      const int64_t item = r * W.n_seg + base + __builtin_ctzll(m);
+      m &= m - 1;
+      float a[NC], c2[NC];
+      vload(a, W.prel + item * 2 * d, d, lane);
+      vload(c2, W.prel + (item * 2 + 1) * d, d, lane);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) { gr[c] += a[c]; gw[c] += c2[c]; }
+    }
+  }
+  owner_write(gr, grad_rel + r * d, rel + r * d, lr, touched, d, lane);
+  owner_write(gw, grad_nv + r * d, nv + r * d, lr, touched, d, lane);
+}
+
+bool th_train_model(int model) { return model == MMRE_TRANSH_L1 || model == MMRE_TRANSH_L2; }
+
+// the shapes the kernels have; the ids and the lists' offsets must fit their integer types
+bool th_train_shape(int dim, int64_t neg) { return dim >= 1 && dim <= 8 * kWave && neg >= 1 && neg <= TH_MAXK; }
+bool th_train_sizes(int64_t batch, int64_t neg, int64_t n_ent, int64_t n_rel) {
+  return batch >= 1 && n_ent >= 1 && n_rel >= 1 && n_ent <= INT32_MAX && n_rel <= INT32_MAX &&
+         batch <= (int64_t)INT32_MAX / 8 / (1 + neg);
+}
+
+// f(NC, L2, NORM) for the model's instance
+template <class F>
+int th_dispatch(int model, int norm_flag, int dim, F&& f) {
+  return with_nc<8>(nc_for_dim(dim, 8), [&](auto nc) {
+    with_bool(model == MMRE_TRANSH_L2, [&](auto l2) {
+      return with_bool(norm_flag != 0, [&](auto nm) {
+        f(nc, l2, nm);
+        return 0;
+      });
+    });
+  });
+}
+
+}  // namespace
+}  // namespace mmre
+
+using namespace mmre;
+
+extern "C" int mmre_transh_ns_supported(int model, int dim, int64_t neg) {
+  return th_train_model(model) && th_train_shape(dim, neg) ? 1 : 0;
+}
+
+extern "C" int64_t mmre_transh_ns_workspace(int64_t batch, int64_t neg, int64_t n_ent, int64_t n_rel, int dim) {
+  if (!th_train_shape(dim, neg) || !th_train_sizes(batch, neg, n_ent, n_rel)) return -1;
+  return th_carve(nullptr, batch, neg, n_ent, n_rel, dim).floats;
+}
+
+extern "C" int mmre_transh_ns_forward(int model, int norm_flag, float model_margin, int use_model_margin,
+                                      const float* d_ent, const float* d_rel, const float* d_norm, int64_t n_ent,
+                                      int64_t n_rel, int dim, const int64_t* d_h, const int64_t* d_t,
+                                      const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin,
+                                      float adv_temperature, float regul_rate, float* d_score, float* d_loss,
+                                      float* d_work, void* stream) {
+  if (!th_train_model(model)) return MMRE_ERR_MODEL;
+  if (!d_ent || !d_rel || !d_norm || !d_h || !d_t || !d_r || !d_score || !d_loss || !d_work) return MMRE_ERR_ARG;
+  if (!th_train_shape(dim, neg) || !th_train_sizes(batch, neg, n_ent, n_rel)) return MMRE_ERR_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  const THArgs A{d_ent, d_rel, d_norm, n_ent, n_rel, dim, d_h, d_t, d_r, batch, neg, model_margin,
+                 use_model_margin, loss_margin, adv_temperature, regul_rate};
+  const THWork W = th_carve(d_work, batch, neg, n_ent, n_rel, dim);
+  const int rc = th_dispatch(model, norm_flag, dim, [&](auto nc, auto l2, auto nm) {
+    hipLaunchKernelGGL((k_th_forward<decltype(nc)::value, decltype(l2)::value, decltype(nm)::value>), dim3((unsigned)batch), dim3(256), 0, st, A,
+                       d_score, W.part);
+  });
+  if (rc != MMRE_OK) return rc;
+  hipLaunchKernelGGL(k_th_reduce, dim3(1), dim3(256), 0, st, A, W.part, d_loss);
+  MMRE_CHECK_LAUNCH();
+  return MMRE_OK;
+}
+
+extern "C" int mmre_transh_ns_grad(int model, int norm_flag, float model_margin, int use_model_margin, float* d_ent,
+                                   float* d_rel, float* d_norm, int64_t n_ent, int64_t n_rel, int dim,
+                                   const int64_t* d_h, const int64_t* d_t, const int64_t* d_r, int64_t batch,
+                                   int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
+                                   const float* d_score, const float* d_grad_loss, float* d_grad_ent,
+                                   float* d_grad_rel, float* d_grad_norm, float* d_work, float lr, void* stream) {
+  if (!th_train_model(model)) return MMRE_ERR_MODEL;
+  if (!d_ent || !d_rel || !d_norm || !d_h || !d_t || !d_r || !d_score || !d_grad_loss || !d_grad_ent ||
+      !d_grad_rel || !d_grad_norm || !d_work)
+    return MMRE_ERR_ARG;
+  if (!th_train_shape(dim, neg) || !th_train_sizes(batch, neg, n_ent, n_rel)) return MMRE_ERR_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  const THArgs A{d_ent, d_rel, d_norm, n_ent, n_rel, dim, d_h, d_t, d_r, batch, neg, model_margin,
+                 use_model_margin, loss_margin, adv_temperature, regul_rate};
+  const THWork W = th_carve(d_work, batch, neg, n_ent, n_rel, dim);
+  const int64_t N = batch * (1 + neg);
+  // d/d(row) of regul_rate (mean h^2 + mean t^2 + mean r^2 + mean w^2) / 4 is reg * row per
+  // gathered row (k_th_records multiplies it by the upstream gradient, read on the device)
+  const float reg = regul_rate != 0.0f ? (float)((double)regul_rate * 2.0 / (4.0 * (double)N * (double)dim)) : 0.0f;
+  hipLaunchKernelGGL(k_th_coef, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, A, d_score, d_grad_loss, W.coef,
+                     W.ecount, W.ecur);
+  MMRE_CHECK_LAUNCH();
+  int rc = th_dispatch(model, norm_flag, dim, [&](auto nc, auto l2, auto nm) {
+    hipLaunchKernelGGL((k_th_records<decltype(nc)::value, decltype(l2)::value, decltype(nm)::value>), dim3((unsigned)batch), dim3(256), 0, st, A,
+                       W.coef, d_grad_loss, reg, W);
+  });
+  if (rc != MMRE_OK) return rc;
+  hipLaunchKernelGGL(k_th_scan, dim3(1), dim3(1024), 0, st, W.ecount, n_ent, W.eoff);
+  MMRE_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_th_fill, dim3((unsigned)((2 * N + 255) / 256)), dim3(256), 0, st, W, 2 * N);
+  MMRE_CHECK_LAUNCH();
+  const int64_t ent_blocks = (n_ent + 3) / 4, rel_blocks = (n_rel * W.n_seg + 3) / 4;
+  if (ent_blocks + rel_blocks > INT32_MAX) return MMRE_ERR_SHAPE;
+  rc = with_nc<8>(nc_for_dim(dim, 8), [&](auto nc) {
+    hipLaunchKernelGGL((k_th_owner<decltype(nc)::value>), dim3((unsigned)(ent_blocks + rel_blocks)), dim3(256), 0, st, A, W,
+                       ent_blocks, d_ent, lr, d_grad_ent);
+  });
+  if (rc != MMRE_OK) return rc;
+  return with_nc<8>(nc_for_dim(dim, 8), [&](auto nc) {
+    hipLaunchKernelGGL((k_th_rel<decltype(nc)::value>), dim3((unsigned)((n_rel + 3) / 4)), dim3(256), 0, st, A, W, d_rel, d_norm,
+                       lr, d_grad_rel, d_grad_norm);
+  });
+}

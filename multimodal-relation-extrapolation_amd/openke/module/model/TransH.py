@@ -1,15 +1,18 @@
 """TransH (OpenKE/openke/module/model/TransH.py:6-115): same constructor, init branches,
 parameter names and state-dict keys.
 
-forward(data) is the reference's torch ops (differentiable: training runs on autograd through
-them); predict(data) and the Tester's evaluations run on libmmre_hip.so (mmre.transh: the fused
-hyperplane-projected sweep and its row kernel). A fused TransH training step is not built:
-ns_spec() returns None, and NegativeSampling / Trainer take their generic paths."""
+forward(data) is the reference's torch ops (differentiable); predict(data) and the Tester's
+evaluations run on libmmre_hip.so (mmre.transh: the fused hyperplane-projected sweep and its row
+kernel). Training under NegativeSampling + MarginLoss runs on libmmre_hip.so as well: fused_ns()
+hands the strategy the three tables and the static spec of mmre.transh_ns.fused_ns_loss (the
+fused loss, row-owner gradients, the in-pass SGD step). ns_spec() stays None -- the generic
+mmre.ns kernels and the one-call sampler-fused step have no TransH instance."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from mmre import transh as _transh
+from mmre import transh_ns as _transh_ns
 from mmre.link import ScoreSpec
 
 from .Model import Model
@@ -50,9 +53,21 @@ class TransH(Model):
         return self.ent_embeddings.weight, self.rel_embeddings.weight, None, None
 
     def ns_spec(self):
-        """No fused negative-sampling step for TransH (its slot records would need a fourth row per
-        triple): the strategy scores through forward() and autograd."""
+        """No instance of the generic mmre.ns kernels for TransH (a triple has a fourth row, the
+        normal): the strategy asks fused_ns() instead."""
         return None
+
+    def fused_ns(self, neg):
+        """(spec, ent, rel, norm_vector) for mmre.transh_ns.fused_ns_loss when the fused TransH
+        training kernels serve this model with `neg` negatives per positive -- float32 device
+        tables, dim <= 512, 1 <= neg <= 512 -- else None (the strategy then scores through
+        forward() and autograd)."""
+        tables = (self.ent_embeddings.weight, self.rel_embeddings.weight, self.norm_vector.weight)
+        if any(not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() for x in tables):
+            return None
+        if neg < 1 or not _transh_ns.supported(self.dim, neg):
+            return None
+        return (_transh_ns.THSpec(self.p_norm, self.dim, self.norm_flag, self._m()),) + tables
 
     def score_spec(self):
         # predict() = margin - forward = m - (m - s) when margin_flag, else s   (TransH.py:109-115)

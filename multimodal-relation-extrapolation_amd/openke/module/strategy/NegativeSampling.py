@@ -7,8 +7,13 @@ a fused backward into the embedding tables. Other losses / cross-sampling modes 
 model(data) (HIP) and apply the loss module on the score tensors. `fuse_optimizer(opt)` (the
 Trainer calls it for its mmre.optim.SGD or Adagrad) lets that backward also apply the
 optimizer's plain step to the tables in the same pass (bit-identical parameters; step() then
-skips them)."""
+skips them). TransH has its own kernels (mmre.transh_ns.fused_ns_loss, through the model's
+fused_ns() hook): MarginLoss in 'normal' mode on float32 device tables at a supported shape;
+everything else about a TransH model takes the generic branch."""
+import torch
+
 from mmre.ns import fused_ns_loss
+from mmre.transh_ns import fused_ns_loss as transh_fused_ns_loss
 
 from ..loss.MarginLoss import MarginLoss
 from ..loss.SigmoidLoss import SigmoidLoss
@@ -35,11 +40,26 @@ class NegativeSampling(Strategy):
     def _get_negative_score(self, score):
         return score[self.batch_size:].view(-1, self.batch_size).permute(1, 0)
 
+    def _transh_fused(self, data, mode):
+        """((spec, ent, rel, norm_vector), neg) when this batch takes the fused TransH path: a
+        MarginLoss, 'normal' mode, a model with the fused_ns hook that offers the shape; else None."""
+        hook = getattr(self.model, "fused_ns", None)
+        if hook is None or not isinstance(self.loss, MarginLoss) or mode != "normal":
+            return None
+        n = int(data["batch_h"].shape[0])
+        if n % self.batch_size:
+            return None
+        neg = n // self.batch_size - 1
+        offer = hook(neg)
+        return None if offer is None else (offer, neg)
+
     def forward(self, data):
         mode = data.get("mode", "normal")
         # (a model without a fused step -- ns_spec() None: TransH -- scores through model(data))
         fused = isinstance(self.loss, (MarginLoss, SoftplusLoss, SigmoidLoss)) and mode == "normal"
-        if fused and self.model.ns_spec() is not None:
+        spec = self.model.ns_spec() if fused else None
+        th = self._transh_fused(data, mode) if spec is None else None
+        if spec is not None:
             ent, rel, ent_im, rel_im = self.model._tables()
             dev = ent.device
             h = data["batch_h"].to(dev)
@@ -51,10 +71,17 @@ class NegativeSampling(Strategy):
             kind = "margin"
             if not isinstance(self.loss, MarginLoss):  # (kind, adv): these losses have no margin
                 kind, margin = margin, 0.0
-            loss_res, _ = fused_ns_loss(self.model.ns_spec(), ent, rel, h, t, r, self.batch_size, neg, margin,
+            loss_res, _ = fused_ns_loss(spec, ent, rel, h, t, r, self.batch_size, neg, margin,
                                         adv, self.regul_rate, ent_im=ent_im, rel_im=rel_im,
                                         optimizer=self.fused_optimizer if self.l3_regul_rate == 0 else None,
                                         loss=kind)
+        elif th is not None:
+            (spec, ent, rel, nv), neg = th
+            h, t, r = (torch.as_tensor(data[k]).to(ent.device) for k in ("batch_h", "batch_t", "batch_r"))
+            margin, adv = self.loss.fused_args()
+            loss_res, _ = transh_fused_ns_loss(spec, ent, rel, nv, h, t, r, self.batch_size, neg, margin, adv,
+                                               self.regul_rate,
+                                               optimizer=self.fused_optimizer if self.l3_regul_rate == 0 else None)
         else:
             score = self.model(data)
             loss_res = self.loss(self._get_positive_score(score), self._get_negative_score(score))
