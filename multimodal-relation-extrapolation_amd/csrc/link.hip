@@ -500,8 +500,11 @@ struct L1Q {
   // byte in `routed` is set (nullptr: no route); k_heavy_rows counts the routed list's queries
   // instead
   const uint8_t* routed;
-  const int32_t* route_list;  // (unused since k_heavy_rows takes the list itself; kept so that the
-  const uint32_t* route_n;    // sweeps' kernel argument, and with it their code, stays as measured)
+  // grouped sweep, row-tile-affine claims (l1q_affine_stride): per XCD group a hint word and one
+  // claim counter per row tile, zeroed by k_eval_prep (nullptr: the group's sequential counter, wq)
+  uint32_t* tq;
+  const uint32_t* route_n;    // (unused since k_heavy_rows takes the list itself; kept so that the
+                              // sweeps' kernel argument, and with it their code, stays as measured)
 };
 // Header words of the route's record (zeroed with the header by K1, written by k_l1q_route_compact):
 // flagged queries, routed queries (k_heavy_rows' query count), sampled columns, flag threshold
@@ -518,6 +521,13 @@ inline uint32_t* l1q_work_counters(const uint32_t* hdr) {
   static const char* env = getenv("MMRE_SWEEP_DYN");
   return (env && env[0] == '0') ? nullptr : const_cast<uint32_t*>(hdr) + (256 + 128) / 4;
 }
+// The grouped sweep's row-tile-affine claims (L1Q::tq; sweep_valu_body's claim_affine): per XCD
+// group a block of l1q_affine_stride words, whole 128-B lines of its own -- word 0 the group's
+// hint (every row tile below it is exhausted; it only rises), word 1 + t the claims made on row
+// tile t. Sized from q_pad, which host and device both know (the device's row tiles are at most
+// q_pad / TQ). The host finds the 8 blocks in the tail of the row map's row_cnt, which nothing
+// reads or writes past the rows' bound (mmre_link_evaluate_l1q), and k_eval_prep zeroes them.
+__host__ __device__ inline int l1q_affine_stride(int64_t q_pad) { return (int)((1 + q_pad / TQ + 31) / 32 * 32); }
 __device__ __forceinline__ float l1q_delta(const uint32_t* absmax, float levels) {
   const float m = __uint_as_float(*absmax);
   return m == 0.0f ? 0.0f : (m < INFINITY ? (2.0f * m) / levels : INFINITY);
@@ -998,6 +1008,14 @@ struct ValuSmemGrp {
 };
 template <>
 struct ValuSmemGrp<0> {};
+// k_sweep_valu's DYNC (units per claim of the dynamically scheduled instances: 1, 2, 4) for the
+// grouped sweep's row-tile-affine 1-unit claims (sweep_valu_body)
+constexpr int DYNC_AFFINE = 8;
+// Workgroups that start on one row tile. C2 (103 row tiles x 13 units per XCD group, 128 workgroups
+// per group), ms per evaluation against the sequential counter's 0.596: 1 (a tile each) 0.68 -- a
+// row tile's codes then have one reader, and every unit fetches them from beyond the L2 -- 2
+// 0.607, 4 0.577, 13 (a unit each) 0.64 (profiles/grouped_affine).
+constexpr int L1Q_AFFINE_SHARE = 4;
 constexpr int L1Q_GS = 8;  // member slots per sweep row: 8 KB + 2 KB per slot = 36 KB, four workgroups per CU
 // The grouped sweep runs when the host's bound on the sweep rows is at most this share of the
 // queries (mmre_link_evaluate_l1q). C2, 1-unit claims: rows at 0.373 / 0.448 / 0.620 / 1.0 of the
@@ -1083,10 +1101,48 @@ __device__ __forceinline__ void sweep_valu_body(
   // once, not at every unit): 4 when a workgroup sweeps many units, 1 for a rank's small share
   // (valu_grid; C2 N = 1, per evaluation: chunks of 1 / 2 / 4 / 8 / 16 units 1.053 / 1.007 /
   // 0.975 / 0.997 / 1.017 ms; 8-way shares: 1 or 2 best)
-  constexpr int ch_log2 = DYNC >= 4 ? 2 : DYNC >= 2 ? 1 : 0;
+  constexpr int ch_log2 = DYNC == DYNC_AFFINE ? 0 : DYNC >= 4 ? 2 : DYNC >= 2 ? 1 : 0;
   constexpr int ch_mask = (1 << ch_log2) - 1;
-  const int u0 = dyn ? gmem << ch_log2 : (int)((int64_t)gmem * um.count / per_grp);
+  int u0 = dyn ? gmem << ch_log2 : (int)((int64_t)gmem * um.count / per_grp);
   const int u1 = dyn ? um.count : (int)((int64_t)(gmem + 1) * um.count / per_grp);
+  // DYNC_AFFINE (grouped, 1-unit claims, l1.tq): row-tile-affine claims. The sequential counter hands a
+  // workgroup a unit ~per_grp units on, ten row tiles later at C2, so every claim paid the flush
+  // / reload of the epilogue; here a claim (thread 0) takes the next unclaimed unit of row tile t
+  // in this XCD group -- its m main units, then its run of the group's leftover units, one counter
+  // over both (l1q_affine_stride) -- and, that tile exhausted, of the lowest row tile that has
+  // one: from the group's hint on, raising the hint past every tile it finds exhausted (a value
+  // read from the hint has only exhausted tiles below it, so hint = t + 1 after tile t = hint
+  // failed keeps that). It never waits for another workgroup: a round takes a unit or moves to a
+  // higher tile, and the claim is um.count (no unit) once the hint reaches the row tiles' count.
+  // The unit indices are UnitMap's; counts are integer sums, so the order of units is free.
+  // (an instance of its own, not a runtime choice beside the sequential counter: with both
+  // claims in one kernel the 8-bit instance spilled 8 VGPRs, 20 B of scratch per lane)
+  constexpr bool AFF = DYNC == DYNC_AFFINE;
+  static_assert(!AFF || GRP, "affine claims are the grouped sweep's");
+  auto claim_affine = [&](int t) -> int {
+    uint32_t* base = l1.tq + grp * l1q_affine_stride(q_pad);
+    const int lo1 = um.lo0 + (um.count - um.n_main);  // the end of the group's leftover run
+    bool hinted = false;
+    for (;;) {  // (one lane runs this: the replies go to SGPRs, the rounds are scalar code)
+      const int c = __builtin_amdgcn_readfirstlane((int)atomicAdd(&base[1 + t], 1u));
+      if (c < um.m) return t * um.m + c;
+      const int j = max(um.lo0, t * um.r) + (c - um.m);
+      if (j < min(lo1, (t + 1) * um.r)) return um.n_main + (j - um.lo0);
+      const int old = __builtin_amdgcn_readfirstlane((int)atomicMax(&base[0], hinted ? (uint32_t)(t + 1) : 0u));
+      const int h = hinted ? max(old, t + 1) : old;
+      hinted = true;
+      if (h >= n_qt) return um.count;
+      t = h;
+    }
+  };
+  if constexpr (AFF) {
+    // the first unit is a claim like any other, on row tile (gmem / L1Q_AFFINE_SHARE) % n_qt (the
+    // members spread over the tiles, a few to a tile) -- after the gate: a shut launch must claim none
+    if (__builtin_amdgcn_readfirstlane(l1.hdr[1]) != (w8 ? L1Q_CODES8 : L1Q_CODES16)) return;
+    if (threadIdx.x == 0) sm.s_unit = claim_affine((gmem / L1Q_AFFINE_SHARE) % n_qt);
+    __syncthreads();
+    u0 = __builtin_amdgcn_readfirstlane(sm.s_unit);  // (overwritten after the first stage's barrier)
+  }
   if (u0 >= u1) return;  // uniform over the workgroup
 
   // L1 filter constants (uniform): code step, bound slope and offset
@@ -1365,7 +1421,10 @@ __device__ __forceinline__ void sweep_valu_body(
   if (L1F && __builtin_amdgcn_readfirstlane(fb_flag) != (w8 ? L1Q_CODES8 : L1Q_CODES16)) return;  // uniform
   if (dyn && ch_mask == 0) {  // u0's successor (after the gate: a shut launch claims none); the
                               // loader reads it at compute stage nkc - 2 of u0, which may be stage 0
-    if (tid == 0) sm.s_unit = per_grp + (int)atomicAdd(&l1.wq[grp * L1Q_WQ_STRIDE], 1u);
+    if (tid == 0) {
+      if constexpr (AFF) sm.s_unit = claim_affine(cur_qt);
+      else sm.s_unit = per_grp + (int)atomicAdd(&l1.wq[grp * L1Q_WQ_STRIDE], 1u);
+    }
     __syncthreads();
   }
 
@@ -1376,6 +1435,15 @@ __device__ __forceinline__ void sweep_valu_body(
     for (int kc = 0; kc < nkc; ++kc) {
       const bool more = ld_unit < u1;
       if (more) gload();
+      if constexpr (AFF) {
+        // The affine claim of the unit after ld_unit, on ld_unit's row tile -- here, at the top of
+        // the unit's last stage, with that stage's loads issued: the loader entered ld_unit in the
+        // stage before (its read of s_unit is a barrier back) and leaves it >= 1 barrier on. (In
+        // the epilogue, where the sequential claim sits, a claim whose address moves with the tile
+        // cost the 8-bit instance 8 spilled VGPRs -- 20 B of scratch per lane -- even as one
+        // atomicAdd; here both widths keep 0 B.)
+        if (kc == nkc - 1 && more && threadIdx.x == 0) sm.s_unit = claim_affine(ld_qt);
+      }
       const int kk_n = (L1F && kc == nkc - 1) ? kk_last : KC;
 #pragma unroll KKU
       for (int kk = 0; kk < kk_n; ++kk) {
@@ -1835,7 +1903,8 @@ __device__ __forceinline__ void sweep_valu_body(
         // the loader entered the last unit of its chunk one stage ago: the next chunk, claimed for
         // the loader's exit from it >= 1 barrier later (the previous claim was read long before);
         // here, after the accumulators were reset, where the claim costs no registers
-        if (dyn && !last && ((unit_next + 1) & ch_mask) == 0 && threadIdx.x == 0)
+        // (the affine claim: at the top of this stage)
+        if (dyn && !AFF && !last && ((unit_next + 1) & ch_mask) == 0 && threadIdx.x == 0)
           sm.s_unit = (per_grp + (int)atomicAdd(&l1.wq[grp * L1Q_WQ_STRIDE], 1u)) << ch_log2;
         if constexpr (TC) ep_par ^= 1;  // the next unit's staged type words
         cur_qt = next_qt;
@@ -3553,7 +3622,8 @@ static int with_bools(bool a, bool b, bool c, F&& f) {
 // f(int_c<DYNC>) for the units per claim, among the instances the caller has (MASK: their sum)
 template <int MASK, class F>
 static void with_chunk(int chunk, F&& f) {
-  if ((MASK & 4) && chunk == 4) f(int_c<MASK & 4>{});
+  if ((MASK & 8) && chunk == 8) f(int_c<MASK & 8>{});
+  else if ((MASK & 4) && chunk == 4) f(int_c<MASK & 4>{});
   else if ((MASK & 2) && chunk == 2) f(int_c<MASK & 2>{});
   else if ((MASK & 1) && chunk == 1) f(int_c<MASK & 1>{});
   else f(int_c<0>{});
@@ -3759,9 +3829,17 @@ static int launch_valu_grp(const SweepCall& C, L1Q l1, int64_t rows_max) {
   const int64_t q_tiles = (rows_max + TQ - 1) / TQ;
   const int64_t units = sweep_units(q_tiles, C.n_et);
   if (units < g) g = (int)(units > 0 ? units : 1);
-  const int chunk = dyn ? sweep_chunk(q_tiles * C.n_et / (g > 0 ? g : 1), true) : 0;
+  // MMRE_SWEEP_GRID (A/B, tests; read per call here, as MMRE_SWEEP_AFFINE is): that many workgroups
+  const char* grid_env = getenv("MMRE_SWEEP_GRID");
+  if (grid_env && grid_env[0] >= '1' && grid_env[0] <= '9') g = std::max(1, atoi(grid_env));
+  // Row-tile-affine claims (l1.tq) are 1-unit claims at any share -- a claim keeps the workgroup's
+  // row tile, which is what the longer chunks were for; a chunk forced by MMRE_SWEEP_CHUNK keeps
+  // the sequential counter.
+  int chunk = dyn ? sweep_chunk(q_tiles * C.n_et / (g > 0 ? g : 1), true) : 0;
+  if (dyn && l1.tq != nullptr && getenv("MMRE_SWEEP_CHUNK") == nullptr) chunk = DYNC_AFFINE;
+  if (chunk != DYNC_AFFINE) l1.tq = nullptr;
   const int ng = xcd_groups(g, C.n_et);
-  with_chunk<4 + 2 + 1>(chunk, [&](auto dync_) {
+  with_chunk<DYNC_AFFINE + 4 + 2 + 1>(chunk, [&](auto dync_) {
     hipLaunchKernelGGL((k_sweep_valu<OP, false, false, 0, decltype(dync_)::value, L1Q_GS>), dim3((unsigned)g), dim3(NT),
                        0, C.st, C.ent, C.e_pad, C.n_slice, C.q, C.q_pad, C.n_query, C.kp, C.n_et, C.e_base, ng, 0, 0.0f,
                        C.truth, C.q_true, nullptr, nullptr, nullptr, nullptr, (int64_t)0, C.counts, nullptr, l1);
@@ -3903,6 +3981,13 @@ struct EvalL1 {
   int32_t* row_cnt;
   int32_t* tile_m;
   int32_t* n_rows;
+  // the rows the map may hold: q_pad, or -- the grouped sweep's claim counters (L1Q::tq) live in
+  // row_cnt's tail -- the host's bound on the rows, padded to tiles; aff_n words at aff, zeroed
+  // here on every call (no launch or memset node of their own: graph replays and a second
+  // evaluation slot's workspace need nothing more)
+  int64_t row_lim;
+  uint32_t* aff;
+  int aff_n;
 };
 
 // canonical sum of squares over x[0..dim) (k ascending, LDS reads batched 16 per round) and
@@ -3966,18 +4051,18 @@ __global__ __launch_bounds__(256, 7) void k_eval_prep(EvalL1 P) {
     const int64_t total = s_scan[255], rows_pad = total > 0 ? (total + TQ - 1) / TQ * TQ : TQ;
     for (int64_t g = g0; g < g1; ++g) {
       const int64_t a = P.grp_qoff[g], n = P.grp_qoff[g + 1] - a;
-      for (int64_t j = 0; j < n && row < P.q_pad; j += cap, ++row) {
+      for (int64_t j = 0; j < n && row < P.row_lim; j += cap, ++row) {
         P.row_off[row] = (int32_t)(a + j);
         P.row_cnt[row] = (int32_t)(n - j < cap ? n - j : cap);
       }
     }
-    for (int64_t r = total + tid; r < rows_pad && r < P.q_pad; r += 256) {
+    for (int64_t r = total + tid; r < rows_pad && r < P.row_lim; r += 256) {
       P.row_off[r] = 0;
       P.row_cnt[r] = 0;
     }
     if (tid == 0) {
-      P.n_rows[0] = (int32_t)(total < P.q_pad ? total : P.q_pad);
-      P.n_rows[1] = (int32_t)(rows_pad < P.q_pad ? rows_pad : P.q_pad);
+      P.n_rows[0] = (int32_t)(total < P.row_lim ? total : P.row_lim);
+      P.n_rows[1] = (int32_t)(rows_pad < P.row_lim ? rows_pad : P.row_lim);
     }
     return;
   }
@@ -4126,8 +4211,10 @@ __global__ __launch_bounds__(256, 7) void k_eval_prep(EvalL1 P) {
     P.pstat[2 * bx] = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
     P.pstat[2 * bx + 1] = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
   }
-  if (bx == 0)
+  if (bx == 0) {
     for (int i = 2 + tid; i < L1Q_PART / 4; i += 256) P.hdr[i] = 0u;
+    for (int i = tid; i < P.aff_n; i += 256) P.aff[i] = 0u;  // the grouped sweep's claim counters
+  }
 }
 
 // The filter-list score of one entry (k_filter_scores' list task, TransE L1, prediction = the
@@ -5303,6 +5390,17 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   }
   const bool grouped = row_cap > 0;
   const int64_t rows_max = grouped ? std::min<int64_t>(n_query, n_groups + n_query / row_cap) : n_query;
+  // The grouped sweep's row-tile-affine claims (sweep_valu_body) need 8 x l1q_affine_stride
+  // zeroed words per call. The workspace does not grow for them: the row map holds at most
+  // rows_max rows, padded to a tile, so the words of row_cnt past that bound are dead (k_eval_prep
+  // is held to the bound, every reader to the row count), and the counters are its last words --
+  // whole 128-B lines, q_pad and the stride being multiples of 32 words. Where the bound leaves no
+  // such tail (a row per query) the sweep keeps the group's sequential counter.
+  // MMRE_SWEEP_AFFINE=0: the sequential counter (A/B, tests; read per call).
+  const char* aff_env = getenv("MMRE_SWEEP_AFFINE");
+  const int64_t aff_words = 8LL * l1q_affine_stride(q_pad), rows_lim = round_up(rows_max, TQ);
+  const bool affine = grouped && !(aff_env && aff_env[0] == '0') && q_pad - rows_lim >= aff_words;
+  uint32_t* aff = affine ? (uint32_t*)W.row_cnt + (q_pad - aff_words) : nullptr;
   static const char* tight_env = getenv("MMRE_L1_TIGHT");  // (once per process here)
   const int bits = l1q_bits();
   const bool tight = kt <= 1984 && !(tight_env && tight_env[0] == '0');
@@ -5345,6 +5443,9 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   P.row_cnt = W.row_cnt;
   P.tile_m = W.tile_m;
   P.n_rows = W.n_rows;
+  P.row_lim = affine ? rows_lim : q_pad;
+  P.aff = aff;
+  P.aff_n = affine ? (int)aff_words : 0;
   // K1: the row map (block 0, grouped) | prep + truths + |x| statistics
   hipLaunchKernelGGL(k_eval_prep, dim3((unsigned)((grouped ? 1 : 0) + P.n_eblk + P.n_qblk)), dim3(256), lds1, st, P);
   MMRE_CHECK_LAUNCH();
@@ -5428,6 +5529,7 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
     l1.grp_q = d_grp_q;
     l1.tile_m = W.tile_m;
     l1.n_rows = W.n_rows;
+    l1.tq = aff;
   }
   if (heavy) l1.routed = R.flags;
   L1Q l16 = l1;
