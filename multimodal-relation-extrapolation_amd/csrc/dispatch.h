@@ -33,6 +33,21 @@ template <class F>
 int with_bool(bool b, F&& f) {
   return b ? f(std::true_type{}) : f(std::false_type{});
 }
+template <class F>  // f(a_, b_, c_)
+int with_bools(bool a, bool b, bool c, F&& f) {
+  return with_bool(a, [&](auto a_) {
+    return with_bool(b, [&](auto b_) { return with_bool(c, [&](auto c_) { return f(a_, b_, c_); }); });
+  });
+}
+
+// f(std::integral_constant<int, OP>) for the link sweeps' score operator op = op_of_model(model), 0 .. 4
+template <int OP = 0, class F>
+int with_op(int op, F&& f) {
+  if constexpr (OP < 4) {
+    if (op != OP) return with_op<OP + 1>(op, f);
+  }
+  return f(std::integral_constant<int, OP>{});
+}
 
 // the five models
 template <class F>

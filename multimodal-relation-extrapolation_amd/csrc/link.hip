@@ -8,44 +8,31 @@
 // 128-wide tile is a single contiguous 512-byte row: coalesced 16-B loads into LDS,
 // conflict-free LDS reads, no transposes inside the hot loop.
 //
-// Kernels (per evaluation, one stream):
-//   k_prep_rows       table -> k-major plane + row-major copy (F.normalize for TransE norm_flag)
+// Kernels defined here (per evaluation, one stream):
+//   k_prep_rows, k_prep_km_gated   table -> k-major plane + row-major copy (F.normalize for TransE
+//                     norm_flag); the planes alone, gated on a device flag
 //   k_prep_queries    (h, r, t, mode) -> k-major query vectors (+ truth ids)
 //   k_truth_filter    pred(truth) per query (the sweep's arithmetic) and the filtered-rank
 //                     correction, one workgroup per filter group (queries sharing a list)
-//   k_sweep_valu      TransE L1/L2, RotatE: VALU 8x8 register micro-tiles
+//   k_filter_scores, k_filter_count   the grouped truth + filter pass, two phases
+//   k_counts_finalize filtered columns += raw columns, after a sweep
 //   k_sweep_mfma      DistMult/ComplEx: v_mfma_f32_32x32x2_f32, register-counter epilogue
+//   k_bf3_*, k_sweep_bf3, k_sweep_bf3w   the split-bf16 MFMA filter in front of it
+//   k_l1q_*, k_zero_words           TransE L1's integer filter: quantisation, probe, route
+//   k_eval_*, k_heavy_rows          the fused TransE L1 evaluation
+// Not here: the VALU sweep (k_sweep_valu: TransE L1/L2, RotatE and the integer filter's code
+// sweeps, 49 of the engine's 102 kernels) is link_valu.hip, reached through launch_valu<OP>,
+// launch_valu_grp<OP> and valu_grp_fills_grid. link_common.h holds what the two units share.
 #include <stdlib.h>
 
 #include <algorithm>
 #include <map>
 #include <mutex>
 #include <tuple>
-#include <type_traits>
 
-#include "mmre_common.h"
+#include "link_common.h"
 
 namespace mmre {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));  // a v_pk_*_f32 operand pair
-
-constexpr int TQ = 128;   // queries per workgroup tile
-constexpr int TE = 128;   // entities per workgroup tile
-constexpr int KC = 8;     // K rows per LDS stage
-constexpr int NT = 256;   // threads per workgroup
-
-// rows per plane: TransE/DistMult use one plane of plane_rows(model, d) rows;
-// ComplEx/RotatE use two planes (re, im) of plane_rows(model, d) rows each.
-// DistMult/ComplEx planes are padded to whole 16-row LDS stages of the MFMA sweep (zero rows
-// add exact zeros to the fma chain; a 32-row stage measured slower: C3 1.27 vs 1.18 ms, C5
-// 37.9 vs 36.6 ms at 248 VGPRs); TransE/RotatE to the VALU sweep's 8.
-constexpr int KS_MFMA = 16;
-__host__ __device__ inline int n_planes(int model) { return (model == MMRE_COMPLEX || model == MMRE_ROTATE) ? 2 : 1; }
-__host__ __device__ inline bool mfma_model(int model) { return model == MMRE_DISTMULT || model == MMRE_COMPLEX; }
-// MFMA planes: K = n_planes x plane_rows a multiple of 16 (ComplEx d = 200: 2 x 200, no padding)
-inline int plane_rows(int model, int dim) {
-  return (int)round_up(dim, !mfma_model(model) ? KC : KS_MFMA / n_planes(model));
-}
 
 // ------------------------------------------------------------------ prep ----
 // Both prep kernels stage a block of rows through LDS (row stride kt+1: odd, so the
@@ -274,29 +261,6 @@ __global__ __launch_bounds__(256) void k_prep_queries(int model, const float* __
   }
 }
 
-// A value the compiler cannot see through: what is computed from it is computed where it is
-// used, not hoisted out of a loop into a register (or scratch) kept live across the loop.
-__device__ __forceinline__ int vgpr_opaque(int x) {
-  __asm__ volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ float vgpr_opaque_f(float x) {
-  __asm__ volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ uint64_t sgpr_opaque64(uint64_t x) {
-  __asm__ volatile("" : "+s"(x));
-  return x;
-}
-__device__ __forceinline__ uint32_t sgpr_opaque(uint32_t x) {
-  __asm__ volatile("" : "+s"(x));
-  return x;
-}
-__device__ __forceinline__ int sgpr_opaque(int x) {
-  __asm__ volatile("" : "+s"(x));
-  return x;
-}
-
 // v_writelane_b32 with an immediate lane select (the lane must be a compile-time constant after
 // unrolling: the switch folds away). Writes the wave-uniform s into lane `lane` of v.
 template <int L>
@@ -372,226 +336,6 @@ __device__ __forceinline__ int writelane_imm(int v, int s, int lane) {
     case 63: return writelane_c<63>(v, s);
     default: return v;
   }
-}
-
-// ------------------------------------------------------------ score ops ----
-// OP: 0 TransE L1, 1 TransE L2, 2 RotatE, 3 DistMult, 4 ComplEx, 5 / 6 TransE L1 on 16-bit /
-// 8-bit codes (the integer filter; acc carries a uint32 in float bits). One k step.
-template <int OP>
-__device__ __forceinline__ float op_step(float acc, float qa, float qb, float x, float y) {
-  if constexpr (OP == 0) {
-    return acc + fabsf(qa - x);
-  } else if constexpr (OP == 1) {
-    float d = qa - x;
-    return acc + d * d;
-  } else if constexpr (OP == 2) {
-    float dr = qa - x, di = qb - y;
-    return acc + sqrtf(__builtin_fmaf(di, di, dr * dr));
-  } else if constexpr (OP == 5) {  // TransE L1 integer filter: two 16-bit codes per dword
-    return __uint_as_float(__builtin_amdgcn_sad_u16(__float_as_uint(qa), __float_as_uint(x), __float_as_uint(acc)));
-  } else if constexpr (OP == 6) {  // TransE L1 integer filter: four 8-bit codes per dword
-    return __uint_as_float(__builtin_amdgcn_sad_u8(__float_as_uint(qa), __float_as_uint(x), __float_as_uint(acc)));
-  } else {
-    return __builtin_fmaf(x, qa, acc);
-  }
-}
-template <int OP>
-__device__ __forceinline__ float op_final(float acc) {
-  if constexpr (OP == 1) return sqrtf(acc);
-  else return acc;
-}
-// RotatE's |(dr, di)| = sqrt(v), v = fma(di, di, dr*dr), correctly rounded, for the sweep's inner
-// loop, in full-rate f32 arithmetic only: y = v_rsq_f32(v), s = v*y, h = y/2, then one
-// Newton step s + (v - s*s)*h in fma form. Checked exhaustively on MI355X against IEEE
-// sqrtf over every float input (scripts/probes/sqrt_candidates.hip): exact for all
-// v in [2^-96, FLT_MAX]; it is not for v = 0, v < 2^-96 or v = inf, so the caller tracks
-// min(v) and the accumulators' NaN-ness and recomputes such a (rare) tile with sqrtf.
-__device__ __forceinline__ float rot_mag(float v, float y) {  // y = v_rsq_f32(v)
-  const float s = v * y, h = 0.5f * y;
-  const float e = __builtin_fmaf(-s, s, v);
-  return __builtin_fmaf(e, h, s);
-}
-constexpr float kRotMin = 0x1p-96f;
-
-// RotatE's fast filter (the plain and type-constrained sweeps; the score-storing sweep keeps
-// the exact chain): the inner loop takes the raw v_sqrt_f32, which is within 1 ulp of the
-// correctly rounded sqrtf on every normal input and within 2^-63 on denormal ones
-// (scripts/probes/sqrt_ulp.hip, exhaustive on MI355X). Both chains add non-negative terms in
-// the same order, so with S' the fast sum and S the canonical one
-//   |S' - S| <= sum_k |m'_k - m_k| + the two chains' rounding errors
-//            <= (kp + 1) 2^-23 S' (1 + small) + kp 2^-63,
-// and rot_bound() returns a bound above that. A pair whose prediction is on the same side of
-// the threshold at both ends of [S' - B, S' + B] (every apply_pred kind is monotone in S) is
-// decided; the few others (~2e-4 of the pairs on the C4 tables) and any non-finite S' are
-// rescored exactly by rot_exact (IEEE sqrtf, the canonical chain), so the counts are the
-// canonical ones bit for bit.
-__device__ __forceinline__ float rot_bound(float s, int kp) {
-  const float f = (float)(kp + 4) * 0x1p-23f * (1.0f + 0x1p-8f);
-  return __builtin_fmaf(s, f, (float)kp * 0x1p-62f);
-}
-__device__ __forceinline__ float rot_exact(const float* __restrict__ q_km, int64_t q_pad, int64_t q,
-                                        const float* __restrict__ ent_km, int64_t e_pad, int64_t e, int kp) {
-  float acc = 0.0f;
-#pragma unroll 8
-  for (int k = 0; k < kp; ++k)
-    acc = op_step<2>(acc, q_km[(int64_t)k * q_pad + q], q_km[(int64_t)(kp + k) * q_pad + q],
-                     ent_km[(int64_t)k * e_pad + e], ent_km[(int64_t)(kp + k) * e_pad + e]);
-  return acc;
-}
-
-// TransE L1's integer filter (count-only sweeps, mmre_link_sweep_l1q). The k-major planes are
-// quantized once per evaluation to 16-bit codes Q(x) = rint((x + M) * 65535 / 2M), M the
-// largest |x| over both planes, two consecutive k per dword, and the sweep's inner loop is
-// one v_sad_u16 per two elements (|a.lo - b.lo| + |a.hi - b.hi| + acc: half rate, i.e. one
-// issue slot per element against two for sub + add-with-abs; scripts/probes/sad_rate.hip).
-// delta * sum|Qq - Qe| is within K delta (1 + small) of the real sum |q - e| (each code is off
-// by at most 1/2 + the float rounding of the map), and the canonical f32 chain is within
-// (K + 1) 2^-24 S of it, so B = 1.03 K delta + (K + 4) 2^-23 S' bounds |S' - S|; decided /
-// undecided pairs as for RotatE (rot_bound), the undecided rescored exactly from the
-// row-major copies (l1_exact_rows: the canonical chain, acc + |q_k - e_k| in k order).
-// M non-finite (an inf / NaN anywhere in the planes): delta = inf, every pair is undecided.
-// Round 4: the default code width is 8 bits -- four k per dword, ONE v_sad_u8 per four elements
-// at the issue cost of one v_sad_u16 (scripts/probes/sad8_rate.hip: 4.4 vs 4.7 SIMD-cycles per
-// wave-instruction), i.e. half the inner loop -- with the same bound at delta = 2M / 255 (a band
-// 257x wider: 0.38 % of the trained C2 pairs undecided, scripts/probes/transe_quant_frac.py).
-// Whether that band pays depends on the data (how many scores sit that close to the
-// thresholds: xavier-init tables, whose truths rank mid-table, put tens of percent there), so
-// k_l1q_probe counts the undecided pairs of a fixed sample with the 8-bit codes and, over
-// L1Q_PROBE_FRAC of it, the 16-bit codes are made and swept instead. The choice is one device
-// word (hdr[1]); the three sweeps (8-bit, 16-bit, f32) are launched gated on it, and the one it
-// names counts -- no host round trip.
-// Workspace header (L1Q_HDR bytes before the code planes): word 0 = bits of M, word 1 = the
-// code-width word (L1Q_CODES8 / L1Q_F32 / L1Q_CODES16), word 2 = the probe's undecided pairs,
-// L1Q_SLOTS undecided-pair counters (uint64, L1Q_SLOT_STRIDE apart: separate cache lines) from
-// byte 256, the absmax blocks' partial sums of |x| from byte L1Q_PART. Zeroed up to L1Q_PART by
-// the launch sequence. The 16-bit planes follow the header, then the 8-bit planes.
-constexpr uint32_t L1Q_CODES8 = 0u, L1Q_F32 = 1u, L1Q_CODES16 = 2u;
-constexpr int L1Q_HDR = 8192;
-constexpr int L1Q_SLOTS = 16;
-constexpr int L1Q_SLOT_STRIDE = 32;  // uint64 units = 256 B
-constexpr int L1Q_PART = 256 + L1Q_SLOTS * L1Q_SLOT_STRIDE * 8;
-constexpr int L1Q_MAX_BLOCKS = 512;
-struct L1Q {
-  const float* q_rows;     // (queries, kt) row-major query vectors
-  const float* ent_rows;   // (whole table, kt) row-major entity rows
-  const uint32_t* hdr;     // workspace header: hdr[0] bits of M, hdr[1] code-width word, hdr[2] probe count
-  unsigned long long* undecided;  // counter slots
-  const float* q_f;        // fallback: the f32 k-major planes (query, entity slice) and their rows
-  const float* ent_f;
-  int kp_f;
-  int kt;                  // floats per row (the canonical chain's length, padding rows are 0)
-  const uint32_t* gate;    // gated launches: run only if *gate is the sweep's code-width word (L1Q_F32 for the f32 sweep)
-  const float* q_l1c;      // 8-bit codes, tight bound: per query row sum |eps_q| (upper bound); nullptr: uniform bound
-  uint32_t* guard;         // hdr[4]: pairs the rescoring refused (query or entity id out of range; must stay 0)
-  uint32_t* und_q;         // optional per-query count of rescored pairs (cost calibration of the sharding)
-  int32_t* fin_counts;     // gated f32 launch of the fused evaluation: the finalize (filtered += raw) rides
-  int64_t fin_n;           // on it -- every workgroup's slice when the gate is shut, the last workgroup's
-  uint32_t* fin_ticket;    // pass after the sweep when it is open (fin_counts nullptr: a separate launch)
-  uint32_t* wq;            // dynamic unit scheduling: one zeroed work counter per XCD group (nullptr: static ranges)
-  // grouped sweep (the fused evaluation; k_eval_prep's row map): sweep row -> its first member's
-  // position in grp_q and its member count; per row tile the largest count; [0] rows, [1] rows
-  // padded to whole tiles. q_l1c is then per ROW, and the code planes hold one column per row.
-  const int32_t* row_off;
-  const int32_t* row_cnt;
-  const int32_t* grp_q;
-  const int32_t* tile_m;
-  const int32_t* n_rows;
-  // per-query route (the fused evaluation): the 8-bit sweeps leave out a query whose
-  // byte in `routed` is set (nullptr: no route); k_heavy_rows counts the routed list's queries
-  // instead
-  const uint8_t* routed;
-  // grouped sweep, row-tile-affine claims (l1q_affine_stride): per XCD group a hint word and one
-  // claim counter per row tile, zeroed by k_eval_prep (nullptr: the group's sequential counter, wq)
-  uint32_t* tq;
-  const uint32_t* route_n;    // (unused since k_heavy_rows takes the list itself; kept so that the
-                              // sweeps' kernel argument, and with it their code, stays as measured)
-};
-// Header words of the route's record (zeroed with the header by K1, written by k_l1q_route_compact):
-// flagged queries, routed queries (k_heavy_rows' query count), sampled columns, flag threshold
-constexpr int L1Q_ROUTE_W = 8;
-// The sweeps' dynamic-scheduling work counters (L1Q::wq): one per XCD group, each on a 128-B
-// line of its own -- the second half of an undecided-pair counter slot (L1Q_SLOT_STRIDE bytes
-// apart from byte 256; the slot's counter uses its first 8 bytes) -- zeroed with the header
-// before every evaluation (k_zero_words / k_eval_prep). (Eight counters on one line serialised
-// every claim of the grid on that line: C2 sweep 1.03 -> 2.33 ms.) MMRE_SWEEP_DYN=0: the
-// static contiguous unit ranges (A/B).
-constexpr int L1Q_WQ_STRIDE = L1Q_SLOT_STRIDE * 2;  // uint32 words between two groups' counters
-inline uint32_t* l1q_work_counters(const uint32_t* hdr) {
-  static_assert(L1Q_SLOTS >= 8 && L1Q_SLOT_STRIDE * 8 >= 256, "a 128-B half slot per XCD group");
-  static const char* env = getenv("MMRE_SWEEP_DYN");
-  return (env && env[0] == '0') ? nullptr : const_cast<uint32_t*>(hdr) + (256 + 128) / 4;
-}
-// The grouped sweep's row-tile-affine claims (L1Q::tq; sweep_valu_body's claim_affine): per XCD
-// group a block of l1q_affine_stride words, whole 128-B lines of its own -- word 0 the group's
-// hint (every row tile below it is exhausted; it only rises), word 1 + t the claims made on row
-// tile t. Sized from q_pad, which host and device both know (the device's row tiles are at most
-// q_pad / TQ). The host finds the 8 blocks in the tail of the row map's row_cnt, which nothing
-// reads or writes past the rows' bound (mmre_link_evaluate_l1q), and k_eval_prep zeroes them.
-__host__ __device__ inline int l1q_affine_stride(int64_t q_pad) { return (int)((1 + q_pad / TQ + 31) / 32 * 32); }
-__device__ __forceinline__ float l1q_delta(const uint32_t* absmax, float levels) {
-  const float m = __uint_as_float(*absmax);
-  return m == 0.0f ? 0.0f : (m < INFINITY ? (2.0f * m) / levels : INFINITY);
-}
-// Integer thresholds of the L1 filter for one query row (prediction = the score): with a = delta
-// S_int, |S - a| <= l1f a + l1c, so S_int < x = (th - l1c) / (delta (1 + l1f)) gives S < th and
-// S_int >= y = (th + l1c) / (delta (1 - l1f)) gives S >= th; x, y shrunk / grown by 2^-18 against
-// the float rounding of their own computation. With the tight 8-bit bound the accumulator also
-// holds the entity's error offset o_e (its code row `words`: S_int + o_e), l1c is the query's own
-// error sum, and o_e >= sum |eps_e| / (delta (1 - l1f)): S_int + o_e < t_sure proves S < th and
-// S_int + o_e >= t_out + 2 o_max proves S >= th (o_max: the largest offset of the slice).
-__device__ __forceinline__ void l1_int_thresholds(float th, float l1c, float l1d, float l1f, uint32_t omax2,
-                                                  uint32_t& t_sure, uint32_t& t_span) {
-  uint32_t ts = 0u, to = 0xFFFFFFFFu;
-  if (l1d < INFINITY) {
-    const float x = (th - l1c) / (l1d * (1.0f + l1f)) * (1.0f - 0x1p-18f);
-    const float y = (th + l1c) / (l1d * (1.0f - l1f)) * (1.0f + 0x1p-18f);
-    ts = x > 0.0f ? (uint32_t)floorf(fminf(x, 0x1p31f)) : 0u;
-    to = y > 0.0f ? (uint32_t)ceilf(fminf(y, 0x1p31f)) : 0u;
-    // y <= 0 or NaN (a padding query row's -inf threshold, a NaN truth): no pair beats it, no
-    // band -- the offsets must not open one (a band there sent padding rows to the rescoring)
-    if (to != 0u) to = to + omax2 < to ? 0xFFFFFFFFu : to + omax2;
-  }
-  t_sure = ts;
-  t_span = to > ts ? to - ts : 0u;
-}
-
-// (U float4 pairs in flight per round: 5, or 3 inside the grouped sweep's slot loop, where the
-// tile's 64 accumulators stay live across the rescoring: 4 and 5 spilled 16 VGPRs there)
-template <int U = 5>
-__device__ __forceinline__ float l1_exact_rows(const float* __restrict__ q, const float* __restrict__ e, int kt) {
-  const float4* q4 = reinterpret_cast<const float4*>(q);
-  const float4* e4 = reinterpret_cast<const float4*>(e);
-  float acc = 0.0f;
-#pragma unroll U
-  for (int k = 0; k < kt / 4; ++k) {
-    const float4 a = q4[k], b = e4[k];
-    acc = acc + fabsf(a.x - b.x);
-    acc = acc + fabsf(a.y - b.y);
-    acc = acc + fabsf(a.z - b.z);
-    acc = acc + fabsf(a.w - b.w);
-  }
-  return acc;
-}
-
-__host__ __device__ inline int op_of_model(int model) {
-  return model == MMRE_TRANSE_L1 ? 0 : model == MMRE_TRANSE_L2 ? 1 : model == MMRE_ROTATE ? 2
-         : model == MMRE_DISTMULT ? 3 : 4;
-}
-
-__device__ __forceinline__ bool type_bit(const uint32_t* __restrict__ mask, int64_t words, int64_t r, int64_t e) {
-  return (mask[r * words + (e >> 5)] >> (e & 31)) & 1u;
-}
-// The type bits of a VALU-sweep thread's 8 entity columns for relation r: columns 0-3 are ids
-// e0 .. e0 + 3, columns 4-7 e0 + 64 .. e0 + 67 (e0 a multiple of 4: each group of four lies in
-// one 32-bit word); bit j = column j. Two loads per query row instead of one per pair, and no
-// per-pair branch (the per-pair `better && type_bit(...)` kept ~100 VGPRs of masks and
-// addresses live in the type-constrained sweeps: they spilled). Columns at or past e_end: 0.
-__device__ __forceinline__ uint32_t type_bits8(const uint32_t* __restrict__ mask, int64_t words, int64_t r, int e0,
-                                               int e_end) {
-  const uint32_t* row = mask + r * words;
-  const uint32_t lo = e0 < e_end ? (row[e0 >> 5] >> (e0 & 31)) & 15u : 0u;
-  const uint32_t hi = e0 + 64 < e_end ? (row[(e0 + 64) >> 5] >> (e0 & 31)) & 15u : 0u;
-  return lo | (hi << 4);
 }
 
 // Two scores of the query vector sq against entity rows e1 and e2 at once (two independent
@@ -908,47 +652,6 @@ __global__ __launch_bounds__(64) void k_filter_count(const int64_t* __restrict__
   }
 }
 
-// ------------------------------------------------------- work-unit map ---
-// Work unit = (query tile of TQ) x (entity tile of TE). XCD group g (workgroups g, g + G,
-// g + 2G, ...: the ones round-robin dispatch places on one XCD when the grid is a multiple of
-// G = 8) owns m = n_et / G whole entity tiles for every query tile (query-tile major, so its
-// L2 keeps streaming the same 1/G of the table and a workgroup leaves a query tile rarely),
-// then a 1/G share of the n_et % G leftover tiles' units. Every group gets the same number of
-// units +-1, so no XCD runs a whole extra round of units (C3: 100 entity tiles = 8 x 12 + 4;
-// whole-tile groups of 12 and 13 left the 13-tile XCDs 10 units per workgroup against 8.7).
-struct UnitMap {
-  int m, r, ex0, el0, n_main, lo0, count, nq;
-  bool emajor;  // entity-tile-major order inside the group (consecutive units share an entity tile)
-  __device__ __forceinline__ UnitMap(int grp, int n_groups, int n_qt, int n_et, bool emajor_ = false) {
-    nq = n_qt;
-    emajor = emajor_;
-    m = n_et / n_groups;
-    r = n_et - m * n_groups;
-    ex0 = grp * m;
-    el0 = m * n_groups;  // first leftover entity tile
-    n_main = n_qt * m;
-    const int64_t left = (int64_t)n_qt * r;
-    lo0 = (int)(left * grp / n_groups);
-    count = n_main + (int)(left * (grp + 1) / n_groups) - lo0;
-  }
-  // unit i (< count) of the group -> (query tile, entity tile)
-  __device__ __forceinline__ void at(int i, int& qt, int& et) const {
-    if (i < n_main) {
-      if (emajor) {
-        qt = i % nq;
-        et = ex0 + i / nq;
-      } else {
-        qt = i / m;
-        et = ex0 + i % m;
-      }
-    } else {
-      const int j = lo0 + (i - n_main);
-      qt = j / r;
-      et = el0 + j % r;
-    }
-  }
-};
-
 // Work units for a persistent grid whose P workgroups per XCD group run in lock-step windows
 // (k_sweep_bf3, round 5): the group owns the contiguous entity tiles [e_lo, e_hi); a window is
 // QB query tiles x EB entity tiles (QB x EB <= P), member m of the group always takes window
@@ -982,1010 +685,6 @@ struct BlockMap {
     et = e_lo + b * EB + ein;
   }
 };
-
-// ------------------------------------------------------------ VALU sweep ---
-// Work unit = (query tile of 128) x (entity tile of 128); units are ordered query-tile
-// major and split into equal contiguous ranges over a persistent grid sized to the
-// resident capacity (4 workgroups per CU), so no tail round is left half empty.
-// Within a unit: 256 threads as 16 (q) x 16 (e); each thread owns queries
-// {4tq..4tq+3, 64+4tq..} and entities {4te..4te+3, 64+4te..}: 64 fp32 accumulators, one
-// sequential k chain each (the canonical order). K is staged through LDS in
-// double-buffered steps of 8 rows (16 B per thread per plane per operand). Per-query
-// counts stay in registers until the workgroup moves to the next query tile.
-// LDS of one VALU-sweep workgroup. A struct declared once in the kernel, so that the L1
-// filter's kernel and its f32 fallback path (the same kernel, one uniform branch) share it.
-// Grouped sweep (the fused evaluation, GS > 0): a sweep row is one query VECTOR shared by up to GS
-// member queries; per member slot and row of the tile, the member's integer thresholds, its query
-// id (-1: no member) and its count accumulator (flushed when the workgroup leaves the row tile).
-// Single-buffered: the flush / reload sits between two workgroup barriers. An empty base for
-// GS = 0, so the ungrouped instantiations keep their LDS to the byte.
-template <int GS>
-struct ValuSmemGrp {
-  uint32_t g_ts[GS][TQ];
-  uint32_t g_tw[GS][TQ];
-  int32_t g_mq[GS][TQ];
-  uint32_t g_acc[GS][TQ];
-};
-template <>
-struct ValuSmemGrp<0> {};
-// k_sweep_valu's DYNC (units per claim of the dynamically scheduled instances: 1, 2, 4) for the
-// grouped sweep's row-tile-affine 1-unit claims (sweep_valu_body)
-constexpr int DYNC_AFFINE = 8;
-// Workgroups that start on one row tile. C2 (103 row tiles x 13 units per XCD group, 128 workgroups
-// per group), ms per evaluation against the sequential counter's 0.596: 1 (a tile each) 0.68 -- a
-// row tile's codes then have one reader, and every unit fetches them from beyond the L2 -- 2
-// 0.607, 4 0.577, 13 (a unit each) 0.64 (profiles/grouped_affine).
-constexpr int L1Q_AFFINE_SHARE = 4;
-constexpr int L1Q_GS = 8;  // member slots per sweep row: 8 KB + 2 KB per slot = 36 KB, four workgroups per CU
-// The grouped sweep runs when the host's bound on the sweep rows is at most this share of the
-// queries (mmre_link_evaluate_l1q). C2, 1-unit claims: rows at 0.373 / 0.448 / 0.620 / 1.0 of the
-// queries (caps 8 / 4 / 2 / 1) 0.709 / 0.807 / 0.915 / 1.268 ms against the ungrouped 0.980: the
-// break-even is near 0.69 of the true rows, which the bound overstates by up to 1/8.
-constexpr double L1Q_GROUP_FRAC = 0.6;
-
-template <int NPL, bool TC, bool LIST, int GS = 0>
-struct ValuSmem : ValuSmemGrp<GS> {
-  float4 sq[2][NPL][KC][TQ / 4];
-  float4 se[2][NPL][KC][TE / 4];
-  float s_thr[2][GS ? 1 : TQ];
-  int32_t s_true[2][GS ? 1 : TQ];
-  int32_t s_rel[2][TC ? TQ : 1];
-  int8_t s_mode[2][TC ? TQ : 1];
-  // per-thread counters (off the VGPR budget); 16-bit with type constraints, so that the wave
-  // lists fit beside them at four workgroups per CU (a thread adds <= 8 per unit and row; the
-  // sweep flushes every unit where a query tile could hold more than 8,190 of a workgroup's units)
-  std::conditional_t<TC, uint16_t, int32_t> s_cnt[TC ? 2 : 1][GS ? 1 : 8][GS ? 1 : NT];
-  uint32_t s_unc[NT / 64];           // undecided pairs per wave (the L1 filter's counter)
-  uint32_t s_ts[2][GS ? 1 : TQ];     // L1 filter, prediction = score: per query row, the integer
-  uint32_t s_tw[2][GS ? 1 : TQ];     // thresholds t_sure and t_out - t_sure (load_meta)
-  int s_unit;                        // dynamic scheduling: the unit after the one being swept
-  // type constraints: per unit (two in flight, by unit parity), the type words of its 128 query
-  // rows over its 128 entity columns -- words 0, 2, 1, 3 of the tile, so a thread's two words
-  // (columns 4te.., 64 + 4te..) are one 8-B read -- staged with the unit's first stage
-  uint32_t s_tb[TC ? 2 : 1][TC ? TQ : 1][4];
-  int2 s_pairs[LIST ? NT / 64 : 1][LIST ? 128 : 1];  // L1 filter: each wave's undecided (query, entity) pairs
-};
-
-// The sweep body. Counts go to the raw columns only (counts[0][q], counts[2][q]); the filtered
-// columns (initialised to minus the listed entities that beat the truth by the truth pass)
-// receive them in k_counts_finalize, one coalesced pass after the sweep (half the atomics).
-template <int OP, bool TC, bool STORE, int PK, int NPL, int DYNC, int GS = 0>
-__device__ __forceinline__ void sweep_valu_body(
-    ValuSmem<NPL, TC, (OP == 5 || OP == 6), GS>& sm, const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent,
-    const float* __restrict__ q_km, int64_t q_pad, int64_t n_query, int kp, int n_et, int e_base, int n_groups,
-    int pred_kind, float margin, const float* __restrict__ thr, const int32_t* __restrict__ qtrue,
-    const int64_t* __restrict__ qr, const int8_t* __restrict__ qmode, const uint32_t* __restrict__ type_head,
-    const uint32_t* __restrict__ type_tail, int64_t type_words, int32_t* __restrict__ counts,
-    float* __restrict__ scores, const L1Q& l1) {
-  static_assert(NPL == ((OP == 2) ? 2 : 1), "planes");
-  // filters: RotatE's raw-sqrt sum (rot_bound / rot_exact), TransE L1's 16-bit codes (L1Q)
-  constexpr bool L1F = OP == 5 || OP == 6;  // TransE L1's integer filter (16- / 8-bit codes)
-  constexpr bool w8 = OP == 6;
-  constexpr bool FAST = (OP == 2 || L1F) && !STORE;
-  // grouped sweep: one SAD chain per sweep row (a query vector), ranked against each member's
-  // thresholds in turn (the slot loop of the epilogue); see ValuSmemGrp and k_eval_prep's row map
-  constexpr bool GRP = GS > 0;
-  static_assert(!GRP || (L1F && PK == 0 && !TC && !STORE), "the grouped sweep is the plain integer filter's");
-  auto& sq = sm.sq;
-  auto& se = sm.se;
-  auto& s_thr = sm.s_thr;
-  auto& s_true = sm.s_true;
-  auto& s_rel = sm.s_rel;
-  auto& s_mode = sm.s_mode;
-  auto& s_cnt = sm.s_cnt;
-
-  const int tid = threadIdx.x;
-  const int tq = tid >> 4, te = tid & 15;
-  const PredSel<PK> pred(pred_kind, margin);
-  // XCD-aware split (UnitMap): the group's units split evenly over its workgroups, each a
-  // contiguous range -- or, with l1.wq (dynamic scheduling, a persistent grid), member m takes
-  // unit m of its group first and every further unit from the group's work counter. The loader
-  // runs one stage ahead of the compute and enters unit U at the top of compute stage nkc - 2 of
-  // the unit before; one stage later thread 0 claims U's successor and publishes it in LDS (its
-  // wave waits for the reply there; the other waves of the CU run on), and the loader reads it
-  // when it leaves U, >= 1 barrier later. (Holding the reply in a register across the stage
-  // instead made it loop-carried: 160 B of scratch per lane.) Units of uneven cost (the
-  // rescoring of undecided pairs) balance themselves instead of leaving a tail of workgroups.
-  const int grp = blockIdx.x % n_groups, gmem = blockIdx.x / n_groups;
-  const int per_grp = gridDim.x / n_groups;
-  // (grouped: the row tiles, known on the device only)
-  const int n_qt = GRP ? __builtin_amdgcn_readfirstlane(l1.n_rows[GRP ? 1 : 0]) / TQ : (int)(q_pad / TQ);
-  const UnitMap um(grp, n_groups, n_qt, n_et);
-  const int nkc = kp / KC;
-  // (compiled per mode and chunk: a runtime choice between the modes, or a runtime chunk size,
-  // kept values of both live across the loop -- 160-168 B of scratch per lane; the host passes
-  // l1.wq only with nkc >= 2)
-  constexpr bool dyn = DYNC > 0;
-  // dynamic scheduling claims chunks of consecutive units (the units of a group are query-tile
-  // major: a chunk mostly keeps its query tile, so its counts flush and its query metadata loads
-  // once, not at every unit): 4 when a workgroup sweeps many units, 1 for a rank's small share
-  // (valu_grid; C2 N = 1, per evaluation: chunks of 1 / 2 / 4 / 8 / 16 units 1.053 / 1.007 /
-  // 0.975 / 0.997 / 1.017 ms; 8-way shares: 1 or 2 best)
-  constexpr int ch_log2 = DYNC == DYNC_AFFINE ? 0 : DYNC >= 4 ? 2 : DYNC >= 2 ? 1 : 0;
-  constexpr int ch_mask = (1 << ch_log2) - 1;
-  int u0 = dyn ? gmem << ch_log2 : (int)((int64_t)gmem * um.count / per_grp);
-  const int u1 = dyn ? um.count : (int)((int64_t)(gmem + 1) * um.count / per_grp);
-  // DYNC_AFFINE (grouped, 1-unit claims, l1.tq): row-tile-affine claims. The sequential counter hands a
-  // workgroup a unit ~per_grp units on, ten row tiles later at C2, so every claim paid the flush
-  // / reload of the epilogue; here a claim (thread 0) takes the next unclaimed unit of row tile t
-  // in this XCD group -- its m main units, then its run of the group's leftover units, one counter
-  // over both (l1q_affine_stride) -- and, that tile exhausted, of the lowest row tile that has
-  // one: from the group's hint on, raising the hint past every tile it finds exhausted (a value
-  // read from the hint has only exhausted tiles below it, so hint = t + 1 after tile t = hint
-  // failed keeps that). It never waits for another workgroup: a round takes a unit or moves to a
-  // higher tile, and the claim is um.count (no unit) once the hint reaches the row tiles' count.
-  // The unit indices are UnitMap's; counts are integer sums, so the order of units is free.
-  // (an instance of its own, not a runtime choice beside the sequential counter: with both
-  // claims in one kernel the 8-bit instance spilled 8 VGPRs, 20 B of scratch per lane)
-  constexpr bool AFF = DYNC == DYNC_AFFINE;
-  static_assert(!AFF || GRP, "affine claims are the grouped sweep's");
-  auto claim_affine = [&](int t) -> int {
-    uint32_t* base = l1.tq + grp * l1q_affine_stride(q_pad);
-    const int lo1 = um.lo0 + (um.count - um.n_main);  // the end of the group's leftover run
-    bool hinted = false;
-    for (;;) {  // (one lane runs this: the replies go to SGPRs, the rounds are scalar code)
-      const int c = __builtin_amdgcn_readfirstlane((int)atomicAdd(&base[1 + t], 1u));
-      if (c < um.m) return t * um.m + c;
-      const int j = max(um.lo0, t * um.r) + (c - um.m);
-      if (j < min(lo1, (t + 1) * um.r)) return um.n_main + (j - um.lo0);
-      const int old = __builtin_amdgcn_readfirstlane((int)atomicMax(&base[0], hinted ? (uint32_t)(t + 1) : 0u));
-      const int h = hinted ? max(old, t + 1) : old;
-      hinted = true;
-      if (h >= n_qt) return um.count;
-      t = h;
-    }
-  };
-  if constexpr (AFF) {
-    // the first unit is a claim like any other, on row tile (gmem / L1Q_AFFINE_SHARE) % n_qt (the
-    // members spread over the tiles, a few to a tile) -- after the gate: a shut launch must claim none
-    if (__builtin_amdgcn_readfirstlane(l1.hdr[1]) != (w8 ? L1Q_CODES8 : L1Q_CODES16)) return;
-    if (threadIdx.x == 0) sm.s_unit = claim_affine((gmem / L1Q_AFFINE_SHARE) % n_qt);
-    __syncthreads();
-    u0 = __builtin_amdgcn_readfirstlane(sm.s_unit);  // (overwritten after the first stage's barrier)
-  }
-  if (u0 >= u1) return;  // uniform over the workgroup
-
-  // L1 filter constants (uniform): code step, bound slope and offset
-  float l1d = 0.0f, l1f = 0.0f, l1c = 0.0f;
-  if constexpr (L1F) {
-    l1d = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(l1q_delta(l1.hdr, w8 ? 255.0f : 65535.0f))));
-    l1f = (float)(l1.kt + 4) * 0x1p-23f * (1.0f + 0x1p-8f);
-    l1c = __builtin_fmaf((float)l1.kt * 1.03f, l1d, 0x1p-120f);
-  }
-
-  // load_meta and the count flush run once per query tile; what they compute from tid and the
-  // filter constants is recomputed there from opaque copies (vgpr_opaque / sgpr_opaque), not
-  // hoisted by the compiler into per-lane values kept live across the sweep (that kept ~21 of
-  // them in scratch: a scratch store of ~90 B per lane at every wave's start)
-  auto load_meta = [&](int qtile, int slot) {
-    const int tid = vgpr_opaque(threadIdx.x);
-    if (tid < TQ) {
-      const int64_t q = (int64_t)qtile * TQ + tid;
-      const bool v = q < n_query;
-      const float th = v ? thr[q] : -INFINITY;
-      s_thr[slot][tid] = th;
-      s_true[slot][tid] = v ? qtrue[q] : -1;
-      if constexpr (L1F && PK == 0) {
-        // prediction = the score: the filter decides in the integer domain. With a = delta *
-        // S_int, |S - a| <= l1f a + l1c, so S_int < x = (th - l1c) / (delta (1 + l1f)) gives
-        // S < th and S_int >= y = (th + l1c) / (delta (1 - l1f)) gives S >= th; x, y are shrunk /
-        // grown by 2^-18 against the float rounding of their own computation. Once per query
-        // row and query tile, not per unit.
-        uint32_t t_sure, t_span;
-        const bool tight = w8 && l1.q_l1c != nullptr;
-        const int ktm = sgpr_opaque(l1.kt);
-        const float md = __uint_as_float(sgpr_opaque(__float_as_uint(l1d)));
-        const float mf = (float)(ktm + 4) * 0x1p-23f * (1.0f + 0x1p-8f);  // = l1f
-        const float mc = __builtin_fmaf((float)ktm * 1.03f, md, 0x1p-120f);  // = l1c
-        l1_int_thresholds(th, tight ? (v ? l1.q_l1c[q] : 0.0f) + 0x1p-120f : mc, md, mf, tight ? 2u * l1.hdr[3] : 0u,
-                          t_sure, t_span);
-        if constexpr (w8) {
-          // a routed query (k_heavy_rows counts it): no sure pair, no band, as a padding row
-          if (l1.routed != nullptr && v && l1.routed[q]) t_sure = t_span = 0u;
-        }
-        sm.s_ts[slot][tid] = t_sure;
-        sm.s_tw[slot][tid] = t_span;
-      }
-      if constexpr (TC) {
-        s_rel[slot][tid] = v ? (int32_t)qr[q] : 0;
-        s_mode[slot][tid] = v ? qmode[q] : 0;
-      }
-    }
-  };
-
-  // Grouped: the row tile's member slots. Entry idx = slot * TQ + row is always thread idx % NT's
-  // (here and in the flush), so reload and flush need no barrier between them. A slot without a
-  // member (or a padding row) gets t_sure = t_span = 0: it neither counts nor lists a pair.
-  // Returns the tile's slot count (uniform).
-  auto load_meta_grp = [&](int qtile) -> int {
-    int m = 0;
-    if constexpr (GRP) {
-      const int tid = vgpr_opaque(threadIdx.x);
-      m = min(__builtin_amdgcn_readfirstlane(l1.tile_m[qtile]), GS);
-      const bool tight = w8 && l1.q_l1c != nullptr;
-      const int ktm = sgpr_opaque(l1.kt);
-      const float md = __uint_as_float(sgpr_opaque(__float_as_uint(l1d)));
-      const float mf = (float)(ktm + 4) * 0x1p-23f * (1.0f + 0x1p-8f);  // = l1f
-      const float mc = __builtin_fmaf((float)ktm * 1.03f, md, 0x1p-120f);  // = l1c
-      const uint32_t om2 = tight ? 2u * l1.hdr[3] : 0u;
-      // thread t: row t % TQ, slots t / TQ + 2 u -- entry t + u NT. Three dependent rounds of
-      // loads for all of them at once (the row's map entry and error sum; its members' ids; their
-      // thresholds), not a chain per entry: the workgroup waits here once per row tile.
-      static_assert(NT == 2 * TQ && GS % 2 == 0, "two slots' rows per pass");
-      const int r = tid % TQ, s0 = tid / TQ;
-      const int64_t row = (int64_t)qtile * TQ + r;
-      const int cnt = l1.row_cnt[row];
-      const int64_t off = l1.row_off[row];
-      const float rc = tight ? l1.q_l1c[row] : 0.0f;
-      int q[GS / 2];
-      float th[GS / 2];
-#pragma unroll
-      for (int u = 0; u < GS / 2; ++u) {
-        q[u] = -1;
-        if (s0 + 2 * u < cnt) {
-          const int qq = l1.grp_q[off + s0 + 2 * u];
-          q[u] = (uint32_t)qq < (uint32_t)n_query ? qq : -1;
-        }
-      }
-      if constexpr (w8) {
-        // a routed member (k_heavy_rows counts it) becomes an empty slot. A round of its
-        // own, before the thresholds': with the bytes in flight beside the thresholds the tile's
-        // 64 accumulators no longer fit (8 VGPRs spilled); once per row tile.
-        if (l1.routed != nullptr) {
-#pragma unroll
-          for (int u = 0; u < GS / 2; ++u)
-            if (q[u] >= 0 && l1.routed[q[u]]) q[u] = -1;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < GS / 2; ++u) th[u] = q[u] >= 0 ? thr[q[u]] : -INFINITY;
-#pragma unroll
-      for (int u = 0; u < GS / 2; ++u) {
-        const int sl = s0 + 2 * u;
-        if (sl < m) {
-          uint32_t t_sure, t_span;
-          l1_int_thresholds(th[u], tight ? (q[u] >= 0 ? rc : 0.0f) + 0x1p-120f : mc, md, mf, om2, t_sure, t_span);
-          sm.g_ts[GRP ? sl : 0][r] = t_sure;
-          sm.g_tw[GRP ? sl : 0][r] = t_span;
-          sm.g_mq[GRP ? sl : 0][r] = q[u];
-        }
-      }
-    }
-    return m;
-  };
-
-  const int srow = tid >> 5, sc4 = tid & 31;
-  float4 rq0, re0, rq1, re1;  // plane 0 / plane 1 (RotatE) staging: scalars, kept in VGPRs
-  // staging position (unit, kc) of the next load, advanced incrementally (no divisions)
-  int ld_unit = u0, ld_kc = 0, ld_qt, ld_et;
-  um.at(u0, ld_qt, ld_et);
-  // type constraints: the staged unit's type words (row tid / 2, words (tid & 1) and 2 + (tid & 1)),
-  // whether the pending stage carries them, and the unit parity they go to (the epilogue's
-  // ep_par reads them back); the loader's parity starts at 1 so that unit u0 gets 0
-  uint32_t rt0 = 0u, rt1 = 0u;
-  bool st_new = false;
-  int ld_tpar = 1, st_par = 0, ep_par = 0;
-  auto gload = [&]() {
-    if constexpr (TC) {
-      st_new = ld_kc == 0;
-      if (st_new) {  // the unit's first stage: its rows' type words ride along
-        ld_tpar ^= 1;
-        st_par = ld_tpar;
-        const int tt = vgpr_opaque(threadIdx.x);
-        const int rr = tt >> 1, jw = tt & 1;
-        const int64_t q = (int64_t)ld_qt * TQ + rr;
-        uint32_t w0 = 0u, w1 = 0u;
-        if (q < n_query) {
-          const uint32_t* tm = (qmode[q] == MMRE_HEAD_BATCH ? type_head : type_tail) + qr[q] * type_words;
-          const int64_t wb = (e_base + (int64_t)ld_et * TE) >> 5;  // e_base and tiles: whole words
-          if (wb + jw < type_words) w0 = tm[wb + jw];
-          if (wb + 2 + jw < type_words) w1 = tm[wb + 2 + jw];
-        }
-        rt0 = w0;
-        rt1 = w1;
-      }
-    }
-    const int k = ld_kc * KC + srow;
-    const int64_t q0 = (int64_t)ld_qt * TQ, e0 = (int64_t)ld_et * TE;
-    const float* qp = q_km + (int64_t)k * q_pad + q0 + sc4 * 4;
-    const float* ep = ent_km + (int64_t)k * e_pad + e0 + sc4 * 4;
-    rq0 = *reinterpret_cast<const float4*>(qp);
-    re0 = *reinterpret_cast<const float4*>(ep);
-    if constexpr (NPL == 2) {
-      rq1 = *reinterpret_cast<const float4*>(qp + (int64_t)kp * q_pad);
-      re1 = *reinterpret_cast<const float4*>(ep + (int64_t)kp * e_pad);
-    }
-    if (++ld_kc == nkc) {
-      ld_kc = 0;
-      if (dyn) {
-        // the next unit of the chunk, or the first of the claimed chunk (published >= 1 barrier ago)
-        ld_unit = ((ld_unit + 1) & ch_mask) != 0 ? ld_unit + 1 : sm.s_unit;
-        if (ld_unit < u1) um.at(ld_unit, ld_qt, ld_et);
-      } else if (++ld_unit < u1) {
-        um.at(ld_unit, ld_qt, ld_et);
-      }
-    }
-  };
-  auto swrite = [&](int buf) {
-    if constexpr (TC) {
-      if (st_new) {
-        const int tt = vgpr_opaque(threadIdx.x);
-        *reinterpret_cast<uint2*>(&sm.s_tb[st_par][tt >> 1][(tt & 1) * 2]) = make_uint2(rt0, rt1);
-      }
-    }
-    sq[buf][0][srow][sc4] = rq0;
-    se[buf][0][srow][sc4] = re0;
-    if constexpr (NPL == 2) {
-      sq[buf][NPL - 1][srow][sc4] = rq1;
-      se[buf][NPL - 1][srow][sc4] = re1;
-    }
-  };
-
-  float acc[8][8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = 0.0f;
-  f32x2 accp[4][8];  // RotatE filter: the packed accumulators (pair layout at the inner loop)
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) accp[i][j] = f32x2{0.0f, 0.0f};
-  if constexpr (GRP) {
-    for (int idx = tid; idx < GS * TQ; idx += NT) (&sm.g_acc[0][0])[idx] = 0u;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      s_cnt[0][i][tid] = 0;
-      if constexpr (TC) s_cnt[TC ? 1 : 0][i][tid] = 0;
-    }
-  }
-  if (L1F && tid < NT / 64) sm.s_unc[tid] = 0u;
-  // L1 filter: the wave's undecided pairs are appended to its LDS list (ballot order, no
-  // atomics) and rescored 64 at a time, one pair per lane, whenever the list holds a full
-  // batch -- the dependent row loads of the canonical chain are paid once per 64 pairs, not once
-  // per lane-pair with the wave waiting on its busiest lane (which made the 8-bit codes' 0.4 %
-  // of undecided pairs cost 0.8 ms at C2). Rescored pairs that beat their threshold go straight
-  // to the raw count columns (the query tile's counts may have been flushed already).
-  // (Type-constrained sweeps too, since round 6: 16-bit LDS counters make room for the list at
-  // four workgroups per CU; their per-lane loop kept 232-240 B of scratch per lane.)
-  constexpr bool LIST = L1F;
-  int list_n = 0;         // wave-uniform
-  uint32_t n_listed = 0;  // the wave's undecided pairs (the filter's counter; per lane without the list)
-  // A batch of listed pairs, one per lane (active lanes): each rescored with the canonical chain;
-  // the beating pairs' raw counts go out as ONE atomic per distinct query of the batch (a wave's
-  // 64 pairs come from its 32 query rows, and the undecided pairs concentrate on few queries --
-  // C2: half of the 1.09 M in 103 queries of ~7,000 beating pairs each -- whose count words were
-  // a same-address chain of per-pair atomics, serialised at ~13 ns each).
-  auto rescore = [&](int2 p, bool active) {
-    const int64_t q = p.x;
-    const int e = p.y;
-    // a guard on the list's invariant: every entry is a (query row, slice column) pair of the
-    // unit just swept, with q < n_query (padding query rows open no band) and 0 <= e < n_ent.
-    // A pair outside is counted in hdr[4] (mmre_link_l1q_stats, asserted 0 by the filter tests)
-    // and never reaches a row gather.
-    bool ok = active;
-    if (active && ((uint64_t)q >= (uint64_t)n_query || (uint32_t)e >= (uint32_t)n_ent)) {
-      if (l1.guard) atomicAdd(l1.guard, 1u);
-      ok = false;
-    }
-    if constexpr (GRP) {
-      // grouped: a member's own truth is skipped here (the slot loop keeps no truth ids in LDS),
-      // and the pairs are counted here, after the skip
-      if (ok && e + e_base == qtrue[q]) ok = false;
-      n_listed += (uint32_t)__builtin_popcountll(__ballot(ok));
-    }
-    bool beat = false;
-    if (ok) {
-      if (l1.und_q) atomicAdd(&l1.und_q[q], 1u);
-      const float th = thr[q];
-      const float sx = l1_exact_rows<GRP ? 3 : 5>(l1.q_rows + q * (int64_t)l1.kt,
-                                                  l1.ent_rows + (int64_t)(e + e_base) * l1.kt, l1.kt);
-      beat = pred(sx) < th;
-      if constexpr (TC) {
-        const uint32_t* tm = qmode[q] == MMRE_HEAD_BATCH ? type_head : type_tail;
-        if (beat && type_bit(tm, type_words, qr[q], e + e_base)) atomicAdd(&counts[2 * n_query + q], 1);
-      }
-    }
-    const int qi = (int)q;  // (int32 ids: check_link_args)
-    uint64_t pend = __ballot(beat);
-    while (pend) {  // uniform: one query of the batch per round
-      const int leader = __builtin_ctzll(pend);
-      const int ql = __builtin_amdgcn_readlane(qi, leader);
-      const bool mine = beat && qi == ql;
-      const uint64_t same = __ballot(mine);
-      if ((int)(threadIdx.x & 63) == leader) atomicAdd(&counts[ql], (int)__builtin_popcountll(same));
-      if (mine) beat = false;
-      pend &= ~same;
-    }
-  };
-
-  int cur_qt, cur_et;
-  um.at(u0, cur_qt, cur_et);
-  int slot = 0;
-  uint32_t lo = 0xFFFFFFFFu;  // RotatE: min of the sqrt inputs' bits over this unit (see rot_mag)
-  // L1 filter: the code rows actually used in the last stage (the plane is padded to whole
-  // stages; 100 of 104 rows at d = 200: the pad rows' zeros are not swept)
-  // (OP 6: the words of the k values + the entity error-offset row, l1q_quant8)
-  const int kk_last = L1F ? ((((l1.kt + (w8 ? 3 : 1)) >> (w8 ? 2 : 1)) + (w8 ? 2 : 1)) & ~1) - (nkc - 1) * KC
-                          : KC;
-  // the L1 filter's code-width word (L1Q_CODES8 / _CODES16 / _F32: which of the gated sweeps
-  // counts), in flight with the stage
-  const uint32_t fb_flag = L1F ? l1.hdr[1] : 0u;
-  int cur_m = 0;  // grouped: the row tile's member slots (uniform)
-  if constexpr (GRP) cur_m = load_meta_grp(cur_qt);
-  else load_meta(cur_qt, 0);
-  gload();
-  swrite(0);
-  __syncthreads();
-  if (L1F && __builtin_amdgcn_readfirstlane(fb_flag) != (w8 ? L1Q_CODES8 : L1Q_CODES16)) return;  // uniform
-  if (dyn && ch_mask == 0) {  // u0's successor (after the gate: a shut launch claims none); the
-                              // loader reads it at compute stage nkc - 2 of u0, which may be stage 0
-    if (tid == 0) {
-      if constexpr (AFF) sm.s_unit = claim_affine(cur_qt);
-      else sm.s_unit = per_grp + (int)atomicAdd(&l1.wq[grp * L1Q_WQ_STRIDE], 1u);
-    }
-    __syncthreads();
-  }
-
-  constexpr int KKU = 2;  // LDS rows of operands per inner-loop iteration
-  int buf = 0;
-  for (int unit = u0; unit < u1;) {
-    int unit_next = unit + 1;
-    for (int kc = 0; kc < nkc; ++kc) {
-      const bool more = ld_unit < u1;
-      if (more) gload();
-      if constexpr (AFF) {
-        // The affine claim of the unit after ld_unit, on ld_unit's row tile -- here, at the top of
-        // the unit's last stage, with that stage's loads issued: the loader entered ld_unit in the
-        // stage before (its read of s_unit is a barrier back) and leaves it >= 1 barrier on. (In
-        // the epilogue, where the sequential claim sits, a claim whose address moves with the tile
-        // cost the 8-bit instance 8 spilled VGPRs -- 20 B of scratch per lane -- even as one
-        // atomicAdd; here both widths keep 0 B.)
-        if (kc == nkc - 1 && more && threadIdx.x == 0) sm.s_unit = claim_affine(ld_qt);
-      }
-      const int kk_n = (L1F && kc == nkc - 1) ? kk_last : KC;
-#pragma unroll KKU
-      for (int kk = 0; kk < kk_n; ++kk) {
-        float4 a0 = sq[buf][0][kk][tq], a1 = sq[buf][0][kk][16 + tq];
-        float4 x0 = se[buf][0][kk][te], x1 = se[buf][0][kk][16 + te];
-        const float qa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-        const float xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-        if constexpr (OP == 2 && FAST) {
-          // packed f32: every v_pk_* computes two pairs' IEEE-identical results (the scalar
-          // chain's sub, sub, mul, fma, add per half), so one full-rate issue covers two
-          // elements and only the two v_sqrt_f32 stay per-element. Pair (ip, jp) of query rows
-          // (2ip, 2ip+1) and entity columns (2jp, 2jp+1): the straight product takes
-          // (2ip, 2jp) | (2ip+1, 2jp+1), the swapped one (op_sel) (2ip, 2jp+1) | (2ip+1, 2jp).
-          float4 b0 = sq[buf][NPL - 1][kk][tq], b1 = sq[buf][NPL - 1][kk][16 + tq];
-          float4 y0 = se[buf][NPL - 1][kk][te], y1 = se[buf][NPL - 1][kk][16 + te];
-          const f32x2 qa2[4] = {{a0.x, a0.y}, {a0.z, a0.w}, {a1.x, a1.y}, {a1.z, a1.w}};
-          const f32x2 qb2[4] = {{b0.x, b0.y}, {b0.z, b0.w}, {b1.x, b1.y}, {b1.z, b1.w}};
-          const f32x2 xv2[4] = {{x0.x, x0.y}, {x0.z, x0.w}, {x1.x, x1.y}, {x1.z, x1.w}};
-          const f32x2 yv2[4] = {{y0.x, y0.y}, {y0.z, y0.w}, {y1.x, y1.y}, {y1.z, y1.w}};
-#pragma unroll
-          for (int ip = 0; ip < 4; ++ip)
-#pragma unroll
-            for (int jp = 0; jp < 4; ++jp) {  // the straight and swapped chains issued side by side
-              const f32x2 dr0 = qa2[ip] - xv2[jp], dr1 = qa2[ip] - xv2[jp].yx;
-              const f32x2 di0 = qb2[ip] - yv2[jp], di1 = qb2[ip] - yv2[jp].yx;
-              const f32x2 p0 = dr0 * dr0, p1 = dr1 * dr1;
-              const f32x2 v0 = __builtin_elementwise_fma(di0, di0, p0), v1 = __builtin_elementwise_fma(di1, di1, p1);
-              const f32x2 m0 = {__builtin_amdgcn_sqrtf(v0.x), __builtin_amdgcn_sqrtf(v0.y)};
-              const f32x2 m1 = {__builtin_amdgcn_sqrtf(v1.x), __builtin_amdgcn_sqrtf(v1.y)};
-              accp[ip][2 * jp] = accp[ip][2 * jp] + m0;
-              accp[ip][2 * jp + 1] = accp[ip][2 * jp + 1] + m1;
-            }
-        } else if constexpr (OP == 2) {
-          float4 b0 = sq[buf][NPL - 1][kk][tq], b1 = sq[buf][NPL - 1][kk][16 + tq];
-          float4 y0 = se[buf][NPL - 1][kk][te], y1 = se[buf][NPL - 1][kk][16 + te];
-          const float qb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-          const float yv[8] = {y0.x, y0.y, y0.z, y0.w, y1.x, y1.y, y1.z, y1.w};
-          // software pipeline across rows: row i + 1's v and v_rsq_f32 are issued before row i's
-          // uses, so every rsq result is consumed a whole row later (C4 83.6 -> 81.2 ms; the 16
-          // extra VGPRs cost a few dwords of scratch at 168)
-          float v[8], y[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float dr = qa[0] - xv[j], di = qb[0] - yv[j];
-            v[j] = __builtin_fmaf(di, di, dr * dr);
-            y[j] = __builtin_amdgcn_rsqf(v[j]);
-          }
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            float vn[8], yn[8];
-            if (i + 1 < 8) {
-#pragma unroll
-              for (int j = 0; j < 8; ++j) {
-                const float dr = qa[i + 1] - xv[j], di = qb[i + 1] - yv[j];
-                vn[j] = __builtin_fmaf(di, di, dr * dr);
-                yn[j] = __builtin_amdgcn_rsqf(vn[j]);
-              }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-              lo = min(min(lo, __float_as_uint(v[j])), __float_as_uint(v[j + 1]));  // v >= 0: bit order; one v_min3
-              acc[i][j] = acc[i][j] + rot_mag(v[j], y[j]);
-              acc[i][j + 1] = acc[i][j + 1] + rot_mag(v[j + 1], y[j + 1]);
-            }
-            if (i + 1 < 8) {
-#pragma unroll
-              for (int j = 0; j < 8; ++j) { v[j] = vn[j]; y[j] = yn[j]; }
-            }
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = op_step<OP>(acc[i][j], qa[i], 0.0f, xv[j], 0.0f);
-        }
-      }
-      if (kc == nkc - 1) {  // unit finished: rank epilogue
-        const int64_t q0 = (int64_t)cur_qt * TQ;
-        const int64_t ebase = (int64_t)cur_et * TE;
-        // type constraints: this thread's 8 type bits of query row ql (bit j = column j), from the
-        // unit's staged words
-        auto tbits = [&](int ql) -> uint32_t {
-          const uint2 w = *reinterpret_cast<const uint2*>(&sm.s_tb[TC ? ep_par : 0][TC ? ql : 0][(te >> 3) * 2]);
-          const int sh = (te & 7) * 4;
-          return ((w.x >> sh) & 15u) | (((w.y >> sh) & 15u) << 4);
-        };
-        if constexpr (GRP) {
-          // Grouped: the tile's integer scores are ranked once per member slot -- the whole-tile
-          // pass below (four VALU per pair) against that slot's thresholds; the last entity tile
-          // adds its column test. No truth test in either: no pair below t_sure is a truth
-          // (S_int < t_sure proves S < th), and the rescoring skips a member's own truth. Per slot
-          // the thread's 8 row counts (<= 8 each) are packed four to a dword, summed over the 16
-          // te lanes of the row (one DPP row: 16 x 8 <= 128 fits a byte; 8 cross-lane adds), and
-          // lane te < 8 adds row te's sum into the slot's LDS accumulator -- one owner per (slot,
-          // row) in the workgroup, so a plain read-modify-write (the flush to counts[], shared with
-          // the other workgroups, is one global atomic per non-zero (slot, row) and row tile).
-          const bool whole = ebase + TE <= n_ent;  // uniform
-          int2* wl = sm.s_pairs[tid >> 6];
-          const int lane = tid & 63;
-          for (int s = 0; s < cur_m; ++s) {  // uniform bound
-            uint32_t unc[2] = {0u, 0u}, pk[2] = {0u, 0u};
-            if (whole) {
-#pragma unroll
-              for (int i = 0; i < 8; ++i) {
-                const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-                const uint32_t t_sure = sm.g_ts[GRP ? s : 0][ql], t_span = sm.g_tw[GRP ? s : 0][ql];
-                int c = 0;
-                uint32_t u = unc[i >> 2];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                  const uint32_t si = __float_as_uint(acc[i][j]);
-                  const uint32_t d = si - t_sure;
-                  c += si < t_sure;
-                  u = u + u + (uint32_t)(d < t_span);
-                }
-                unc[i >> 2] = u;
-                pk[i >> 2] |= (uint32_t)c << (8 * (i & 3));
-              }
-            } else {
-#pragma unroll
-              for (int i = 0; i < 8; ++i) {
-                const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-                const uint32_t t_sure = sm.g_ts[GRP ? s : 0][ql], t_span = sm.g_tw[GRP ? s : 0][ql];
-                int c = 0;
-                uint32_t u = unc[i >> 2];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                  const int e = (int)ebase + ((j < 4) ? te * 4 + j : 64 + te * 4 + (j - 4));
-                  const bool valid = e < n_ent;
-                  const uint32_t si = __float_as_uint(acc[i][j]);
-                  c += (si < t_sure) & valid;
-                  u = u + u + (uint32_t)((si - t_sure < t_span) & valid);
-                }
-                unc[i >> 2] = u;
-                pk[i >> 2] |= (uint32_t)c << (8 * (i & 3));
-              }
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {  // sum over the row's 16 lanes: xor 1, xor 2, half mirror, mirror
-              uint32_t v = pk[h];
-              v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
-              v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);
-              v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);
-              v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);
-              pk[h] = v;
-            }
-            if (te < 8) {
-              const uint32_t cnt = ((te < 4 ? pk[0] : pk[1]) >> (8 * (te & 3))) & 255u;
-              const int ql = (te < 4) ? tq * 4 + te : 64 + tq * 4 + (te - 4);
-              if (cnt) sm.g_acc[GRP ? s : 0][ql] += cnt;
-            }
-            for (;;) {  // uniform: one undecided pair per lane and round into the wave's list
-              const bool has = (unc[0] | unc[1]) != 0u;
-              const uint64_t bal = __ballot(has);
-              if (bal == 0) break;
-              if (has) {
-                const int h = unc[0] ? 0 : 1;
-                const int p = __builtin_clz(unc[h]);  // pair p = (i & 3) * 8 + j sits at bit 31 - p
-                unc[h] &= ~(0x80000000u >> p);
-                const int i = h * 4 + (p >> 3), j = p & 7;
-                const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-                const int e = (int)ebase + ((j < 4) ? te * 4 + j : 64 + te * 4 + (j - 4));
-                // list_n < 64 at the top of every round and a round appends <= 64: pos < 128
-                const int pos = list_n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-                                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                wl[pos] = make_int2(sm.g_mq[GRP ? s : 0][ql], e);
-              }
-              list_n += __builtin_popcountll(bal);
-              if (list_n >= 64) {  // a full batch
-                list_n -= 64;
-                rescore(wl[list_n + lane], true);
-              }
-            }
-          }
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = 0.0f;
-        } else if constexpr (FAST) {
-          if constexpr (OP == 2) {  // unpack the pair layout (register renames) and restart it
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-              for (int j = 0; j < 8; ++j) {
-                const f32x2 p = accp[i >> 1][(j & ~1) + ((i ^ j) & 1)];
-                acc[i][j] = (i & 1) ? p.y : p.x;
-              }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-              for (int j = 0; j < 8; ++j) accp[i][j] = f32x2{0.0f, 0.0f};
-          }
-          // undecided pairs: pair (i, j) is bit 31 - ((i & 3) * 8 + j) of unc[i >> 2] (rows 0-3 /
-          // 4-7; the whole-tile epilogue shifts the bits in, pair by pair)
-          uint32_t unc[2] = {0u, 0u};
-          bool whole = false;
-          if constexpr (L1F && PK == 0 && !TC) {
-            // L1 filter, a whole entity tile (every tile but the last, uniform), ONE pass: per
-            // pair d = S_int - t_sure (its borrow, S_int < t_sure, carry-added to the count) and
-            // the undecided band d < t_out - t_sure carry-shifted into the pair's bit: four VALU
-            // per pair (v_sub_co, v_addc, v_cmp, v_addc). The count needs no truth test: the
-            // truth's S is th itself, which no pair below t_sure reaches (S_int < t_sure proves
-            // S < th). The truth's own pair is in the band; the rescoring list skips it. (A first
-            // pass with a wave-wide "any" ballot and the per-pair bits rebuilt when it was set
-            // paid ~420 more VALU per wave and unit: at C2 nearly every wave holds an undecided
-            // pair in every unit -- a quarter of them hold a truth.)
-            if (ebase + TE <= n_ent) {
-              whole = true;
-#pragma unroll
-              for (int i = 0; i < 8; ++i) {
-                const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-                const uint32_t t_sure = sm.s_ts[slot][ql], t_span = sm.s_tw[slot][ql];
-                // type constraints: the row's 8 type bits (a pair below t_sure is never the truth)
-                const uint32_t tb = TC ? tbits(ql) : 0u;
-                int c = 0, cc = 0;
-                uint32_t u = unc[i >> 2];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                  const uint32_t si = __float_as_uint(acc[i][j]);
-                  const uint32_t d = si - t_sure;
-                  const bool sure = si < t_sure;
-                  c += sure;
-                  if constexpr (TC) cc += sure & ((tb >> j) & 1u);
-                  u = u + u + (uint32_t)(d < t_span);
-                }
-                unc[i >> 2] = u;
-                s_cnt[0][i][tid] += c;
-                if constexpr (TC) s_cnt[TC ? 1 : 0][i][tid] += cc;
-              }
-            }
-          }
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            if (whole) break;
-            const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-            const float th = s_thr[slot][ql];
-            const int32_t tr = s_true[slot][ql];
-            int c = 0, cc = 0;
-            const uint32_t tb = TC ? tbits(ql) : 0u;
-            if constexpr (L1F && PK == 0) {
-              // prediction = the score: the integer thresholds of load_meta
-              const uint32_t t_sure = sm.s_ts[slot][ql], t_span = sm.s_tw[slot][ql];
-#pragma unroll
-              for (int j = 0; j < 8; ++j) {
-                const int e = (int)ebase + ((j < 4) ? te * 4 + j : 64 + te * 4 + (j - 4));
-                const bool valid = (e + e_base != tr) & (e < n_ent);
-                const uint32_t si = __float_as_uint(acc[i][j]);
-                const bool sure = si < t_sure;
-                const bool better = sure & valid;
-                c += better;
-                if constexpr (TC) cc += better & ((tb >> j) & 1u);
-                unc[i >> 2] |= (uint32_t)((si - t_sure < t_span) & valid) << (31 - ((i & 3) * 8 + j));
-              }
-              s_cnt[0][i][tid] += c;
-              if constexpr (TC) s_cnt[TC ? 1 : 0][i][tid] += cc;
-              continue;
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const int e = (int)ebase + ((j < 4) ? te * 4 + j : 64 + te * 4 + (j - 4));
-              const bool valid = (e + e_base != tr) & (e < n_ent);
-              float a, bnd;
-              if constexpr (L1F) {
-                a = (float)__float_as_uint(acc[i][j]) * l1d;
-                bnd = __builtin_fmaf(a, l1f, l1c);
-              } else {
-                a = acc[i][j];
-                bnd = rot_bound(a, kp);
-              }
-              const float p1 = pred(a - bnd), p2 = pred(a + bnd);
-              const bool fin = a < INFINITY;  // false for inf and NaN: rescored
-              const bool sure = fin & (fmaxf(p1, p2) < th);
-              const bool out = (fin & (fminf(p1, p2) >= th)) | (th != th);
-              const bool better = sure & valid;
-              c += better;
-              if constexpr (TC) cc += better & ((tb >> j) & 1u);
-              unc[i >> 2] |= (uint32_t)(!sure & !out & valid) << (31 - ((i & 3) * 8 + j));
-            }
-            s_cnt[0][i][tid] += c;
-            if constexpr (TC) s_cnt[TC ? 1 : 0][i][tid] += cc;
-          }
-          if constexpr (LIST) {
-            int2* wl = sm.s_pairs[tid >> 6];
-            const int lane = tid & 63;
-            for (;;) {  // uniform: one undecided pair per lane and round into the list
-              const bool has = (unc[0] | unc[1]) != 0u;
-              if (__ballot(has) == 0) break;
-              bool keep = false;
-              int2 pr = make_int2(0, 0);
-              if (has) {
-                const int h = unc[0] ? 0 : 1;
-                const int p = __builtin_clz(unc[h]);  // pair p = (i & 3) * 8 + j sits at bit 31 - p
-                unc[h] &= ~(0x80000000u >> p);
-                const int i = h * 4 + (p >> 3), j = p & 7;
-                const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-                const int e = (int)ebase + ((j < 4) ? te * 4 + j : 64 + te * 4 + (j - 4));
-                keep = (int)(e + e_base) != s_true[slot][ql];  // the truth's own pair is not rescored
-                pr = make_int2((int)(q0 + ql), e);
-              }
-              const uint64_t bal = __ballot(keep);
-              if (keep) {
-                // list_n < 64 at the top of every round and a round appends <= 64: pos < 128
-                const int pos = list_n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-                                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                wl[pos] = pr;
-              }
-              const int nb = __builtin_popcountll(bal);
-              list_n += nb;
-              n_listed += (uint32_t)nb;
-              if (list_n >= 64) {  // a full batch (the list holds < 128: < 64 before this round)
-                list_n -= 64;
-                rescore(wl[list_n + lane], true);
-              }
-            }
-          }
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            uint32_t m = LIST ? 0u : unc[h];  // (the L1 filter's pairs went to the wave's list)
-            while (m) {  // rare: exact rescoring, one pair at a time
-              const int p = __builtin_clz(m);
-              m &= ~(0x80000000u >> p);
-              const int i = h * 4 + (p >> 3), j = p & 7;
-              const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-              const int e = (int)ebase + ((j < 4) ? te * 4 + j : 64 + te * 4 + (j - 4));
-              float sx;
-              if constexpr (L1F) {
-                ++n_listed;
-                sx = l1_exact_rows(l1.q_rows + (q0 + ql) * (int64_t)l1.kt, l1.ent_rows + (int64_t)(e + e_base) * l1.kt,
-                                   l1.kt);
-              } else {
-                sx = rot_exact(q_km, q_pad, q0 + ql, ent_km, e_pad, e, kp);
-              }
-              const float v = pred(sx);
-              if (v < s_thr[slot][ql]) {
-                s_cnt[0][i][tid] += 1;
-                if constexpr (TC) {
-                  const uint32_t* tm = s_mode[slot][ql] == MMRE_HEAD_BATCH ? type_head : type_tail;
-                  s_cnt[TC ? 1 : 0][i][tid] += type_bit(tm, type_words, s_rel[slot][ql], e + e_base) ? 1 : 0;
-                }
-              }
-            }
-          }
-          // the accumulators restart here, after the rescoring: dead while it runs, so its row
-          // loads have the registers
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = 0.0f;
-        } else {
-        if constexpr (OP == 2) {
-          bool bad = lo < __float_as_uint(kRotMin);  // v = 0 or v < 2^-96
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bad |= acc[i][j] != acc[i][j];  // v = inf (or a NaN input)
-          if (__ballot(bad)) {  // rare: redo this wave's tiles with the IEEE sqrtf
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-              for (int j = 0; j < 8; ++j) acc[i][j] = 0.0f;
-            for (int k = 0; k < kp; ++k) {
-              float qa[8], qb[8], xv[8], yv[8];
-#pragma unroll
-              for (int i = 0; i < 8; ++i) {
-                const int64_t ql = q0 + ((i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4));
-                const int64_t ec = ebase + ((i < 4) ? te * 4 + i : 64 + te * 4 + (i - 4));
-                qa[i] = q_km[(int64_t)k * q_pad + ql];
-                qb[i] = q_km[(int64_t)(kp + k) * q_pad + ql];
-                xv[i] = ent_km[(int64_t)k * e_pad + ec];
-                yv[i] = ent_km[(int64_t)(kp + k) * e_pad + ec];
-              }
-#pragma unroll
-              for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[i][j] = op_step<2>(acc[i][j], qa[i], qb[i], xv[j], yv[j]);
-            }
-          }
-          lo = 0xFFFFFFFFu;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-          const float th = s_thr[slot][ql];
-          const int32_t tr = s_true[slot][ql];
-          int c = 0, cc = 0;
-          const uint32_t tb = TC ? tbits(ql) : 0u;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            // 32-bit ids (int32 by check_link_args); bitwise &: no per-pair branch
-            const int e = (int)ebase + ((j < 4) ? te * 4 + j : 64 + te * 4 + (j - 4));
-            const float v = pred(op_final<OP>(acc[i][j]));
-            const bool better = (v < th) & (e + e_base != tr) & (e < n_ent);
-            c += better;
-            if constexpr (TC) cc += better & ((tb >> j) & 1u);
-            if constexpr (STORE) {
-              if (q0 + ql < n_query && e < n_ent) scores[(q0 + ql) * n_ent + e] = v;
-            }
-            acc[i][j] = 0.0f;
-          }
-          s_cnt[0][i][tid] += c;
-          if constexpr (TC) s_cnt[TC ? 1 : 0][i][tid] += cc;
-        }
-        }  // !FAST
-        if (dyn) unit_next = ld_unit;  // the loader entered it at the top of the stage before
-        const bool last = unit_next >= u1;
-        int next_qt = cur_qt, next_et = cur_et;
-        if (!last) um.at(unit_next, next_qt, next_et);
-        // (TC: 16-bit counters, up to 8 per unit, so 8,191 units -- flush every unit where the units
-        // of one query tile that an XCD group owns, all of which one workgroup may sweep back to
-        // back, could exceed them: um.m = n_et / n_groups whole tiles and, when the leftover units
-        // that follow start in that query tile, up to 7 more (UnitMap); n_groups is 1 for a grid
-        // that is no multiple of 8)
-        if constexpr (GRP) {
-          if (last || next_qt != cur_qt) {  // uniform: flush this row tile's member counts
-            __syncthreads();  // every wave's adds of this unit are in, and its threshold reads done
-            const int tid = vgpr_opaque(threadIdx.x);
-            for (int idx = tid; idx < cur_m * TQ; idx += NT) {
-              const uint32_t c = (&sm.g_acc[0][0])[idx];
-              if (c) {
-                const int q = (&sm.g_mq[0][0])[idx];
-                if (q >= 0) atomicAdd(&counts[q], (int)c);
-                (&sm.g_acc[0][0])[idx] = 0u;
-              }
-            }
-            if (!last) cur_m = load_meta_grp(next_qt);  // visible after the stage's barrier below
-          }
-        } else
-        if (last || next_qt != cur_qt || (TC && um.m > 8184)) {  // uniform: flush this query tile's counts
-          const int tid = vgpr_opaque(threadIdx.x);  // (see load_meta)
-          const int tq = tid >> 4, te = tid & 15;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            int c = s_cnt[0][i][tid], cc = TC ? s_cnt[TC ? 1 : 0][i][tid] : 0;
-#pragma unroll
-            for (int sh = 1; sh < 16; sh <<= 1) {
-              c += __shfl_xor(c, sh);
-              if constexpr (TC) cc += __shfl_xor(cc, sh);
-            }
-            const int ql = (i < 4) ? tq * 4 + i : 64 + tq * 4 + (i - 4);
-            const int64_t q = q0 + ql;
-            const bool vq = q < n_query;
-            if (te == 0 && vq) {  // raw columns only: k_counts_finalize adds them to the filtered ones
-              if (c) atomicAdd(&counts[q], c);
-              if constexpr (TC) {
-                if (cc) atomicAdd(&counts[2 * n_query + q], cc);
-              }
-            }
-            s_cnt[0][i][tid] = 0;
-            if constexpr (TC) s_cnt[TC ? 1 : 0][i][tid] = 0;
-          }
-          if (!last) {
-            slot ^= 1;
-            load_meta(next_qt, slot);
-          }
-        }
-        // the loader entered the last unit of its chunk one stage ago: the next chunk, claimed for
-        // the loader's exit from it >= 1 barrier later (the previous claim was read long before);
-        // here, after the accumulators were reset, where the claim costs no registers
-        // (the affine claim: at the top of this stage)
-        if (dyn && !AFF && !last && ((unit_next + 1) & ch_mask) == 0 && threadIdx.x == 0)
-          sm.s_unit = (per_grp + (int)atomicAdd(&l1.wq[grp * L1Q_WQ_STRIDE], 1u)) << ch_log2;
-        if constexpr (TC) ep_par ^= 1;  // the next unit's staged type words
-        cur_qt = next_qt;
-        cur_et = next_et;
-      }
-      if (more) swrite(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
-    }
-    unit = unit_next;
-  }
-  if constexpr (L1F) {  // the filter's undecided pairs: one atomic per workgroup, 16 slots
-    if constexpr (LIST) {
-      if (list_n > 0) rescore(sm.s_pairs[tid >> 6][tid & 63], (tid & 63) < list_n);  // the last partial batch
-      if ((tid & 63) == 0) sm.s_unc[tid >> 6] = n_listed;
-    } else {
-      if (n_listed) atomicAdd(&sm.s_unc[tid >> 6], n_listed);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      uint32_t t = 0;
-#pragma unroll
-      for (int w = 0; w < NT / 64; ++w) t += sm.s_unc[w];
-      // 32-bit counter in the slot's low word (the stats kernel reads only that word)
-      if (t) atomicAdd(reinterpret_cast<uint32_t*>(l1.undecided + (blockIdx.x & (L1Q_SLOTS - 1)) * L1Q_SLOT_STRIDE), t);
-    }
-  }
-}
-
-template <int OP, bool TC, bool STORE, int PK, int DYNC = 0, int GS = 0>
-__global__ __launch_bounds__(NT, (OP == 2) ? 3 : 4) void k_sweep_valu(
-    const float* __restrict__ ent_km, int64_t e_pad, int64_t n_ent, const float* __restrict__ q_km,
-    int64_t q_pad, int64_t n_query, int kp, int n_et, int e_base, int n_groups, int pred_kind, float margin,
-    const float* __restrict__ thr, const int32_t* __restrict__ qtrue, const int64_t* __restrict__ qr,
-    const int8_t* __restrict__ qmode, const uint32_t* __restrict__ type_head,
-    const uint32_t* __restrict__ type_tail, int64_t type_words, int32_t* __restrict__ counts,
-    float* __restrict__ scores, L1Q l1) {
-  constexpr int NPL = (OP == 2) ? 2 : 1;
-  __shared__ ValuSmem<NPL, TC, (OP == 5 || OP == 6), GS> sm;
-  // the L1 filter's fallback (k_l1q_quant decided that the codes are too coarse for these
-  // planes -- one outlier value sets the code step for everything): the filter launch does
-  // nothing (sweep_valu_body tests the flag once its first stage is loaded, so the flag's load
-  // latency hides under the stage's) and the exact f32 sweep launched after it, gated on the
-  // same flag, counts. A separate launch, not a branch here: inlining the f32 body beside the
-  // filter's grew the kernel by half and its register spills (18 -> 23)
-  if (l1.gate != nullptr) {
-    const uint32_t want = OP == 6 ? L1Q_CODES8 : OP == 5 ? L1Q_CODES16 : L1Q_F32;
-    if (__builtin_amdgcn_readfirstlane(*l1.gate) != want) {
-      if (l1.fin_counts != nullptr) {  // shut (the codes counted): this workgroup's slice of the finalize
-        for (int64_t q = (int64_t)blockIdx.x * NT + threadIdx.x; q < l1.fin_n; q += (int64_t)gridDim.x * NT) {
-          l1.fin_counts[l1.fin_n + q] += l1.fin_counts[q];
-          if constexpr (TC) l1.fin_counts[3 * l1.fin_n + q] += l1.fin_counts[2 * l1.fin_n + q];
-        }
-      }
-      return;
-    }
-  }
-  sweep_valu_body<OP, TC, STORE, PK, NPL, DYNC, GS>(sm, ent_km, e_pad, n_ent, q_km, q_pad, n_query, kp, n_et, e_base,
-                                                    n_groups, pred_kind, margin, thr, qtrue, qr, qmode, type_head, type_tail,
-                                                    type_words, counts, scores, l1);
-  if (l1.gate != nullptr && l1.fin_counts != nullptr) {
-    // open (the rare f32 fallback): the finalize after every workgroup's counts, by the last
-    // workgroup (each wave's count atomics drained, then ONE ticket add per workgroup)
-    __shared__ uint32_t s_last;
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0)
-      s_last = __hip_atomic_fetch_add(l1.fin_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    __syncthreads();
-    if (s_last) {
-      for (int64_t q = threadIdx.x; q < l1.fin_n; q += NT) {
-        atomicAdd(&l1.fin_counts[l1.fin_n + q],
-                  __hip_atomic_load(&l1.fin_counts[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if constexpr (TC)
-          atomicAdd(&l1.fin_counts[3 * l1.fin_n + q],
-                    __hip_atomic_load(&l1.fin_counts[2 * l1.fin_n + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      }
-      if (threadIdx.x == 0) *l1.fin_ticket = 0u;
-    }
-  }
-}
 
 // filtered columns += raw columns (after the sweep): counts[1] = counts[0] + (minus the listed
 // entities that beat the truth, written by the truth pass), likewise counts[3] from counts[2]
@@ -3585,13 +2284,15 @@ __global__ void k_bf3_stats(const uint32_t* __restrict__ hdr, unsigned long long
 }
 
 // ---------------------------------------------------------------- launch ---
-// An entry point fills one SweepCall, each kernel family has one launcher that takes it, run-time
-// choices reach the template arguments through with_op / with_bool(s) / with_chunk, grid rules are functions.
+// An entry point fills one SweepCall (link_common.h), each kernel family has one launcher that takes
+// it, run-time choices reach the template arguments through with_op / with_bool(s) (dispatch.h),
+// grid rules are functions.
 
 // Resident workgroups of a persistent sweep: the occupancy API's blocks per CU (capped at 4,
 // the VGPR-limited residency of a 256-thread group at <= 128 VGPRs) x the device's CUs. Queried
-// once per kernel and device: the fused evaluation asks on every call.
-static int resident_groups(const void* kernel, int threads) {
+// once per kernel and device: the fused evaluation asks on every call. (The one cache of every
+// sweep, link_valu.hip's and TransH's included: link_common.h declares it.)
+int resident_groups(const void* kernel, int threads) {
   static std::mutex mu;
   static std::map<std::tuple<const void*, int, int>, int> cache;
   int dev = 0;
@@ -3606,62 +2307,6 @@ static int resident_groups(const void* kernel, int threads) {
   }
   return it->second;
 }
-
-template <int V>
-using int_c = std::integral_constant<int, V>;
-template <class F>
-static int with_bool(bool b, F&& f) {
-  return b ? f(std::true_type{}) : f(std::false_type{});
-}
-template <class F>  // f(a_, b_, c_)
-static int with_bools(bool a, bool b, bool c, F&& f) {
-  return with_bool(a, [&](auto a_) {
-    return with_bool(b, [&](auto b_) { return with_bool(c, [&](auto c_) { return f(a_, b_, c_); }); });
-  });
-}
-// f(int_c<DYNC>) for the units per claim, among the instances the caller has (MASK: their sum)
-template <int MASK, class F>
-static void with_chunk(int chunk, F&& f) {
-  if ((MASK & 8) && chunk == 8) f(int_c<MASK & 8>{});
-  else if ((MASK & 4) && chunk == 4) f(int_c<MASK & 4>{});
-  else if ((MASK & 2) && chunk == 2) f(int_c<MASK & 2>{});
-  else if ((MASK & 1) && chunk == 1) f(int_c<MASK & 1>{});
-  else f(int_c<0>{});
-}
-// f(int_c<OP>) for the score operator op = op_of_model(model), 0 .. 4
-template <int OP = 0, class F>
-static int with_op(int op, F&& f) {
-  if constexpr (OP < 4) {
-    if (op != OP) return with_op<OP + 1>(op, f);
-  }
-  return f(int_c<OP>{});
-}
-
-// What every sweep launcher needs. An entry point fills the first part from its ABI arguments
-// (ent: the table's k-major planes), check_link_args validates it, sweep_slice() the rest.
-struct SweepCall {
-  hipStream_t st;
-  const float* ent;
-  int64_t e_pad;
-  const float* q;
-  int64_t q_pad, n_query;
-  int pred_kind;
-  float margin;
-  const float* truth;
-  const int32_t* q_true;
-  const int64_t* qr;
-  const int8_t* qmode;
-  const uint32_t *type_head, *type_tail;  // both or neither
-  int32_t* counts;
-  float* scores;
-  // sweep_slice: ent now at the first column of the slice [e_base, e_base + n_slice) -- e_cols
-  // columns in n_et whole tiles; kp K rows of the planes (ktot for the MFMA sweeps); tw type words
-  int kp, n_et, e_base;
-  int64_t n_slice, e_cols, tw;
-  bool tc() const { return type_head != nullptr; }
-  bool store() const { return scores != nullptr; }
-  int64_t q_tiles() const { return q_pad / TQ; }
-};
 
 // The sweep over entities [e_begin, e_end) of the table (e_begin a multiple of TE): the kernels
 // see the slice (pointer offset by e_begin columns, row stride e_pad, n_slice ids) and add
@@ -3696,27 +2341,6 @@ static int check_link_args(int model, const SweepCall& C, int64_t n_ent) {
   return MMRE_OK;
 }
 
-// Work units (query tile x entity tile) of an XCD-grouped sweep: the busiest group's (UnitMap) x 8.
-static int64_t sweep_units(int64_t q_tiles, int n_et) {
-  return n_et >= 8 ? 8 * q_tiles * ((n_et + 7) / 8) : q_tiles * n_et;
-}
-static int xcd_groups(int g, int n_et) { return (g % 8 == 0 && n_et >= 8) ? 8 : 1; }  // of a grid of g workgroups
-// MMRE_SWEEP_GRID (experiments): a number = that many persistent workgroups; "tiles" = the
-// caller's tile grid, where it has one (the VALU sweep)
-static int grid_override(int g, int tiles = 0) {
-  static const char* env = getenv("MMRE_SWEEP_GRID");
-  if (env && env[0] == 't' && tiles > 0) return tiles;
-  return (env && env[0] >= '1' && env[0] <= '9') ? atoi(env) : g;
-}
-// Units per claim of a dynamically scheduled sweep: 4 from 16 units per workgroup on, else 1
-// (measurements: launch_valu_grp, sweep_valu_body). MMRE_SWEEP_CHUNK (A/B) forces 1, 4 or -- where
-// the launcher has that instance (allow2) -- 2.
-static int sweep_chunk(int64_t per_wg, bool allow2) {
-  static const char* env = getenv("MMRE_SWEEP_CHUNK");
-  if (!env) return per_wg >= 16 ? 4 : 1;
-  const int v = atoi(env);
-  return v >= 4 ? 4 : (allow2 && v >= 2) ? 2 : 1;
-}
 // Units entity-tile-major inside each XCD group when the entity planes outgrow the caches
 // (> 64 MB; the 256 MB MALL also holds the query planes): a workgroup's consecutive units then
 // share its entity tile (L2-resident) and sweep the query tiles, which stay MALL-resident, so
@@ -3728,122 +2352,9 @@ static int mfma_emajor(int64_t e_pad, int ktot) {
   return env ? atoi(env) : ((double)e_pad * ktot * 4.0 > 64.0 * (1 << 20) ? 1 : 0);
 }
 
-static int launch_finalize(hipStream_t st, int32_t* counts, int64_t n_query, bool tc) {
+int launch_finalize(hipStream_t st, int32_t* counts, int64_t n_query, bool tc) {
   hipLaunchKernelGGL(k_counts_finalize, dim3((unsigned)((n_query + 255) / 256)), dim3(256), 0, st, counts, n_query,
                      tc ? 1 : 0);
-  MMRE_CHECK_LAUNCH();
-  return MMRE_OK;
-}
-
-struct ValuGrid { int g, ng, chunk; };  // workgroups, XCD groups, units per claim (0: static ranges)
-// (k_static / k_dyn: the instance with static ranges and the dynamically scheduled one, if any)
-static ValuGrid valu_grid(const SweepCall& C, const L1Q& l1, const void* k_static, const void* k_dyn) {
-  // 16 workgroups per resident slot: short per-workgroup ranges let the dispatcher balance
-  // CUs that run at different speeds (C2 on MI355X: 1,024 groups 4.0 ms, 8,192 3.43 ms,
-  // 16,384 3.30 ms, 30,528 (one unit each) 3.36 ms).
-  int g = 16 * resident_groups(k_static, NT);
-  // a gated launch (the L1 filter's f32 fallback, l1.gate) runs 4 workgroups per resident
-  // slot: when the gate is shut -- every time but the rare fallback -- its workgroups only
-  // read the flag and leave, and a 16x grid of such workgroups cost 77 us per evaluation at
-  // C2; one per slot (1x) made the open-gate sweep 15% slower than the plain f32 sweep
-  static const char* fbdiv = getenv("MMRE_L1_FB_DIV");
-  if (l1.gate != nullptr) {
-    const int div = fbdiv ? atoi(fbdiv) : 4;
-    g /= div > 1 ? div : 1;
-  }
-  // Dynamic scheduling (l1.wq, the TransE L1 filter sweeps): one persistent workgroup per
-  // resident slot, units from the XCD groups' work counters -- the shut gated launch too (its
-  // workgroups only read the gate).
-  const bool dyn = k_dyn != nullptr && l1.wq != nullptr && C.kp / KC >= 2;
-  const int64_t q_tiles = C.q_tiles();
-  int chunk = 0;
-  if (dyn) {
-    g = resident_groups(k_dyn, NT);
-    chunk = sweep_chunk(q_tiles * C.n_et / (g > 0 ? g : 1), false);
-  }
-  // Small sweeps (a rank's share under relation sharding): no more workgroups than the
-  // busiest XCD group has units, so every workgroup gets at most one unit and no empty
-  // workgroups are dispatched (C2 at 8-way: 4,380 sweeps 0.52 -> 0.47 ms; 4-way 0.89 -> 0.85).
-  const int64_t units = sweep_units(q_tiles, C.n_et);
-  if (units < g) g = (int)(units > 0 ? units : 1);
-  // Dynamic scheduling of a small share: as many workgroups per XCD group as make its units an
-  // (almost) whole number of rounds -- the same rounds as the full grid, no nearly empty last
-  // round (an 8-way C2 share: 527 units per group over 128 workgroups = 4.1 rounds, the fifth
-  // run by 15 of them; over 106 workgroups, 5 rounds). Measured no faster on 8-way C2 shares
-  // (ranks 1 / 3 / 7: 0.190 / 0.203 / 0.199 against 0.185 / 0.193 / 0.196 ms, profiles/r6): off
-  // unless MMRE_SWEEP_BALANCE=1 (A/B).
-  static const char* bal_env = getenv("MMRE_SWEEP_BALANCE");
-  if (dyn && g % 8 == 0 && C.n_et >= 8 && bal_env && bal_env[0] == '1') {
-    const int64_t per_group = (q_tiles * C.n_et + 7) / 8;  // UnitMap: every group within +-1 of this
-    const int64_t slots = g / 8;
-    const int64_t rounds = (per_group + slots - 1) / slots;
-    if (rounds <= 16) g = 8 * (int)((per_group + rounds - 1) / rounds);
-  }
-  g = grid_override(g, 8 * (int)q_tiles);  // "tiles": one workgroup per (query tile, 1/8 of the entity tiles)
-  return {g, xcd_groups(g, C.n_et), chunk};
-}
-
-// The VALU sweep of operator OP (0 - 2 the f32 sweeps, 5 / 6 the integer filter's count-only ones,
-// the only ones with DYNC instances). The model's usual prediction kind is compiled into the
-// epilogue (PK = fast) of the plain sweep (C2 3.27 -> 3.23 ms) and of the integer filter's sweeps,
-// type masks or not (integer thresholds: prediction = the score); all else decodes it (PK = -1).
-template <int OP>
-static int launch_valu(const SweepCall& C, const L1Q& l1 = {}, bool finalize = true) {
-  constexpr int fast = (OP == 2) ? 3 : 0;  // RotatE -(m - s), TransE s
-  constexpr bool COUNT_ONLY = OP == 5 || OP == 6;
-  if (COUNT_ONLY && C.store()) return MMRE_ERR_ARG;
-  const bool fast_pk = C.pred_kind == fast && (COUNT_ONLY || (!C.tc() && !C.store()));
-  with_bools(C.tc(), C.store(), fast_pk, [&](auto tc_, auto st_, auto fast_) {
-    constexpr bool TC = decltype(tc_)::value, ST = decltype(st_)::value;
-    constexpr int PK = decltype(fast_)::value ? fast : -1;
-    if constexpr (!(COUNT_ONLY && ST) && !(PK == fast && !COUNT_ONLY && (TC || ST))) {  // the instances there are
-      const void* k_dyn = COUNT_ONLY ? (const void*)k_sweep_valu<OP, TC, ST, PK, COUNT_ONLY ? 4 : 0> : nullptr;
-      const ValuGrid G = valu_grid(C, l1, (const void*)k_sweep_valu<OP, TC, ST, PK>, k_dyn);
-      with_chunk<COUNT_ONLY ? 4 + 1 : 0>(G.chunk, [&](auto dync_) {
-        hipLaunchKernelGGL((k_sweep_valu<OP, TC, ST, PK, decltype(dync_)::value>), dim3((unsigned)G.g), dim3(NT), 0,
-                           C.st, C.ent, C.e_pad, C.n_slice, C.q, C.q_pad, C.n_query, C.kp, C.n_et, C.e_base, G.ng,
-                           C.pred_kind, C.margin, C.truth, C.q_true, C.qr, C.qmode, C.type_head, C.type_tail, C.tw,
-                           C.counts, C.scores, l1);
-      });
-    }
-    return MMRE_OK;
-  });
-  MMRE_CHECK_LAUNCH();
-  return finalize ? launch_finalize(C.st, C.counts, C.n_query, C.tc()) : MMRE_OK;
-}
-
-// The grouped integer-filter sweep of the fused evaluation (k_sweep_valu<.., GS = L1Q_GS>): work
-// units are (row tile) x (entity tile), the row tiles known on the device only -- the host sizes
-// the grid from rows_max, an upper bound (workgroups past the last unit leave at once).
-// Units per claim, C2 N = 1 (103 row tiles x 111 entity tiles over 1,024 workgroups, ~11 units
-// each, heavy tiles first), per evaluation: chunks of 1 / 2 / 4 units (MMRE_SWEEP_CHUNK) 0.705 /
-// 0.733 / 0.969 ms -- with so few units per workgroup a 4-unit claim is a third of its share, and
-// the last claims leave a long tail (the ungrouped sweep's ~30 units each favoured 4: see
-// sweep_valu_body). The host picks 1 below 16 units per workgroup, as valu_grid does.
-template <int OP>
-static int launch_valu_grp(const SweepCall& C, L1Q l1, int64_t rows_max) {
-  const bool dyn = l1.wq != nullptr && C.kp / KC >= 2;
-  if (!dyn) l1.wq = nullptr;
-  int g = resident_groups((const void*)k_sweep_valu<OP, false, false, 0, 1, L1Q_GS>, NT);
-  if (!dyn) g *= 16;  // static ranges: short ones (valu_grid)
-  const int64_t q_tiles = (rows_max + TQ - 1) / TQ;
-  const int64_t units = sweep_units(q_tiles, C.n_et);
-  if (units < g) g = (int)(units > 0 ? units : 1);
-  // MMRE_SWEEP_GRID (A/B, tests; read per call here, as MMRE_SWEEP_AFFINE is): that many workgroups
-  const char* grid_env = getenv("MMRE_SWEEP_GRID");
-  if (grid_env && grid_env[0] >= '1' && grid_env[0] <= '9') g = std::max(1, atoi(grid_env));
-  // Row-tile-affine claims (l1.tq) are 1-unit claims at any share -- a claim keeps the workgroup's
-  // row tile, which is what the longer chunks were for; a chunk forced by MMRE_SWEEP_CHUNK keeps
-  // the sequential counter.
-  int chunk = dyn ? sweep_chunk(q_tiles * C.n_et / (g > 0 ? g : 1), true) : 0;
-  if (dyn && l1.tq != nullptr && getenv("MMRE_SWEEP_CHUNK") == nullptr) chunk = DYNC_AFFINE;
-  if (chunk != DYNC_AFFINE) l1.tq = nullptr;
-  const int ng = xcd_groups(g, C.n_et);
-  with_chunk<DYNC_AFFINE + 4 + 2 + 1>(chunk, [&](auto dync_) {
-    hipLaunchKernelGGL((k_sweep_valu<OP, false, false, 0, decltype(dync_)::value, L1Q_GS>), dim3((unsigned)g), dim3(NT),
-                       0, C.st, C.ent, C.e_pad, C.n_slice, C.q, C.q_pad, C.n_query, C.kp, C.n_et, C.e_base, ng, 0, 0.0f,
-                       C.truth, C.q_true, nullptr, nullptr, nullptr, nullptr, (int64_t)0, C.counts, nullptr, l1);
-  });
   MMRE_CHECK_LAUNCH();
   return MMRE_OK;
 }
@@ -5384,9 +3895,8 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   const char* cap_env = getenv("MMRE_GROUP_CAP");
   int row_cap = cap_env ? std::min(L1Q_GS, std::max(1, atoi(cap_env))) : L1Q_GS;
   if (!cap_env) {
-    const int64_t res = resident_groups((const void*)k_sweep_valu<6, false, false, 0, 1, L1Q_GS>, NT);
     const int64_t rows8 = std::min<int64_t>(n_query, n_groups + n_query / L1Q_GS);
-    if ((rows8 + TQ - 1) / TQ * C.n_et < res || (double)rows8 > L1Q_GROUP_FRAC * (double)n_query) row_cap = 0;
+    if (!valu_grp_fills_grid(rows8, C.n_et) || (double)rows8 > L1Q_GROUP_FRAC * (double)n_query) row_cap = 0;
   }
   const bool grouped = row_cap > 0;
   const int64_t rows_max = grouped ? std::min<int64_t>(n_query, n_groups + n_query / row_cap) : n_query;
@@ -5485,10 +3995,9 @@ extern "C" int mmre_link_evaluate_l1q(int norm_flag, const float* d_ent, int64_t
   bool heavy = bits != 16 && R.cap > 0;
   if (heavy && heavy_env) heavy = atoi(heavy_env) != 0;
   else if (heavy) {  // (the grouping rule's bound on the rows, whichever sweep MMRE_GROUP_CAP forces)
-    const int64_t res = resident_groups((const void*)k_sweep_valu<6, false, false, 0, 1, L1Q_GS>, NT);
     const int64_t rows8 = std::min<int64_t>(n_query, n_groups + n_query / L1Q_GS);
     // (a forced code width, MMRE_L1_BITS, is an A/B hook: its record stays the plain sweep's)
-    heavy = bits == 0 && (rows8 + TQ - 1) / TQ * C.n_et >= res;
+    heavy = bits == 0 && valu_grp_fills_grid(rows8, C.n_et);
   }
   HeavyProbe H{};
   uint32_t route_cap = 0;

@@ -13,7 +13,8 @@
 // share a row between triples (tripleclass.hip, ns.hip) or read the elements from memory instead
 // of registers (ns.hip row_score): the same operations on the same operands, in this order.
 // Users: ns.hip (row_score, the TransE and the generic forward), relpred.hip, tripleclass.hip.
-// Not the fused TransE step (ns_fused_body: its own reduction) nor link.hip (k-major tiles).
+// Not the fused TransE step (ns_fused_body: its own reduction) nor the link sweeps
+// (link.hip, link_valu.hip, transh.hip: k-major tiles, one sequential chain per pair).
 #pragma once
 #include "mmre_common.h"
 

@@ -23,21 +23,19 @@
 //   k_th_filter_count  one wave per filter group: counts = {0, -c, 0, -cc}
 //   k_sweep_transh     128 x 128 units, 16 x 16 threads, 8 x 8 f32 accumulators, K in 8-row
 //                      double-buffered LDS stages
-//   k_th_finalize      filtered columns += raw columns
 //   k_transh_rows      predict of arbitrary (h, r, t) rows, one thread per row
+// and, after the sweep, link.hip's finalize (launch_finalize: filtered columns += raw columns).
+// The tile geometry, the type-bit lookup and the grid rules are the link sweeps' own
+// (link_common.h).
 #include <algorithm>
-#include <type_traits>
 
-#include "mmre_common.h"
+#include "link_common.h"
 
 namespace mmre {
 namespace {
 
-constexpr int TQ = 128;  // query rows per workgroup tile (one relation per tile)
-constexpr int TE = 128;  // entities per workgroup tile
-constexpr int KC = 8;    // K rows per LDS stage
-constexpr int NT = 256;  // threads per workgroup
-
+// The tile geometry is the link sweeps' (link_common.h): TQ query rows per workgroup tile -- one
+// relation per tile here -- x TE entities, KC K rows per LDS stage, NT threads.
 __host__ __device__ inline int th_kp(int dim) { return (int)round_up(dim, KC); }
 
 // ------------------------------------------------------------ element functions ----
@@ -85,10 +83,6 @@ __device__ __forceinline__ float th_chain(const float* __restrict__ anchor, cons
     s = th_step<L2>(s, q, th_p<NORM>(cand[k], ac, wk, nc));
   }
   return th_final<L2>(s);
-}
-
-__device__ __forceinline__ bool th_type_bit(const uint32_t* __restrict__ mask, int64_t words, int64_t r, int64_t e) {
-  return (mask[r * words + (e >> 5)] >> (e & 31)) & 1u;
 }
 
 // ------------------------------------------------------------------ prologue ----
@@ -306,7 +300,7 @@ __global__ __launch_bounds__(64) void k_th_filter_count(THEval P, const int64_t*
           if (j >= 0 && j < P.n_ent) {
             id = (int32_t)j;
             v = list_v[lc + tid];
-            tb = tm ? (int32_t)th_type_bit(tm, type_words, G.r, j) : 0;
+            tb = tm ? (int32_t)type_bit(tm, type_words, G.r, j) : 0;
           }
         }
         s_id[tid] = id;
@@ -331,20 +325,14 @@ __global__ __launch_bounds__(64) void k_th_filter_count(THEval P, const int64_t*
   }
 }
 
-// filtered columns += raw columns, after the sweep
-__global__ __launch_bounds__(256) void k_th_finalize(int32_t* __restrict__ counts, int64_t n_query, int tc) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= n_query) return;
-  counts[n_query + q] += counts[q];
-  if (tc) counts[3 * n_query + q] += counts[2 * n_query + q];
-}
-
 // ------------------------------------------------------------------- sweep ----
 // Work unit = (query tile) x (entity tile). XCD group g (workgroups g, g + G, ...: the ones the
 // round-robin dispatch places on one XCD when the grid is a multiple of G = 8) owns n_et / G whole
 // entity tiles for every query tile, query-tile major, then a 1 / G share of the leftover tiles'
-// units; a workgroup sweeps one contiguous range of its group's units (link.hip's static split,
-// restated).
+// units; a workgroup sweeps one contiguous range of its group's units. This is link_common.h's
+// UnitMap without its entity-major order, kept as a type of its own: with UnitMap (emajor left at
+// its default) the four type-constrained k_sweep_transh instances allocate their SGPRs differently
+// -- the same instructions on other registers -- and the sweep is held to its measured code.
 struct THUnitMap {
   int m, r, ex0, el0, n_main, lo0, count;
   __device__ __forceinline__ THUnitMap(int grp, int n_groups, int n_qt, int n_et) {
@@ -674,35 +662,21 @@ int64_t th_layout(THWork& W, int64_t n_ent, int64_t n_rel, int dim, int64_t n_ti
   return at;
 }
 
-int th_resident(const void* kernel) {
-  int dev = 0, cus = 0, per = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, NT, 0) != hipSuccess || per <= 0) per = 1;
-  return cus * std::min(per, 4);
-}
-
 template <bool L2, bool TC, int PK, bool NORM>
 int th_launch_sweep(hipStream_t st, const THEval& P, const THWork& W, const int32_t* tiles, int64_t n_tiles,
                     int pred_kind, float margin, const float* thr, const uint32_t* type_head,
                     const uint32_t* type_tail, int32_t* counts) {
   const int n_et = (int)(P.e_pad / TE), n_qt = (int)n_tiles;
-  // 16 short static ranges per resident slot, as link.hip's f32 sweep; no more workgroups than the
-  // busiest XCD group has units
-  int64_t g = 16 * (int64_t)th_resident((const void*)k_sweep_transh<L2, TC, PK, NORM>);
-  const int64_t units = n_et >= 8 ? 8 * (int64_t)n_qt * ((n_et + 7) / 8) : (int64_t)n_qt * n_et;
-  if (units < g) g = units > 0 ? units : 1;
-  const int ng = (g % 8 == 0 && n_et >= 8) ? 8 : 1;
+  // 16 short static ranges per resident slot, as the link f32 sweep's (valu_grid, link_valu.hip);
+  // no more workgroups than the busiest XCD group has units
+  int g = 16 * resident_groups((const void*)k_sweep_transh<L2, TC, PK, NORM>, NT);
+  const int64_t units = sweep_units(n_qt, n_et);
+  if (units < g) g = (int)(units > 0 ? units : 1);
   hipLaunchKernelGGL((k_sweep_transh<L2, TC, PK, NORM>), dim3((unsigned)g), dim3(NT), 0, st, P, W.q_km, n_tiles * TQ,
-                     tiles, n_qt, n_et, ng, pred_kind, margin, thr, W.row_q, type_head, type_tail,
+                     tiles, n_qt, n_et, xcd_groups(g, n_et), pred_kind, margin, thr, W.row_q, type_head, type_tail,
                      (P.n_ent + 31) / 32, counts);
   MMRE_CHECK_LAUNCH();
   return MMRE_OK;
-}
-
-template <class F>
-int th_bool(bool b, F&& f) {
-  return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 }  // namespace
@@ -763,8 +737,8 @@ extern "C" int mmre_transh_evaluate(int model, int norm_flag, int pred_kind, flo
   const bool l2 = model == MMRE_TRANSH_L2, tc = d_type_head != nullptr;
   const int64_t tasks = n_query + n_entries;
   const int64_t fc_grid = grouped ? std::min<int64_t>(n_groups, 1 << 20) : std::min<int64_t>((n_query + 63) / 64, 4096);
-  return th_bool(l2, [&](auto l2_) {
-    return th_bool(norm_flag != 0, [&](auto nm_) {
+  return with_bool(l2, [&](auto l2_) {
+    return with_bool(norm_flag != 0, [&](auto nm_) {
       constexpr bool L2 = decltype(l2_)::value, NORM = decltype(nm_)::value;
       hipLaunchKernelGGL((k_th_queries<NORM>), dim3((unsigned)n_tiles), dim3(TQ), 0, st, P, d_perm, d_tiles, n_tiles,
                          W.q_km, W.row_q);
@@ -776,7 +750,7 @@ extern "C" int mmre_transh_evaluate(int model, int norm_flag, int pred_kind, flo
                          d_filt_off, d_filt_ids, W.list_v, n_entries, d_truth, d_type_head, d_type_tail,
                          (n_ent + 31) / 32, d_counts);
       MMRE_CHECK_LAUNCH();
-      const int rs = th_bool(tc, [&](auto tc_) {
+      const int rs = with_bool(tc, [&](auto tc_) {
         constexpr bool TC = decltype(tc_)::value;
         return pred_kind == 0 ? th_launch_sweep<L2, TC, 0, NORM>(st, P, W, d_tiles, n_tiles, pred_kind, margin, d_truth,
                                                                  d_type_head, d_type_tail, d_counts)
@@ -784,10 +758,7 @@ extern "C" int mmre_transh_evaluate(int model, int norm_flag, int pred_kind, flo
                                                                  d_type_head, d_type_tail, d_counts);
       });
       if (rs != MMRE_OK) return rs;
-      hipLaunchKernelGGL(k_th_finalize, dim3((unsigned)((n_query + 255) / 256)), dim3(256), 0, st, d_counts, n_query,
-                         tc ? 1 : 0);
-      MMRE_CHECK_LAUNCH();
-      return (int)MMRE_OK;
+      return launch_finalize(st, d_counts, n_query, tc);  // filtered columns += raw columns
     });
   });
 }
@@ -804,8 +775,8 @@ extern "C" int mmre_transh_score_rows(int model, int norm_flag, int pred_kind, f
   if (n_rows == 0) return MMRE_OK;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((n_rows + 127) / 128));
-  return th_bool(model == MMRE_TRANSH_L2, [&](auto l2_) {
-    return th_bool(norm_flag != 0, [&](auto nm_) {
+  return with_bool(model == MMRE_TRANSH_L2, [&](auto l2_) {
+    return with_bool(norm_flag != 0, [&](auto nm_) {
       hipLaunchKernelGGL((k_transh_rows<decltype(l2_)::value, decltype(nm_)::value>), grid, dim3(128), 0, st, d_ent,
                          d_rel, d_norm, n_ent, n_rel, dim, d_h, d_r, d_t, n_rows, head_batch, pred_kind, margin, d_out);
       MMRE_CHECK_LAUNCH();

@@ -1,5 +1,5 @@
 """Row-tile changes of the grouped sweep's claim rules, counted on the CPU from the rules alone
-(csrc/link.hip: sweep_valu_body's claim_affine and the sequential counter). One XCD group of C2:
+(csrc/link_valu.hip: sweep_valu_body's claim_affine and the sequential counter). One XCD group of C2:
 128 workgroups, 103 row tiles of 13 or 14 units (13 main entity tiles + the group's share of the
 7 leftover tiles' units). A unit costs 1 (the lightest row tile) to `heavy` (the first), +-10 %;
 a row-tile change is a unit whose row tile differs from the workgroup's previous one (the flush /

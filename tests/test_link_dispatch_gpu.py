@@ -1,4 +1,4 @@
-"""One case per branch of the link sweeps' host dispatch (csrc/link.hip), at the smallest shape
+"""One case per branch of the link sweeps' host dispatch (csrc/link.hip, link_valu.hip), at the smallest shape
 that still has two tiles on each axis and a ragged tail: E = 300 (three 128-entity tiles, the
 last one ragged), Q = 130 (two query tiles), R = 5; d = 20 for TransE L1 / L2 and RotatE, 16 and
 24 for DistMult and ComplEx. Inputs as test_link_gpu._random_case(with_ties=True) builds them (a

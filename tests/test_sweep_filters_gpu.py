@@ -1,4 +1,4 @@
-"""GPU parity of the sweep's filters (csrc/link.hip): the count-only RotatE sweeps sum the raw
+"""GPU parity of the sweep's filters (csrc/link_valu.hip): the count-only RotatE sweeps sum the raw
 v_sqrt_f32 -- within 1 ulp of sqrtf (scripts/probes/sqrt_ulp.hip, exhaustive) -- and the
 count-only TransE L1 sweeps sum |code differences| of 8-bit (v_sad_u8) or 16-bit (v_sad_u16)
 quantized planes (mmre_link_sweep_l1q; the width picked on the device by a sampled probe, or
