@@ -35,7 +35,10 @@ enum {
   MMRE_ROTATE = 4,
   /* TransH (mmre_transh_* only; the entry points above answer MMRE_ERR_MODEL for them) */
   MMRE_TRANSH_L1 = 5,
-  MMRE_TRANSH_L2 = 6
+  MMRE_TRANSH_L2 = 6,
+  /* TransD (mmre_transd_* only; every other entry point answers MMRE_ERR_MODEL for them) */
+  MMRE_TRANSD_L1 = 7,
+  MMRE_TRANSD_L2 = 8
 };
 enum { MMRE_HEAD_BATCH = 0, MMRE_TAIL_BATCH = 1 };
 /* Loss of the negative-sampling entry points (mmre_ns_opts_t) and the optimizer whose step the
@@ -381,6 +384,56 @@ int mmre_transh_ns_grad(int model, int norm_flag, float model_margin, int use_mo
                         float adv_temperature, float regul_rate, const float* d_score, const float* d_grad_loss,
                         float* d_grad_ent, float* d_grad_rel, float* d_grad_norm, float* d_work, float lr,
                         void* stream);
+
+/* ====================================================================== *
+ *  TransD (OpenKE/openke/module/model/TransD.py): link prediction with    *
+ *  entities moved by the transfer vectors of the entity and of the        *
+ *  query's relation, and predict for arbitrary rows. Models               *
+ *  MMRE_TRANSD_L1 / MMRE_TRANSD_L2 (p_norm 1 / 2). Tables: entities and   *
+ *  ent_transfer (E, dim_e), relations and rel_transfer (R, dim_r),        *
+ *  dim_e >= dim_r (a wider entity row is cut to its first dim_r values,   *
+ *  TransD.py:62-68). csrc/transh.hip: TransH's sweep, another prologue.   *
+ * ====================================================================== */
+
+/* Bytes of d_work for mmre_transd_evaluate: mmre_transh_workspace at dim = dim_r (the k-major
+ * and row-major copies of the narrowed entity table, the relation vectors, the (a, n) table of
+ * 2 * n_used * e_pad floats, which holds (-s(e), N(r, e)): s = e . e_p over dim_e (TransD.py:100),
+ * N the divisor of both normalisations (TransD.py:99-103, :79-82), the query planes and the listed
+ * scores) plus s itself, e_pad floats. 0 for a non-positive size or dim_e < dim_r. */
+int64_t mmre_transd_workspace(int64_t n_ent, int64_t n_rel, int dim_e, int dim_r, int64_t n_tiles, int64_t n_used,
+                              int64_t n_entries);
+
+/* One TransD link-prediction evaluation, enqueued on `stream`: mmre_transh_evaluate's contract
+ * (the Tester loop Tester.py:70-91 around TransD.predict TransD.py:149-155 = forward :112-129
+ * with _transfer :94-110 and _calc :78-92) with TransD's tables. d_ent and d_ent_transfer
+ * (E, dim_e), d_rel and d_rel_transfer (R, dim_r); d_ent_narrow (E, dim_r), contiguous: the first
+ * dim_r columns of d_ent (it may be d_ent itself when dim_e == dim_r). Queries, the plan of
+ * one-relation query tiles, filter groups, type masks, pred_kind (0 / 1), d_counts and d_truth as
+ * mmre_transh_evaluate takes and writes them. norm_flag: _calc's normalisation of h, r and t;
+ * _transfer's own is always applied.
+ * Checked in this order: the model (MMRE_ERR_MODEL), null tables and arrays and the sizes
+ * (MMRE_ERR_ARG), dim_r <= 0 or dim_e < dim_r (MMRE_ERR_SHAPE), work_bytes (MMRE_ERR_WORKSPACE). */
+int mmre_transd_evaluate(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                         const float* d_ent_transfer, const float* d_rel, const float* d_rel_transfer,
+                         const float* d_ent_narrow, int64_t n_ent, int64_t n_rel, int dim_e, int dim_r,
+                         const int64_t* d_qh, const int64_t* d_qr, const int64_t* d_qt, const int8_t* d_qmode,
+                         int64_t n_query, const int32_t* d_perm, const int32_t* d_tiles, int64_t n_tiles,
+                         const int32_t* d_used, int64_t n_used, const int32_t* d_rel_slot,
+                         const int64_t* d_grp_qoff, const int32_t* d_grp_q, int64_t n_groups,
+                         const int64_t* d_filt_off, const int32_t* d_filt_ids, const int32_t* d_entry_q,
+                         int64_t n_entries, const uint32_t* d_type_head, const uint32_t* d_type_tail,
+                         int32_t* d_counts, float* d_truth, void* d_work, int64_t work_bytes, void* stream);
+
+/* TransD.predict / forward values of the rows (d_h[i], d_r[i], d_t[i]) (TransD.py:112-129,
+ * :149-155) from the raw tables, bit for bit what mmre_transd_evaluate scores for the same triple
+ * and mode. head_batch != 0: the grouping h + (r - t) of TransD.py:87-88, else (h + r) - t.
+ * pred_kind as apply_pred's 0 .. 4 (4 = m - s, forward() of a model with a margin). A row with an
+ * id outside the tables gets NaN. */
+int mmre_transd_score_rows(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                           const float* d_ent_transfer, const float* d_rel, const float* d_rel_transfer,
+                           int64_t n_ent, int64_t n_rel, int dim_e, int dim_r, const int64_t* d_h,
+                           const int64_t* d_r, const int64_t* d_t, int64_t n_rows, int head_batch, float* d_out,
+                           void* stream);
 
 /* ====================================================================== *
  *  Relation prediction: every test pair (h, t) against every relation.   *

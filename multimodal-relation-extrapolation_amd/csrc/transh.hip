@@ -784,3 +784,328 @@ extern "C" int mmre_transh_score_rows(int model, int norm_flag, int pred_kind, f
     });
   });
 }
+
+// =====================================================================================
+// TransD (OpenKE/openke/module/model/TransD.py:78-155): the transfer projection
+//   e_perp = normalize(e[:dim_r] + (e . e_p) r_p)                          (TransD.py:94-110)
+// is TransH's staged element with another prologue: with s(e) = e . e_p over dim_e (relation-
+// independent) the (a, n) table holds (-s(e), N(r, e)) and the w_hat table the RAW rel_transfer
+// rows, so (e_k - a w_k) / n = (e_k + s rp_k) / N bit for bit ((-s) x == -(s x), y - (-z) == y + z).
+// _transfer always normalises, so the NORM = true instances of k_th_queries, k_th_scores and
+// k_sweep_transh run whatever norm_flag says; norm_flag adds _calc's second normalisation
+// (TransD.py:79-82), folded into the one divisor N = n1 * n2, and r_hat.
+//
+// Canonical arithmetic (TransD): as TransH's -- f32, no contraction, IEEE division
+// and sqrtf, every sum one sequential chain in ascending k from 0.0f.
+//   s = sum_{k < dim_e} e_k ep_k ; a = -s ; u_k = e_k - a rp_k (k < dim_r) ; n1 = den(sum u_k u_k)
+//   norm_flag: n2 = den(sum (u_k / n1)(u_k / n1)), N = n1 * n2 ; else N = n1 ; p_k = u_k / N
+//
+// New kernels:
+//   k_td_relations  w[R][kp] = raw rel_transfer, r_hat[R][kp] as k_th_relations makes it
+//   k_td_s          s[e] over dim_e from the raw (E, dim_e) tables
+//   k_td_an         (-s, N)[used relation][entity] from the raw k-major planes (first dim_r columns)
+//   k_transd_rows   predict of arbitrary (h, r, t) rows, one thread per row
+namespace mmre {
+namespace {
+
+// One 64-thread workgroup per relation: w = the raw rel_transfer row, r_hat = r / max(|r|, 1e-12)
+// with norm_flag (TransD.py:81), else r; rows padded to kp with zeros. The norm is one sequential
+// chain, by lane 0 from LDS.
+__global__ __launch_bounds__(64) void k_td_relations(const float* __restrict__ rel_transfer,
+                                                     const float* __restrict__ rel, int dim, int kp, int norm_flag,
+                                                     float* __restrict__ w, float* __restrict__ r_hat) {
+  extern __shared__ float lds[];  // [kp]
+  __shared__ float s_den;
+  const int64_t r = blockIdx.x;
+  for (int k = threadIdx.x; k < kp; k += 64) lds[k] = k < dim ? rel[r * dim + k] : 0.0f;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float ss = 0.0f;
+    for (int k = 0; k < dim; ++k) ss = ss + lds[k] * lds[k];
+    s_den = th_den(ss);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < kp; k += 64) {
+    w[r * kp + k] = k < dim ? rel_transfer[r * dim + k] : 0.0f;
+    r_hat[r * kp + k] = norm_flag ? lds[k] / s_den : lds[k];
+  }
+}
+
+// s[e] = sum_{k < dim_e} ent[e][k] * ent_transfer[e][k] (TransD.py:100), one sequential chain per
+// entity. A workgroup takes TD_SE entities: all 256 threads copy TD_SK-wide slices of both tables'
+// rows to LDS (coalesced along k), then thread e < TD_SE extends its entity's chain over the slice
+// (row stride TD_SK + 1: the 64 chains read 64 different banks). Columns n_ent .. e_pad get 0.
+constexpr int TD_SE = 64, TD_SK = 32;
+__global__ __launch_bounds__(256) void k_td_s(const float* __restrict__ ent, const float* __restrict__ ent_transfer,
+                                              int64_t n_ent, int64_t e_pad, int dim_e, float* __restrict__ s) {
+  __shared__ float sx[TD_SE][TD_SK + 1], sy[TD_SE][TD_SK + 1];
+  const int64_t e0 = (int64_t)blockIdx.x * TD_SE;
+  float acc = 0.0f;
+  for (int k0 = 0; k0 < dim_e; k0 += TD_SK) {
+    for (int i = threadIdx.x; i < TD_SE * TD_SK; i += 256) {
+      const int row = i / TD_SK, col = i % TD_SK;
+      const int64_t e = e0 + row;
+      const bool in = e < n_ent && k0 + col < dim_e;
+      sx[row][col] = in ? ent[e * dim_e + k0 + col] : 0.0f;
+      sy[row][col] = in ? ent_transfer[e * dim_e + k0 + col] : 0.0f;
+    }
+    __syncthreads();
+    if (threadIdx.x < TD_SE) {
+      const int nk = dim_e - k0 < TD_SK ? dim_e - k0 : TD_SK;
+      for (int k = 0; k < nk; ++k) acc = acc + sx[threadIdx.x][k] * sy[threadIdx.x][k];
+    }
+    __syncthreads();  // the slice is read before the next one overwrites it
+  }
+  const int64_t e = e0 + threadIdx.x;
+  if (threadIdx.x < TD_SE && e < e_pad) s[e] = e < n_ent ? acc : 0.0f;
+}
+
+// (-s, N) of every entity column for TD_RB used relations per workgroup, in k_th_an's shape: a
+// thread owns one column of the k-major planes and TD_RB chains per pass, the relations' raw
+// transfer rows in LDS. Pass 1: n1 = den(sum u u), u = x - a rp; with norm_flag pass 2: n2 =
+// den(sum (u / n1)(u / n1)) and N = n1 * n2 (one multiply), else N = n1. Padded columns hold zeros
+// and s = 0: u = 0, N = 1e-12 or 1e-24 -- finite, and the sweep never counts them.
+// TD_RB is 2 where k_th_an's AN_RB is 4: pass 2 is bound by its IEEE division per element and
+// relation, not by the plane loads a wider block saves (C2 shape, 29 relations: 92 us at 4, 69 at 2,
+// 63 at 1; profiles/transd/README.md).
+constexpr int TD_RB = 2;
+__global__ __launch_bounds__(256) void k_td_an(const float* __restrict__ ent_km, int64_t e_pad, int dim, int kp,
+                                               const float* __restrict__ w, const float* __restrict__ s,
+                                               const int32_t* __restrict__ used, int64_t n_used, int64_t n_rel,
+                                               int norm_flag, float* __restrict__ an) {
+  extern __shared__ float sw[];  // [TD_RB][kp]
+  const int64_t u0 = (int64_t)blockIdx.y * TD_RB;
+  for (int i = threadIdx.x; i < TD_RB * kp; i += 256) {
+    const int64_t u = u0 + i / kp;
+    int64_t r = u < n_used ? used[u] : -1;
+    sw[i] = (r >= 0 && r < n_rel) ? w[r * kp + i % kp] : 0.0f;
+  }
+  __syncthreads();
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= e_pad) return;
+  const float a = -s[e];
+  float n1[TD_RB], ss[TD_RB];
+#pragma unroll
+  for (int j = 0; j < TD_RB; ++j) ss[j] = 0.0f;
+  for (int k = 0; k < dim; ++k) {
+    const float x = ent_km[(int64_t)k * e_pad + e];
+#pragma unroll
+    for (int j = 0; j < TD_RB; ++j) {
+      const float u = x - a * sw[j * kp + k];
+      ss[j] = ss[j] + u * u;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < TD_RB; ++j) {
+    n1[j] = th_den(ss[j]);
+    ss[j] = 0.0f;
+  }
+  if (norm_flag) {
+    for (int k = 0; k < dim; ++k) {
+      const float x = ent_km[(int64_t)k * e_pad + e];
+#pragma unroll
+      for (int j = 0; j < TD_RB; ++j) {
+        const float v = (x - a * sw[j * kp + k]) / n1[j];
+        ss[j] = ss[j] + v * v;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < TD_RB; ++j) {
+    if (u0 + j >= n_used) break;
+    an[(2 * (u0 + j)) * e_pad + e] = a;
+    an[(2 * (u0 + j) + 1) * e_pad + e] = norm_flag ? n1[j] * th_den(ss[j]) : n1[j];
+  }
+}
+
+// (a, N) of one entity row x (stride-1, dim_e values, transfer row xp) under the raw transfer row
+// rp of a relation (dim_r values), by the chains of k_td_s and k_td_an.
+template <bool NF>
+__device__ __forceinline__ void td_an_row(const float* __restrict__ x, const float* __restrict__ xp,
+                                          const float* __restrict__ rp, int dim_e, int dim_r, float& a, float& n) {
+  float s = 0.0f;
+  for (int k = 0; k < dim_e; ++k) s = s + x[k] * xp[k];
+  a = -s;
+  float ss = 0.0f;
+  for (int k = 0; k < dim_r; ++k) {
+    const float u = x[k] - a * rp[k];
+    ss = ss + u * u;
+  }
+  const float n1 = th_den(ss);
+  if constexpr (NF) {
+    float s2 = 0.0f;
+    for (int k = 0; k < dim_r; ++k) {
+      const float v = (x[k] - a * rp[k]) / n1;
+      s2 = s2 + v * v;
+    }
+    n = n1 * th_den(s2);
+  } else {
+    n = n1;
+  }
+}
+
+// predict of arbitrary rows, one thread per row, from the raw tables (entity rows of stride
+// dim_e, relation rows of stride dim_r): (a, N) of both entities and r_hat by the prologue's
+// chains, then the sweep's score chain. NF: norm_flag. head != 0: the head_batch grouping
+// h + (r - t), else (h + r) - t (TransD.py:87-90).
+template <bool L2, bool NF>
+__global__ __launch_bounds__(128) void k_transd_rows(const float* __restrict__ ent,
+                                                     const float* __restrict__ ent_transfer,
+                                                     const float* __restrict__ rel,
+                                                     const float* __restrict__ rel_transfer, int64_t n_ent,
+                                                     int64_t n_rel, int dim_e, int dim_r,
+                                                     const int64_t* __restrict__ hs, const int64_t* __restrict__ rs,
+                                                     const int64_t* __restrict__ ts, int64_t n_rows, int head,
+                                                     int pred_kind, float margin, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_rows) return;
+  const int64_t h = hs[i], r = rs[i], t = ts[i];
+  if (h < 0 || h >= n_ent || t < 0 || t >= n_ent || r < 0 || r >= n_rel) {
+    out[i] = __builtin_nanf("");
+    return;
+  }
+  const float* rp = rel_transfer + r * dim_r;
+  const float* rr = rel + r * dim_r;
+  float dr = 1.0f;
+  if constexpr (NF) {
+    float sr = 0.0f;
+    for (int k = 0; k < dim_r; ++k) sr = sr + rr[k] * rr[k];
+    dr = th_den(sr);
+  }
+  const int64_t ia = head ? t : h, ic = head ? h : t;  // anchor, candidate
+  const float* xa = ent + ia * dim_e;
+  const float* xc = ent + ic * dim_e;
+  float aa, na, ac, nc;
+  td_an_row<NF>(xa, ent_transfer + ia * dim_e, rp, dim_e, dim_r, aa, na);
+  td_an_row<NF>(xc, ent_transfer + ic * dim_e, rp, dim_e, dim_r, ac, nc);
+  float s = 0.0f;
+  for (int k = 0; k < dim_r; ++k) {
+    const float wk = rp[k];
+    const float rh = NF ? rr[k] / dr : rr[k];
+    const float q = th_q(th_p<true>(xa[k], aa, wk, na), rh, head != 0);
+    s = th_step<L2>(s, q, th_p<true>(xc[k], ac, wk, nc));
+  }
+  out[i] = apply_pred(pred_kind, margin, th_final<L2>(s));
+}
+
+inline bool td_model(int m) { return m == MMRE_TRANSD_L1 || m == MMRE_TRANSD_L2; }
+
+// TransH's workspace at dim_r, then s[e_pad]
+int64_t td_layout(THWork& W, float*& s, int64_t n_ent, int64_t n_rel, int dim_r, int64_t n_tiles, int64_t n_used,
+                  int64_t n_entries, void* base) {
+  const int64_t at = th_layout(W, n_ent, n_rel, dim_r, n_tiles, n_used, n_entries, base);
+  s = base ? (float*)((char*)base + at) : nullptr;
+  return at + round_up(round_up(n_ent > 0 ? n_ent : 1, TE) * 4, 256);
+}
+
+}  // namespace
+}  // namespace mmre
+
+extern "C" int64_t mmre_transd_workspace(int64_t n_ent, int64_t n_rel, int dim_e, int dim_r, int64_t n_tiles,
+                                         int64_t n_used, int64_t n_entries) {
+  if (n_ent <= 0 || n_rel <= 0 || dim_r <= 0 || dim_e < dim_r || n_tiles < 0 || n_used < 0 || n_entries < 0) return 0;
+  THWork W;
+  float* s;
+  return td_layout(W, s, n_ent, n_rel, dim_r, n_tiles, n_used, n_entries, nullptr);
+}
+
+extern "C" int mmre_transd_evaluate(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                                    const float* d_ent_transfer, const float* d_rel, const float* d_rel_transfer,
+                                    const float* d_ent_narrow, int64_t n_ent, int64_t n_rel, int dim_e, int dim_r,
+                                    const int64_t* d_qh, const int64_t* d_qr, const int64_t* d_qt,
+                                    const int8_t* d_qmode, int64_t n_query, const int32_t* d_perm,
+                                    const int32_t* d_tiles, int64_t n_tiles, const int32_t* d_used, int64_t n_used,
+                                    const int32_t* d_rel_slot, const int64_t* d_grp_qoff, const int32_t* d_grp_q,
+                                    int64_t n_groups, const int64_t* d_filt_off, const int32_t* d_filt_ids,
+                                    const int32_t* d_entry_q, int64_t n_entries, const uint32_t* d_type_head,
+                                    const uint32_t* d_type_tail, int32_t* d_counts, float* d_truth, void* d_work,
+                                    int64_t work_bytes, void* stream) {
+  if (!td_model(model)) return MMRE_ERR_MODEL;
+  if (!d_ent || !d_ent_transfer || !d_rel || !d_rel_transfer || !d_ent_narrow || !d_qh || !d_qr || !d_qt ||
+      !d_qmode || !d_perm || !d_tiles || !d_used || !d_rel_slot || !d_counts || !d_truth || !d_work)
+    return MMRE_ERR_ARG;
+  if (n_ent <= 0 || n_rel <= 0 || n_query <= 0 || n_tiles <= 0 || n_used <= 0 || n_used > n_rel) return MMRE_ERR_ARG;
+  if (pred_kind < 0 || pred_kind > 1) return MMRE_ERR_ARG;
+  if ((d_type_head == nullptr) != (d_type_tail == nullptr)) return MMRE_ERR_ARG;
+  const bool grouped = d_grp_qoff != nullptr;
+  if (grouped && (!d_grp_q || !d_filt_off || n_groups <= 0 || n_entries < 0 ||
+                  (n_entries > 0 && (!d_filt_ids || !d_entry_q))))
+    return MMRE_ERR_ARG;
+  if (!grouped) n_entries = 0;
+  if (dim_r <= 0 || dim_e < dim_r) return MMRE_ERR_SHAPE;
+  if (n_ent > (int64_t)INT32_MAX - 256 || n_query > (int64_t)INT32_MAX - 256 || n_tiles > (1 << 24))
+    return MMRE_ERR_SHAPE;
+  THWork W;
+  float* s;
+  if (work_bytes < td_layout(W, s, n_ent, n_rel, dim_r, n_tiles, n_used, n_entries, d_work)) return MMRE_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int kp = th_kp(dim_r);
+  const int64_t e_pad = round_up(n_ent, TE);
+  // the raw k-major planes and the row-major copy of the first dim_r columns (TransD.py:62-68)
+  const int rc = mmre_link_prepare_entities(MMRE_TRANSE_L1, 0, d_ent_narrow, nullptr, n_ent, dim_r, W.ent_km, e_pad,
+                                            W.ent_rows, stream);
+  if (rc != MMRE_OK) return rc;
+  hipLaunchKernelGGL(k_td_relations, dim3((unsigned)n_rel), dim3(64), kp * sizeof(float), st, d_rel_transfer, d_rel,
+                     dim_r, kp, norm_flag, W.w_hat, W.r_hat);
+  MMRE_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_td_s, dim3((unsigned)((e_pad + TD_SE - 1) / TD_SE)), dim3(256), 0, st, d_ent, d_ent_transfer,
+                     n_ent, e_pad, dim_e, s);
+  MMRE_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_td_an, dim3((unsigned)(e_pad / 256 + (e_pad % 256 != 0)), (unsigned)((n_used + TD_RB - 1) / TD_RB)),
+                     dim3(256), TD_RB * kp * sizeof(float), st, W.ent_km, e_pad, dim_r, kp, W.w_hat, s, d_used, n_used,
+                     n_rel, norm_flag, W.an);
+  MMRE_CHECK_LAUNCH();
+  THEval P{W.ent_km, W.ent_rows, W.w_hat, W.r_hat, W.an, d_rel_slot, n_ent, e_pad, n_rel, n_used, n_query,
+           dim_r,    kp,         d_qh,    d_qr,    d_qt, d_qmode};
+  const bool l2 = model == MMRE_TRANSD_L2, tc = d_type_head != nullptr;
+  const int64_t tasks = n_query + n_entries;
+  const int64_t fc_grid = grouped ? std::min<int64_t>(n_groups, 1 << 20) : std::min<int64_t>((n_query + 63) / 64, 4096);
+  // from here on TransH's NORM = true kernels, unchanged: the staged element is (e - a w) / n
+  return with_bool(l2, [&](auto l2_) {
+    constexpr bool L2 = decltype(l2_)::value;
+    hipLaunchKernelGGL((k_th_queries<true>), dim3((unsigned)n_tiles), dim3(TQ), 0, st, P, d_perm, d_tiles, n_tiles,
+                       W.q_km, W.row_q);
+    MMRE_CHECK_LAUNCH();
+    hipLaunchKernelGGL((k_th_scores<L2, true>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st, P, pred_kind,
+                       margin, d_entry_q, d_filt_ids, n_entries, d_truth, W.list_v);
+    MMRE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_th_filter_count, dim3((unsigned)fc_grid), dim3(64), 0, st, P, d_grp_qoff, d_grp_q, n_groups,
+                       d_filt_off, d_filt_ids, W.list_v, n_entries, d_truth, d_type_head, d_type_tail,
+                       (n_ent + 31) / 32, d_counts);
+    MMRE_CHECK_LAUNCH();
+    const int rs = with_bool(tc, [&](auto tc_) {
+      constexpr bool TC = decltype(tc_)::value;
+      return pred_kind == 0 ? th_launch_sweep<L2, TC, 0, true>(st, P, W, d_tiles, n_tiles, pred_kind, margin, d_truth,
+                                                               d_type_head, d_type_tail, d_counts)
+                            : th_launch_sweep<L2, TC, 1, true>(st, P, W, d_tiles, n_tiles, pred_kind, margin, d_truth,
+                                                               d_type_head, d_type_tail, d_counts);
+    });
+    if (rs != MMRE_OK) return rs;
+    return launch_finalize(st, d_counts, n_query, tc);  // filtered columns += raw columns
+  });
+}
+
+extern "C" int mmre_transd_score_rows(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                                      const float* d_ent_transfer, const float* d_rel, const float* d_rel_transfer,
+                                      int64_t n_ent, int64_t n_rel, int dim_e, int dim_r, const int64_t* d_h,
+                                      const int64_t* d_r, const int64_t* d_t, int64_t n_rows, int head_batch,
+                                      float* d_out, void* stream) {
+  if (!td_model(model)) return MMRE_ERR_MODEL;
+  if (!d_ent || !d_ent_transfer || !d_rel || !d_rel_transfer || n_ent <= 0 || n_rel <= 0 || n_rows < 0)
+    return MMRE_ERR_ARG;
+  if (n_rows > 0 && (!d_h || !d_r || !d_t || !d_out)) return MMRE_ERR_ARG;
+  if (pred_kind < 0 || pred_kind > 4) return MMRE_ERR_ARG;
+  if (dim_r <= 0 || dim_e < dim_r) return MMRE_ERR_SHAPE;
+  if (n_rows == 0) return MMRE_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)((n_rows + 127) / 128));
+  return with_bool(model == MMRE_TRANSD_L2, [&](auto l2_) {
+    return with_bool(norm_flag != 0, [&](auto nf_) {
+      hipLaunchKernelGGL((k_transd_rows<decltype(l2_)::value, decltype(nf_)::value>), grid, dim3(128), 0, st, d_ent,
+                         d_ent_transfer, d_rel, d_rel_transfer, n_ent, n_rel, dim_e, dim_r, d_h, d_r, d_t, n_rows,
+                         head_batch, pred_kind, margin, d_out);
+      MMRE_CHECK_LAUNCH();
+      return (int)MMRE_OK;
+    });
+  });
+}

@@ -20,7 +20,8 @@ from . import _lib
 from ._lib import call, ptr, stream_ptr
 
 MODEL_IDS = {"transe": 0, "transe_l2": 1, "distmult": 2, "complex": 3, "rotate": 4,
-             "transh": 5, "transh_l2": 6}  # TransH: mmre.transh (TransHSweep, score_rows) only
+             "transh": 5, "transh_l2": 6,  # TransH: mmre.transh (TransHSweep, score_rows) only
+             "transd": 7, "transd_l2": 8}  # TransD: mmre.transd (TransDSweep, score_rows) only
 HEAD, TAIL = 0, 1
 METRIC_NAMES = ["mrr", "mr", "hit10", "hit3", "hit1"]
 GROUPS = ["filter", "raw", "filter_tc", "raw_tc"]
@@ -40,6 +41,10 @@ class ScoreSpec:
     margin: float = 0.0
     phase_denom: float = 0.0        # RotatE
     norm_vec: torch.Tensor | None = None   # TransH: the hyperplane normals (R, d)
+    # TransD: ent is (E, dim_e), rel (R, dim_r) and dim is dim_r; the transfer vectors of both
+    ent_transfer: torch.Tensor | None = None   # (E, dim_e)
+    rel_transfer: torch.Tensor | None = None   # (R, dim_r)
+    dim_e: int = 0
 
 
 def rotate_phase_denom(margin: float, epsilon: float, dim: int) -> float:
@@ -201,6 +206,8 @@ class LinkSweep:
     def __init__(self, spec: ScoreSpec):
         if spec.model in ("transh", "transh_l2"):
             raise ValueError("TransH sweeps one relation per query tile: use mmre.transh.TransHSweep")
+        if spec.model in ("transd", "transd_l2"):
+            raise ValueError("TransD sweeps one relation per query tile: use mmre.transd.TransDSweep")
         self.spec = spec
         self.model_id = MODEL_IDS[spec.model]
         dev = spec.ent.device
@@ -531,6 +538,11 @@ def evaluate_link_prediction(spec: ScoreSpec, test_h, test_r, test_t, index: Fil
         from .transh import TransHSweep, plan_tiles
         res = TransHSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
                                     torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks, plan=plan_tiles(qr))
+    elif spec.model in ("transd", "transd_l2"):  # TransH's plan and sweep, TransD's prologue
+        from .transd import TransDSweep
+        from .transh import plan_tiles
+        res = TransDSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
+                                    torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks, plan=plan_tiles(qr))
     else:
         res = LinkSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
                                   torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks)
@@ -601,6 +613,9 @@ def evaluate_relation_prediction(spec: ScoreSpec, test_h, test_r, test_t, index:
     if spec.model in ("transh", "transh_l2"):
         raise NotImplementedError("relation prediction for TransH: every candidate relation projects both "
                                   "entities on its own hyperplane; no TransH relation sweep is built yet")
+    if spec.model in ("transd", "transd_l2"):
+        raise NotImplementedError("relation prediction for TransD: every candidate relation moves both "
+                                  "entities by its own transfer vector; no TransD relation sweep is built yet")
     test_h, test_r, test_t = (np.asarray(x, np.int64) for x in (test_h, test_r, test_t))
     dev = spec.ent.device
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)

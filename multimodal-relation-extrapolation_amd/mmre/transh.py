@@ -87,13 +87,22 @@ class TransHSweep:
         if tuple(self._nv.shape) != tuple(self._rel.shape):
             raise ValueError("TransH: norm_vec and rel must have one shape")
 
+    # the two calls a model of this sweep family makes with its own tables (mmre.transd overrides them)
+    def _workspace(self, n_tiles, n_used, n_entries):
+        return _lib.lib().mmre_transh_workspace(self.n_ent, self.n_rel, int(self.spec.dim), n_tiles, n_used, n_entries)
+
+    def _evaluate(self, *rest):
+        s = self.spec
+        call("mmre_transh_evaluate", self.model_id, int(bool(s.norm_flag)), int(s.pred_kind), float(s.margin),
+             ptr(self._ent), ptr(self._rel), ptr(self._nv), self.n_ent, self.n_rel, int(s.dim), *rest)
+
     def run(self, qh, qr, qt, qmode, filt=None, type_masks=None, buffers=None, plan=None, events=None):
         """qh/qr/qt int64 and qmode int8 device tensors; filt: filter groups (FilterIndex.groups)
         or None; type_masks: (head, tail) uint32 device bitsets or None; plan: plan_tiles(qr) when
         the caller has it (else qr is read back once). events: optional (start, end)
         torch.cuda.Event pair recorded around the whole enqueued evaluation.
         Returns dict(counts=(4, Q) int32 [raw, filt, raw_tc, filt_tc], truth=(Q,), padding)."""
-        s, dev = self.spec, self.device
+        dev, who = self.device, type(self).__name__
         n = int(qh.shape[0])
         b = buffers if buffers is not None else {}
         if b.get("th_n") != n:
@@ -103,14 +112,14 @@ class TransHSweep:
         if n == 0:
             return dict(counts=b["counts"], truth=b["truth"], padding=1.0)
         if filt is not None and len(filt) != 5:
-            raise ValueError("TransHSweep takes filter groups (FilterIndex.groups)")
+            raise ValueError(f"{who} takes filter groups (FilterIndex.groups)")
         if plan is None:
             plan = plan_tiles(qr.cpu().numpy())
         if b.get("th_plan") is not plan:
             slot = np.full(self.n_rel, -1, np.int32)
             used = plan["used"]
             if len(used) and (used.min() < 0 or used.max() >= self.n_rel):
-                raise ValueError("TransHSweep: a query's relation is outside the relation table")
+                raise ValueError(f"{who}: a query's relation is outside the relation table")
             slot[used] = np.arange(len(used), dtype=np.int32)
             to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
             b["th_dev"] = tuple(to(a) for a in (plan["perm"], plan["tiles"], used, slot))
@@ -122,18 +131,17 @@ class TransHSweep:
         if filt is not None:
             gqo, gq, off, ids, entry_q = filt
             n_groups, n_entries = int(gqo.shape[0]) - 1, int(ids.shape[0])
-        need = int(_lib.lib().mmre_transh_workspace(self.n_ent, self.n_rel, int(s.dim), n_tiles, n_used, n_entries))
+        need = int(self._workspace(n_tiles, n_used, n_entries))
         wk = b.get("th_work")
         if wk is None or wk.numel() < need:
             wk = b["th_work"] = torch.empty(need, dtype=torch.uint8, device=dev)
         th, tt = (None, None) if type_masks is None else type_masks
         if events is not None:
             events[0].record()
-        call("mmre_transh_evaluate", self.model_id, int(bool(s.norm_flag)), int(s.pred_kind), float(s.margin),
-             ptr(self._ent), ptr(self._rel), ptr(self._nv), self.n_ent, self.n_rel, int(s.dim), ptr(qh), ptr(qr),
-             ptr(qt), ptr(qmode), n, ptr(perm), ptr(tiles), n_tiles, ptr(used), n_used, ptr(slot), ptr(gqo), ptr(gq),
-             n_groups, ptr(off), ptr(ids) if n_entries else None, ptr(entry_q) if n_entries else None, n_entries,
-             ptr(th), ptr(tt), ptr(b["counts"]), ptr(b["truth"]), ptr(wk), int(wk.numel()), stream_ptr(dev))
+        self._evaluate(ptr(qh), ptr(qr), ptr(qt), ptr(qmode), n, ptr(perm), ptr(tiles), n_tiles, ptr(used), n_used,
+                       ptr(slot), ptr(gqo), ptr(gq), n_groups, ptr(off), ptr(ids) if n_entries else None,
+                       ptr(entry_q) if n_entries else None, n_entries, ptr(th), ptr(tt), ptr(b["counts"]),
+                       ptr(b["truth"]), ptr(wk), int(wk.numel()), stream_ptr(dev))
         if events is not None:
             events[1].record()
         return dict(counts=b["counts"], truth=b["truth"], padding=plan["padding"])

@@ -130,10 +130,15 @@ def evaluate_triple_classification(spec: ScoreSpec, test_h, test_r, test_t, trai
     """The whole task in one enqueued call (mmre_tc_evaluate): negatives of the test triples from
     thread 0's `seed_state`, both prediction arrays, and the best threshold (or the counts at a given
     one). Returns dict(accuracy, threshold, P, A, n_nan, n_pos, n_neg, neg_h, neg_t, pos_scores,
-    neg_scores (numpy), seed_state_after). A TransH spec composes the same result from
-    classification_negatives, mmre.transh.score_rows and best_threshold / accuracy_at."""
+    neg_scores (numpy), seed_state_after). A TransH or TransD spec composes the same result from
+    classification_negatives, its engine's score_rows (mmre.transh / mmre.transd) and
+    best_threshold / accuracy_at."""
     if spec.model in ("transh", "transh_l2"):
-        return _evaluate_transh(spec, test_h, test_r, test_t, train_index, seed_state, threshold)
+        from .transh import score_rows
+        return _evaluate_rows(score_rows, spec, test_h, test_r, test_t, train_index, seed_state, threshold)
+    if spec.model in ("transd", "transd_l2"):
+        from .transd import score_rows
+        return _evaluate_rows(score_rows, spec, test_h, test_r, test_t, train_index, seed_state, threshold)
     ent, rel, ent_im, rel_im = _tables(spec)
     dev = ent.device
     d = device_index(train_index, dev)
@@ -162,8 +167,8 @@ def evaluate_triple_classification(spec: ScoreSpec, test_h, test_r, test_t, trai
     return res
 
 
-def _evaluate_transh(spec, test_h, test_r, test_t, train_index, seed_state, threshold):
-    from .transh import score_rows
+def _evaluate_rows(score_rows, spec, test_h, test_r, test_t, train_index, seed_state, threshold):
+    """The task composed around a model's row kernel: score_rows(spec, h, r, t) -> predict values."""
     _lib.require_cuda(spec.ent)
     dev = spec.ent.device
     h, r, t = (_i64(x, dev) for x in (test_h, test_r, test_t))
