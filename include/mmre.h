@@ -435,6 +435,46 @@ int mmre_transd_score_rows(int model, int norm_flag, int pred_kind, float margin
                            const int64_t* d_r, const int64_t* d_t, int64_t n_rows, int head_batch, float* d_out,
                            void* stream);
 
+/* ---- TransD negative-sampling training (csrc/transh_train.hip) ----
+ * The mmre_transh_ns_* contract for TransD.py:94-147: model(data) in 'normal' mode for the
+ * B (1 + K) rows of [pos | neg_1 | ... | neg_K], MarginLoss(loss_margin, adv_temperature) +
+ * regul_rate (mean h^2 + mean t^2 + mean r^2 + mean h_p^2 + mean t_p^2 + mean r_p^2) / 6, entity
+ * means over N dim_e elements and relation means over N dim_r. Tables: d_ent and d_ent_transfer
+ * (n_ent, dim_e), d_rel and d_rel_transfer (n_rel, dim_r). model: MMRE_TRANSD_L1 / MMRE_TRANSD_L2
+ * only (anything else: MMRE_ERR_MODEL; mmre_ns_* and mmre_transh_ns_* keep refusing these two).
+ * The arithmetic is the "TransD training chain" of DESIGN.md §3: a score agrees with
+ * mmre_transd_score_rows to rounding, not bit for bit. Shapes: 1 <= dim_r <= dim_e <= 512 and
+ * 1 <= neg <= 512 (mmre_transd_ns_supported asks first); n_ent, n_rel and batch as for TransH;
+ * else MMRE_ERR_SHAPE. Checks run before the first launch: model, null pointers (MMRE_ERR_ARG),
+ * shape. Every call only enqueues on `stream`. Ids are trusted to lie inside their tables. */
+
+/* 1 when the kernels exist for (model, dim_e, dim_r, neg), else 0. */
+int mmre_transd_ns_supported(int model, int dim_e, int dim_r, int64_t neg);
+
+/* Floats of d_work for both calls below; -1 for a shape they answer MMRE_ERR_SHAPE to. Monotone in
+ * every argument. It reserves 4 dim_e + 2 dim_r floats of records for each of the B (1 + K) rows. */
+int64_t mmre_transd_ns_workspace(int64_t batch, int64_t neg, int64_t n_ent, int64_t n_rel, int dim_e, int dim_r);
+
+/* d_score[B (1 + K)] <- forward values, d_loss[0] <- the loss, the same bits every run. Two launches. */
+int mmre_transd_ns_forward(int model, int norm_flag, float model_margin, int use_model_margin,
+                           const float* d_ent, const float* d_ent_transfer, const float* d_rel,
+                           const float* d_rel_transfer, int64_t n_ent, int64_t n_rel, int dim_e, int dim_r,
+                           const int64_t* d_h, const int64_t* d_t, const int64_t* d_r, int64_t batch, int64_t neg,
+                           float loss_margin, float adv_temperature, float regul_rate, float* d_score,
+                           float* d_loss, float* d_work, void* stream);
+
+/* The four gradient tables <- d(loss)/d(table) times d_grad_loss[0]: every row written (untouched
+ * rows exactly 0), no float atomics, the same bits every run. d_score: what the forward wrote for
+ * the same arguments. lr != 0: the owner of a touched row also applies p <- fma(-lr, g, p) in place
+ * to all four tables, bit-identical to backward() + SGD.step(); lr == 0: the tables are only read. */
+int mmre_transd_ns_grad(int model, int norm_flag, float model_margin, int use_model_margin, float* d_ent,
+                        float* d_ent_transfer, float* d_rel, float* d_rel_transfer, int64_t n_ent, int64_t n_rel,
+                        int dim_e, int dim_r, const int64_t* d_h, const int64_t* d_t, const int64_t* d_r,
+                        int64_t batch, int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
+                        const float* d_score, const float* d_grad_loss, float* d_grad_ent,
+                        float* d_grad_ent_transfer, float* d_grad_rel, float* d_grad_rel_transfer, float* d_work,
+                        float lr, void* stream);
+
 /* ====================================================================== *
  *  Relation prediction: every test pair (h, t) against every relation.   *
  *  Replaces, per evaluation, the loop getRelBatch (Test.h:55-62) +        *

@@ -1,6 +1,8 @@
 // transh_train.hip -- TransH negative-sampling training (OpenKE TransH.py:52-107 in 'normal' mode
 // under strategy/NegativeSampling.py:23-32 + MarginLoss.py:24-28): the fused loss and its
 // gradient into three dense tables (ent, rel, norm_vector), no float atomics, DESIGN.md §10h.
+// Below it, the same step for TransD (four tables, six rows per triple) on the same index, scan,
+// fill, relation and SGD kernels: the section headed "TransD".
 //
 // Arithmetic (the "TransH training chain"): f32, -ffp-contract=off, a row's element
 // lane + 64 c in slot c, every sum a lane partial in increasing c then wave_sum (row_chain.h).
@@ -680,6 +682,519 @@ int th_dispatch(int model, int norm_flag, int dim, F&& f) {
   });
 }
 
+// ==========================================================================================
+// TransD (OpenKE TransD.py:94-147 in 'normal' mode): the same step for a model with two rows per
+// entity (e, e_p of dim_e) and two per relation (r, r_p of dim_r <= dim_e). The "TransD training
+// chain" (DESIGN.md §3), the conventions above, one NC = nc_for_dim(dim_e): relation-side rows are
+// loaded zero past dim_r, so every vector of a row has dim_e's register shape.
+//   s_e = e . e_p   u_e = e[:dim_r] + s_e r_p   u^_e = u_e / max(|u_e|, 1e-12)      (e = h, t)
+//   norm_flag: u^_e <- u^_e / max(|u^_e|, 1e-12), r^ = r / max(|r|, 1e-12); else r^ = r
+//   x = (u^_h + r^) - u^_t     s, forward and gx as TransH's
+// Backward, v = +-gx:
+//   norm_flag: v <- (v - u^ (u^ . v)) / |u^|, v / 1e-12 where clamped; du = v / max(|u|, 1e-12)
+//              (where |u| > 1e-12 v is already normal to u^: the first normalise's projection
+//              is collapsed; where it is clamped that normalise is linear)
+//   else:      du = (v - u^ (u^ . v)) / |u|, v / 1e-12 where clamped
+//   q = du . r_p   de = du (its first dim_r elements; it is 0 past them) + q e_p   de_p = q e
+//   dr_p = s_h du_h + s_t du_t   dr as TransH's
+// Records: row i owns 4 dim_e + 2 dim_r floats, [dh | dh_p | dt | dt_p | dr | dr_p]: entity slot
+// 4 i + (0 | 1) of k_th_fill is the pair at (slot & 3) 2 dim_e of row slot >> 2. Keys, the inverted
+// index, the relation segments and k_th_rel (rows of dim_r) are TransH's, unchanged.
+// ==========================================================================================
+struct TDArgs {
+  THArgs A;  // ent, rel, nv = rel_transfer, dim = dim_e
+  const float* ept;
+  int dim_r;
+};
+
+__host__ __device__ inline int64_t td_row_floats(int dim_e, int dim_r) { return 4 * (int64_t)dim_e + 2 * (int64_t)dim_r; }
+
+// THWork for TransD: part holds hinge, sq h, t, r, h_p, t_p, r_p (7 of 8); prel pairs of dim_r
+THWork td_carve(float* base, int64_t B, int64_t K, int64_t n_ent, int64_t n_rel, int dim_e, int dim_r) {
+  const int64_t N = B * (1 + K);
+  THWork W;
+  W.n_seg = (N + TH_SEG - 1) / TH_SEG;
+  int64_t o = 0;
+  auto take = [&](int64_t n_floats) {
+    const int64_t at = o;
+    o += round_up(n_floats, 2);
+    return base + at;
+  };
+  W.elist = reinterpret_cast<int64_t*>(take(4 * N));
+  W.eoff = reinterpret_cast<int64_t*>(take(2 * (n_ent + 1)));
+  W.part = take(8 * B);
+  W.coef = take(N);
+  W.rkey = reinterpret_cast<int32_t*>(take(N));
+  W.ekey = reinterpret_cast<int32_t*>(take(2 * N));
+  W.ecount = reinterpret_cast<int32_t*>(take(n_ent));
+  W.ecur = reinterpret_cast<int32_t*>(take(n_ent));
+  W.flag = reinterpret_cast<int32_t*>(take(n_rel * W.n_seg));
+  W.prel = take(n_rel * W.n_seg * 2 * dim_r);
+  W.rec = take(N * td_row_floats(dim_e, dim_r));
+  W.floats = o;
+  return W;
+}
+
+// A relation's side of a row: raw r and r_p (0 past dim_r), r^ and |r| (1 without norm_flag).
+template <int NC>
+struct TDRel {
+  float r[NC], rp[NC], rh[NC];
+  float nr;
+};
+// An entity transferred by a relation: raw e and e_p, the final u^, s = e . e_p, |u| and the
+// second normalise's |u^| (1 without norm_flag).
+template <int NC>
+struct TDEnt {
+  float e[NC], ep[NC], uh[NC];
+  float s, nu, n2;
+};
+
+template <int NC, bool NORM>
+__device__ __forceinline__ void td_load_rel(const TDArgs& D, int64_t r, int lane, TDRel<NC>& R) {
+  vload(R.r, D.A.rel + r * D.dim_r, D.dim_r, lane);
+  vload(R.rp, D.A.nv + r * D.dim_r, D.dim_r, lane);
+  R.nr = 1.0f;
+  if constexpr (NORM) R.nr = sqrtf(wave_sum(vsq(R.r)));
+  const float cr = fmaxf(R.nr, TH_EPS);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) R.rh[c] = NORM ? R.r[c] / cr : R.r[c];
+}
+
+template <int NC, bool NORM>
+__device__ __forceinline__ void td_load_ent(const TDArgs& D, int64_t e, const TDRel<NC>& R, int lane, TDEnt<NC>& E) {
+  vload(E.e, D.A.ent + e * D.A.dim, D.A.dim, lane);
+  vload(E.ep, D.ept + e * D.A.dim, D.A.dim, lane);
+  E.s = vdot(E.e, E.ep);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) E.uh[c] = (lane + c * kWave < D.dim_r ? E.e[c] : 0.0f) + E.s * R.rp[c];
+  E.nu = sqrtf(wave_sum(vsq(E.uh)));
+  const float cu = fmaxf(E.nu, TH_EPS);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) E.uh[c] = E.uh[c] / cu;
+  E.n2 = 1.0f;
+  if constexpr (NORM) {
+    E.n2 = sqrtf(wave_sum(vsq(E.uh)));
+    const float c2 = fmaxf(E.n2, TH_EPS);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) E.uh[c] = E.uh[c] / c2;
+  }
+}
+
+template <int NC, bool L2>
+__device__ __forceinline__ float td_row_x(const TDEnt<NC>& H, const TDRel<NC>& R, const TDEnt<NC>& T, float (&x)[NC]) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    x[c] = (H.uh[c] + R.rh[c]) - T.uh[c];
+    acc += L2 ? x[c] * x[c] : fabsf(x[c]);
+  }
+  const float s = wave_sum(acc);
+  return L2 ? sqrtf(s) : s;
+}
+
+template <int NC>
+struct TDRow {
+  TDRel<NC> R;
+  TDEnt<NC> H, T;
+  int64_t h, t, r;
+  bool same_r, same_h, same_t;
+};
+template <int NC, bool NORM>
+__device__ __forceinline__ void td_load_row(const TDArgs& D, int64_t i, int lane, int64_t pr, int64_t ph, int64_t pt,
+                                            const TDRel<NC>& PR, const TDEnt<NC>& PH, const TDEnt<NC>& PT,
+                                            TDRow<NC>& X) {
+  X.h = D.A.h[i]; X.t = D.A.t[i]; X.r = D.A.r[i];
+  X.same_r = X.r == pr;
+  X.same_h = X.same_r && X.h == ph;
+  X.same_t = X.same_r && X.t == pt;
+  if (X.same_r) X.R = PR; else td_load_rel<NC, NORM>(D, X.r, lane, X.R);
+  if (X.same_h) X.H = PH; else td_load_ent<NC, NORM>(D, X.h, X.R, lane, X.H);
+  if (X.same_t) X.T = PT; else td_load_ent<NC, NORM>(D, X.t, X.R, lane, X.T);
+}
+
+template <int NC, bool L2, bool NORM>
+__global__ __launch_bounds__(256) void k_tdt_forward(TDArgs D, float* __restrict__ score, float* __restrict__ part) {
+  __shared__ float s_sc[TH_MAXK + 1];
+  __shared__ float s_sq[TH_WPP][6];
+  const THArgs& A = D.A;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t b = blockIdx.x;
+  const int64_t pr = A.r[b], ph = A.h[b], pt = A.t[b];
+  TDRel<NC> PR;
+  TDEnt<NC> PH, PT;
+  td_load_rel<NC, NORM>(D, pr, lane, PR);
+  td_load_ent<NC, NORM>(D, ph, PR, lane, PH);
+  td_load_ent<NC, NORM>(D, pt, PR, lane, PT);
+  float sq[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  for (int64_t j = w; j <= A.K; j += TH_WPP) {
+    const int64_t i = b + j * A.B;
+    TDRow<NC> X;
+    td_load_row<NC, NORM>(D, i, lane, pr, ph, pt, PR, PH, PT, X);
+    float x[NC];
+    const float s = td_row_x<NC, L2>(X.H, X.R, X.T, x);
+    const float f = A.use_model_margin ? A.model_margin - s : s;
+    if (lane == 0) { score[i] = f; s_sc[j] = f; }
+    if (A.regul_rate != 0.0f) {
+      sq[0] += vsq(X.H.e); sq[1] += vsq(X.T.e); sq[2] += vsq(X.R.r);
+      sq[3] += vsq(X.H.ep); sq[4] += vsq(X.T.ep); sq[5] += vsq(X.R.rp);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    const float v = A.regul_rate != 0.0f ? wave_sum(sq[q]) : 0.0f;
+    if (lane == 0) s_sq[w][q] = v;
+  }
+  __syncthreads();
+  if (w != 0) return;
+  // the positive's hinge partial, as k_th_forward forms it
+  const float p = s_sc[0];
+  float mx = -INFINITY, den = 0.0f;
+  if (A.adv_t > 0.0f) {
+    for (int64_t j = lane; j < A.K; j += kWave) mx = fmaxf(mx, -s_sc[1 + j] * A.adv_t);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s));
+    for (int64_t j = lane; j < A.K; j += kWave) den += expf(-s_sc[1 + j] * A.adv_t - mx);
+    den = wave_sum(den);
+  }
+  float loss = 0.0f;
+  for (int64_t j = lane; j < A.K; j += kWave) {
+    const float n = s_sc[1 + j];
+    const float hinge = fmaxf(p - n, -A.loss_margin);
+    loss += A.adv_t > 0.0f ? expf(-n * A.adv_t - mx) / den * hinge : hinge;
+  }
+  loss = wave_sum(loss);
+  if (lane == 0) {
+    float* o = part + b * 8;
+    o[0] = loss;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) o[1 + q] = (s_sq[0][q] + s_sq[1][q]) + (s_sq[2][q] + s_sq[3][q]);
+  }
+}
+
+// k_th_reduce for seven partials: the hinge and the six sums of squares (entity rows have dim_e
+// elements, relation rows dim_r).
+__global__ __launch_bounds__(256) void k_tdt_reduce(TDArgs D, const float* __restrict__ part, float* __restrict__ loss) {
+  __shared__ double red[7][4];
+  const THArgs& A = D.A;
+  double acc[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int64_t b = threadIdx.x; b < A.B; b += 256) {
+#pragma unroll
+    for (int q = 0; q < 7; ++q) acc[q] += (double)part[b * 8 + q];
+  }
+#pragma unroll
+  for (int q = 0; q < 7; ++q) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) acc[q] += __shfl_xor(acc[q], s);
+  }
+  if ((threadIdx.x & 63) == 0)
+    for (int q = 0; q < 7; ++q) red[q][threadIdx.x >> 6] = acc[q];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double t[7];
+  for (int q = 0; q < 7; ++q) t[q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
+  const double Bd = (double)A.B, Kd = (double)A.K;
+  double l = A.adv_t > 0.0f ? t[0] / Bd : t[0] / (Bd * Kd);
+  l += (double)A.loss_margin;
+  if (A.regul_rate != 0.0f) {
+    const double ne = Bd * (1.0 + Kd) * (double)A.dim, nr = Bd * (1.0 + Kd) * (double)D.dim_r;
+    l += (double)A.regul_rate * ((t[1] / ne + t[2] / ne + t[3] / nr + t[4] / ne + t[5] / ne + t[6] / nr) / 6.0);
+  }
+  loss[0] = (float)l;
+}
+
+// d(score)/d(u^) = v through the normalises to du, then to the entity's two rows (section header).
+template <int NC, bool NORM, bool NEG>
+__device__ __forceinline__ void td_ent_grad(const TDEnt<NC>& E, const TDRel<NC>& R, const float (&gx)[NC],
+                                            float (&du)[NC], float (&dE)[NC], float (&dEp)[NC]) {
+  float a = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) a += E.uh[c] * (NEG ? -gx[c] : gx[c]);
+  a = wave_sum(a);
+  const float cu = fmaxf(E.nu, TH_EPS);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const float v = NEG ? -gx[c] : gx[c];
+    if constexpr (NORM) {
+      const float y = E.n2 > TH_EPS ? (v - E.uh[c] * a) / E.n2 : v / TH_EPS;
+      du[c] = y / cu;
+    } else {
+      du[c] = E.nu > TH_EPS ? (v - E.uh[c] * a) / E.nu : v / TH_EPS;
+    }
+  }
+  const float q = vdot(du, R.rp);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    dE[c] = du[c] + q * E.ep[c];
+    dEp[c] = q * E.e[c];
+  }
+}
+
+// The exact derivative of one row's score times g with respect to its six raw rows:
+// dv[0 .. 5] = dh, dt, dh_p, dt_p, dr, dr_p.
+template <int NC, bool L2, bool NORM>
+__device__ __forceinline__ void td_row_grad(const TDRow<NC>& X, float g, float (&dv)[6][NC]) {
+  float x[NC], gx[NC];
+  const float s = td_row_x<NC, L2>(X.H, X.R, X.T, x);
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    gx[c] = L2 ? (s > 0.0f ? g * x[c] / s : 0.0f) : g * (float)((x[c] > 0.0f) - (x[c] < 0.0f));
+  if constexpr (NORM) {
+    float e = 0.0f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) e += X.R.rh[c] * gx[c];
+    e = wave_sum(e);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) dv[4][c] = X.R.nr > TH_EPS ? (gx[c] - X.R.rh[c] * e) / X.R.nr : gx[c] / TH_EPS;
+  } else {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) dv[4][c] = gx[c];
+  }
+  float duh[NC], dut[NC];
+  td_ent_grad<NC, NORM, false>(X.H, X.R, gx, duh, dv[0], dv[2]);
+  td_ent_grad<NC, NORM, true>(X.T, X.R, gx, dut, dv[1], dv[3]);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) dv[5][c] = X.H.s * duh[c] + X.T.s * dut[c];
+}
+
+// slot q (h, t, h_p, t_p, r, r_p) of a row's record: its offset, and whose sharing decides it
+__device__ __forceinline__ int64_t td_slot_off(int q, int de, int dr) {
+  return q < 4 ? (int64_t)((q & 1) * 2 + (q >> 1)) * de : 4 * (int64_t)de + (q - 4) * dr;
+}
+__device__ __forceinline__ int td_slot_pair(int q) { return q < 4 ? (q & 1) : 2; }
+
+template <int NC, bool L2, bool NORM>
+__global__ __launch_bounds__(256) void k_tdt_records(TDArgs D, const float* __restrict__ coef,
+                                                      const float* __restrict__ grad_loss, float reg_ent,
+                                                      float reg_rel, THWork W) {
+  __shared__ float s_acc[6][TH_WPP][NC * kWave];
+  __shared__ int s_cnt[TH_WPP][3];
+  const THArgs& A = D.A;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t b = blockIdx.x;
+  const int de = A.dim, dr = D.dim_r;
+  const int64_t stride = td_row_floats(de, dr);
+  const float gl = grad_loss[0];
+  const float rege = reg_ent * gl, regr = reg_rel * gl;  // the regulariser's weight per gathered row
+  const int64_t pr = A.r[b], ph = A.h[b], pt = A.t[b];
+  TDRel<NC> PR;
+  TDEnt<NC> PH, PT;
+  td_load_rel<NC, NORM>(D, pr, lane, PR);
+  td_load_ent<NC, NORM>(D, ph, PR, lane, PH);
+  td_load_ent<NC, NORM>(D, pt, PR, lane, PT);
+  // This wave's sums for the positive's six rows, in j order, and how many rows each pair sums
+  // (h, t, r). The regulariser joins a shared row once, at the end, as in k_th_records.
+  float acc[6][NC];
+#pragma unroll
+  for (int q = 0; q < 6; ++q)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[q][c] = 0.0f;
+  int cnt[3] = {0, 0, 0};
+  for (int64_t j = w; j <= A.K; j += TH_WPP) {
+    const int64_t i = b + j * A.B;
+    float g = coef[i];
+    const bool files = g != 0.0f || rege != 0.0f || regr != 0.0f;  // else the row adds nothing anywhere
+    int32_t kh = -1, kt = -1, kr = -1;
+    if (files) {
+      if (A.use_model_margin) g = -g;  // forward = m - s
+      TDRow<NC> X;
+      td_load_row<NC, NORM>(D, i, lane, pr, ph, pt, PR, PH, PT, X);
+      float dv[6][NC];
+      td_row_grad<NC, L2, NORM>(X, g, dv);
+      float* __restrict__ row = W.rec + i * stride;
+      auto put = [&](int q, bool shared, float (&v)[NC], const float (&raw)[NC]) {
+        if (shared) {
+#pragma unroll
+          for (int c = 0; c < NC; ++c) acc[q][c] += v[c];
+        } else {
+          const float reg = q < 4 ? rege : regr;
+#pragma unroll
+          for (int c = 0; c < NC; ++c) v[c] += reg * raw[c];
+          vstore(row + td_slot_off(q, de, dr), v, q < 4 ? de : dr, lane);
+        }
+      };
+      put(0, X.same_h, dv[0], X.H.e);
+      put(2, X.same_h, dv[2], X.H.ep);
+      put(1, X.same_t, dv[1], X.T.e);
+      put(3, X.same_t, dv[3], X.T.ep);
+      put(4, X.same_r, dv[4], X.R.r);
+      put(5, X.same_r, dv[5], X.R.rp);
+      cnt[0] += X.same_h; cnt[1] += X.same_t; cnt[2] += X.same_r;
+      if (!X.same_h) kh = (int32_t)X.h;
+      if (!X.same_t) kt = (int32_t)X.t;
+      if (!X.same_r) kr = (int32_t)X.r;
+    }
+    if (j > 0 && lane == 0) {  // (row b's keys: below, once the positive's slots are known live)
+      W.ekey[2 * i] = kh;
+      W.ekey[2 * i + 1] = kt;
+      W.rkey[i] = kr;
+      if (kh >= 0) atomicAdd(&W.ecount[kh], 1);
+      if (kt >= 0) atomicAdd(&W.ecount[kt], 1);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) s_acc[q][w][lane + c * kWave] = acc[q][c];
+  }
+  if (lane == 0) { s_cnt[w][0] = cnt[0]; s_cnt[w][1] = cnt[1]; s_cnt[w][2] = cnt[2]; }
+  __syncthreads();
+  // wave w adds the four waves' sums of slots w and w + 4 in wave order and writes the positive's records
+  float* __restrict__ row = W.rec + b * stride;
+  for (int q = w; q < 6; q += TH_WPP) {
+    const int p = td_slot_pair(q);
+    const int rows = (s_cnt[0][p] + s_cnt[1][p]) + (s_cnt[2][p] + s_cnt[3][p]);
+    if (rows == 0) continue;
+    const float rw = (q < 4 ? rege : regr) * (float)rows;
+    float v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int k = lane + c * kWave;
+      const float raw = q == 0 ? PH.e[c] : q == 1 ? PT.e[c] : q == 2 ? PH.ep[c] : q == 3 ? PT.ep[c]
+                      : q == 4 ? PR.r[c] : PR.rp[c];
+      v[c] = (((s_acc[q][0][k] + s_acc[q][1][k]) + s_acc[q][2][k]) + s_acc[q][3][k]) + rw * raw;
+    }
+    vstore(row + td_slot_off(q, de, dr), v, q < 4 ? de : dr, lane);
+  }
+  if (w == 0 && lane == 0) {
+    bool any[3];
+    for (int p = 0; p < 3; ++p) any[p] = (s_cnt[0][p] + s_cnt[1][p]) + (s_cnt[2][p] + s_cnt[3][p]) > 0;
+    W.ekey[2 * b] = any[0] ? (int32_t)ph : -1;
+    W.ekey[2 * b + 1] = any[1] ? (int32_t)pt : -1;
+    W.rkey[b] = any[2] ? (int32_t)pr : -1;
+    if (any[0]) atomicAdd(&W.ecount[ph], 1);
+    if (any[1]) atomicAdd(&W.ecount[pt], 1);
+  }
+}
+
+// k_th_owner for record pairs. Workgroups [0, ent_blocks): one wave per entity sums its list's
+// (e, e_p) pairs in increasing slot id and writes both rows. The rest: one wave per (relation,
+// segment) sums the matching (r, r_p) pairs into a partial for k_th_rel. (The list ordering is
+// k_th_owner's, repeated: factored into a helper both call, k_th_owner compiles to other code.)
+template <int NC>
+__global__ __launch_bounds__(256) void k_tdt_owner(TDArgs D, THWork W, int64_t ent_blocks, float* ent, float* ept,
+                                                    float lr, float* __restrict__ grad_ent,
+                                                    float* __restrict__ grad_ept) {
+  __shared__ int64_t s_ord[4][kWave];
+  const THArgs& A = D.A;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int de = A.dim, dr = D.dim_r;
+  const int64_t stride = td_row_floats(de, dr);
+  const int64_t N = A.B * (1 + A.K);
+  constexpr int64_t kNone = INT64_MAX;
+  if ((int64_t)blockIdx.x < ent_blocks) {
+    const int64_t e = (int64_t)blockIdx.x * 4 + w;
+    if (e >= A.n_ent) return;
+    const int64_t off = W.eoff[e], L = W.eoff[e + 1] - off;
+    const int64_t* __restrict__ list = W.elist + off;
+    float g[NC], gp[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) g[c] = gp[c] = 0.0f;
+    auto add = [&](int64_t slot) {
+      const float* __restrict__ pair = W.rec + (slot >> 2) * stride + (slot & 3) * 2 * (int64_t)de;
+      float a[NC], c2[NC];
+      vload(a, pair, de, lane);
+      vload(c2, pair + de, de, lane);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) { g[c] += a[c]; gp[c] += c2[c]; }
+    };
+    if (L <= kWave) {  // rank the slot ids (they are distinct), then sum in rank order
+      const int64_t x = lane < L ? list[lane] : kNone;
+      int rank = 0;
+      for (int m = 0; m < (int)L; ++m) rank += __shfl(x, m) < x ? 1 : 0;
+      if (lane < L) s_ord[w][rank] = x;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int k = 0; k < (int)L; ++k) add(s_ord[w][k]);
+    } else {  // repeated selection of the next larger slot id
+      const bool in_regs = L <= (int64_t)TH_REGL * kWave;
+      int64_t mine[TH_REGL];
+#pragma unroll
+      for (int u = 0; u < TH_REGL; ++u) {
+        const int64_t at = lane + (int64_t)u * kWave;
+        mine[u] = in_regs && at < L ? list[at] : kNone;
+      }
+      int64_t cur = -1;
+      for (int64_t k = 0; k < L; ++k) {
+        int64_t best = kNone;
+        if (in_regs) {
+#pragma unroll
+          for (int u = 0; u < TH_REGL; ++u) best = (mine[u] > cur && mine[u] < best) ? mine[u] : best;
+        } else {
+          for (int64_t at = lane; at < L; at += kWave) {
+            const int64_t x = list[at];
+            best = (x > cur && x < best) ? x : best;
+          }
+        }
+        cur = wave_min(best);
+        add(cur);
+      }
+    }
+    owner_write(g, grad_ent + e * de, ent + e * de, lr, L > 0, de, lane);
+    owner_write(gp, grad_ept + e * de, ept + e * de, lr, L > 0, de, lane);
+    return;
+  }
+  // relation side: the segment's rows of relation r, in row order
+  const int64_t item = ((int64_t)blockIdx.x - ent_blocks) * 4 + w;
+  if (item >= A.n_rel * W.n_seg) return;
+  const int64_t r = item / W.n_seg, seg = item % W.n_seg;
+  const int64_t lo = seg * TH_SEG, hi = lo + TH_SEG < N ? lo + TH_SEG : N;
+  float gr[NC], gw[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) gr[c] = gw[c] = 0.0f;
+  bool found = false;
+  for (int64_t base = lo; base < hi; base += kWave) {
+    const int64_t i = base + lane;
+    const bool hit = i < hi && (int64_t)W.rkey[i] == r;
+    uint64_t m = __ballot(hit);
+    found = found || m != 0;
+    while (m) {
+      const int64_t row = base + __builtin_ctzll(m);
+      m &= m - 1;
+      const float* __restrict__ pair = W.rec + row * stride + 4 * (int64_t)de;
+      float a[NC], c2[NC];
+      vload(a, pair, dr, lane);
+      vload(c2, pair + dr, dr, lane);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) { gr[c] += a[c]; gw[c] += c2[c]; }
+    }
+  }
+  if (lane == 0) W.flag[item] = found ? 1 : 0;
+  if (found) {
+    vstore(W.prel + item * 2 * dr, gr, dr, lane);
+    vstore(W.prel + (item * 2 + 1) * dr, gw, dr, lane);
+  }
+}
+
+bool td_train_model(int model) { return model == MMRE_TRANSD_L1 || model == MMRE_TRANSD_L2; }
+bool td_train_shape(int dim_e, int dim_r, int64_t neg) {
+  return dim_r >= 1 && dim_r <= dim_e && th_train_shape(dim_e, neg);
+}
+
+TDArgs td_args(const float* ent, const float* ept, const float* rel, const float* rpt, int64_t n_ent, int64_t n_rel,
+               int dim_e, int dim_r, const int64_t* h, const int64_t* t, const int64_t* r, int64_t batch, int64_t neg,
+               float model_margin, int use_model_margin, float loss_margin, float adv_t, float regul_rate) {
+  return TDArgs{THArgs{ent, rel, rpt, n_ent, n_rel, dim_e, h, t, r, batch, neg, model_margin, use_model_margin,
+                       loss_margin, adv_t, regul_rate},
+                ept, dim_r};
+}
+
+// f(NC, L2, NORM) for the model's instance; NC is dim_e's
+template <class F>
+int td_dispatch(int model, int norm_flag, int dim_e, F&& f) {
+  return with_nc<8>(nc_for_dim(dim_e, 8), [&](auto nc) {
+    with_bool(model == MMRE_TRANSD_L2, [&](auto l2) {
+      return with_bool(norm_flag != 0, [&](auto nm) {
+        f(nc, l2, nm);
+        return 0;
+      });
+    });
+  });
+}
+
 }  // namespace
 }  // namespace mmre
 
@@ -758,5 +1273,89 @@ extern "C" int mmre_transh_ns_grad(int model, int norm_flag, float model_margin,
   return with_nc<8>(nc_for_dim(dim, 8), [&](auto nc) {
     hipLaunchKernelGGL((k_th_rel<decltype(nc)::value>), dim3((unsigned)((n_rel + 3) / 4)), dim3(256), 0, st, A, W, d_rel, d_norm,
                        lr, d_grad_rel, d_grad_norm);
+  });
+}
+
+// ---- TransD ---------------------------------------------------------------------------------
+extern "C" int mmre_transd_ns_supported(int model, int dim_e, int dim_r, int64_t neg) {
+  return td_train_model(model) && td_train_shape(dim_e, dim_r, neg) ? 1 : 0;
+}
+
+extern "C" int64_t mmre_transd_ns_workspace(int64_t batch, int64_t neg, int64_t n_ent, int64_t n_rel, int dim_e,
+                                            int dim_r) {
+  if (!td_train_shape(dim_e, dim_r, neg) || !th_train_sizes(batch, neg, n_ent, n_rel)) return -1;
+  return td_carve(nullptr, batch, neg, n_ent, n_rel, dim_e, dim_r).floats;
+}
+
+extern "C" int mmre_transd_ns_forward(int model, int norm_flag, float model_margin, int use_model_margin,
+                                      const float* d_ent, const float* d_ent_transfer, const float* d_rel,
+                                      const float* d_rel_transfer, int64_t n_ent, int64_t n_rel, int dim_e, int dim_r,
+                                      const int64_t* d_h, const int64_t* d_t, const int64_t* d_r, int64_t batch,
+                                      int64_t neg, float loss_margin, float adv_temperature, float regul_rate,
+                                      float* d_score, float* d_loss, float* d_work, void* stream) {
+  if (!td_train_model(model)) return MMRE_ERR_MODEL;
+  if (!d_ent || !d_ent_transfer || !d_rel || !d_rel_transfer || !d_h || !d_t || !d_r || !d_score || !d_loss || !d_work)
+    return MMRE_ERR_ARG;
+  if (!td_train_shape(dim_e, dim_r, neg) || !th_train_sizes(batch, neg, n_ent, n_rel)) return MMRE_ERR_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  const TDArgs D = td_args(d_ent, d_ent_transfer, d_rel, d_rel_transfer, n_ent, n_rel, dim_e, dim_r, d_h, d_t, d_r,
+                           batch, neg, model_margin, use_model_margin, loss_margin, adv_temperature, regul_rate);
+  const THWork W = td_carve(d_work, batch, neg, n_ent, n_rel, dim_e, dim_r);
+  const int rc = td_dispatch(model, norm_flag, dim_e, [&](auto nc, auto l2, auto nm) {
+    hipLaunchKernelGGL((k_tdt_forward<decltype(nc)::value, decltype(l2)::value, decltype(nm)::value>), dim3((unsigned)batch), dim3(256), 0, st, D,
+                       d_score, W.part);
+  });
+  if (rc != MMRE_OK) return rc;
+  hipLaunchKernelGGL(k_tdt_reduce, dim3(1), dim3(256), 0, st, D, W.part, d_loss);
+  MMRE_CHECK_LAUNCH();
+  return MMRE_OK;
+}
+
+extern "C" int mmre_transd_ns_grad(int model, int norm_flag, float model_margin, int use_model_margin, float* d_ent,
+                                   float* d_ent_transfer, float* d_rel, float* d_rel_transfer, int64_t n_ent,
+                                   int64_t n_rel, int dim_e, int dim_r, const int64_t* d_h, const int64_t* d_t,
+                                   const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin,
+                                   float adv_temperature, float regul_rate, const float* d_score,
+                                   const float* d_grad_loss, float* d_grad_ent, float* d_grad_ent_transfer,
+                                   float* d_grad_rel, float* d_grad_rel_transfer, float* d_work, float lr,
+                                   void* stream) {
+  if (!td_train_model(model)) return MMRE_ERR_MODEL;
+  if (!d_ent || !d_ent_transfer || !d_rel || !d_rel_transfer || !d_h || !d_t || !d_r || !d_score || !d_grad_loss ||
+      !d_grad_ent || !d_grad_ent_transfer || !d_grad_rel || !d_grad_rel_transfer || !d_work)
+    return MMRE_ERR_ARG;
+  if (!td_train_shape(dim_e, dim_r, neg) || !th_train_sizes(batch, neg, n_ent, n_rel)) return MMRE_ERR_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  const TDArgs D = td_args(d_ent, d_ent_transfer, d_rel, d_rel_transfer, n_ent, n_rel, dim_e, dim_r, d_h, d_t, d_r,
+                           batch, neg, model_margin, use_model_margin, loss_margin, adv_temperature, regul_rate);
+  THArgs Ar = D.A;  // the relation tables' view, for k_th_rel: rows of dim_r
+  Ar.dim = dim_r;
+  const THWork W = td_carve(d_work, batch, neg, n_ent, n_rel, dim_e, dim_r);
+  const int64_t N = batch * (1 + neg);
+  // d/d(row) of regul_rate (the six means) / 6 is reg * row per gathered row: entity rows have dim_e
+  // elements, relation rows dim_r (k_tdt_records multiplies by the upstream gradient on the device)
+  const double unit = regul_rate != 0.0f ? (double)regul_rate * 2.0 / (6.0 * (double)N) : 0.0;
+  const float reg_ent = (float)(unit / (double)dim_e), reg_rel = (float)(unit / (double)dim_r);
+  hipLaunchKernelGGL(k_th_coef, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, D.A, d_score, d_grad_loss, W.coef,
+                     W.ecount, W.ecur);
+  MMRE_CHECK_LAUNCH();
+  int rc = td_dispatch(model, norm_flag, dim_e, [&](auto nc, auto l2, auto nm) {
+    hipLaunchKernelGGL((k_tdt_records<decltype(nc)::value, decltype(l2)::value, decltype(nm)::value>), dim3((unsigned)batch), dim3(256), 0, st, D,
+                       W.coef, d_grad_loss, reg_ent, reg_rel, W);
+  });
+  if (rc != MMRE_OK) return rc;
+  hipLaunchKernelGGL(k_th_scan, dim3(1), dim3(1024), 0, st, W.ecount, n_ent, W.eoff);
+  MMRE_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_th_fill, dim3((unsigned)((2 * N + 255) / 256)), dim3(256), 0, st, W, 2 * N);
+  MMRE_CHECK_LAUNCH();
+  const int64_t ent_blocks = (n_ent + 3) / 4, rel_blocks = (n_rel * W.n_seg + 3) / 4;
+  if (ent_blocks + rel_blocks > INT32_MAX) return MMRE_ERR_SHAPE;
+  rc = with_nc<8>(nc_for_dim(dim_e, 8), [&](auto nc) {
+    hipLaunchKernelGGL((k_tdt_owner<decltype(nc)::value>), dim3((unsigned)(ent_blocks + rel_blocks)), dim3(256), 0, st, D, W,
+                       ent_blocks, d_ent, d_ent_transfer, lr, d_grad_ent, d_grad_ent_transfer);
+  });
+  if (rc != MMRE_OK) return rc;
+  return with_nc<8>(nc_for_dim(dim_r, 8), [&](auto nc) {
+    hipLaunchKernelGGL((k_th_rel<decltype(nc)::value>), dim3((unsigned)((n_rel + 3) / 4)), dim3(256), 0, st, Ar, W, d_rel,
+                       d_rel_transfer, lr, d_grad_rel, d_grad_rel_transfer);
   });
 }

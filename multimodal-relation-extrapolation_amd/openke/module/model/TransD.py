@@ -3,14 +3,17 @@ parameter names and state-dict keys.
 
 forward(data) and regularization(data) are the reference's torch ops (differentiable);
 predict(data) and the Tester's evaluations run on libmmre_hip.so (mmre.transd: TransH's fused sweep
-behind TransD's prologue, and the row kernel). Training runs on autograd over forward():
-ns_spec() is None and there is no fused_ns hook, so NegativeSampling and Trainer take their
-generic branches."""
+behind TransD's prologue, and the row kernel). Training under NegativeSampling + MarginLoss runs on
+libmmre_hip.so as well: fused_ns_transd() hands the strategy the four tables and the static spec
+of mmre.transd_ns.fused_ns_loss (the fused loss, row-owner gradients, the in-pass SGD step).
+ns_spec() stays None -- the generic mmre.ns kernels and the one-call sampler-fused step have no
+TransD instance -- and every other loss or mode trains on autograd over forward()."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from mmre import transd as _transd
+from mmre import transd_ns as _transd_ns
 from mmre.link import ScoreSpec
 
 from .Model import Model
@@ -59,8 +62,22 @@ class TransD(Model):
         return self.ent_embeddings.weight, self.rel_embeddings.weight, None, None
 
     def ns_spec(self):
-        """No fused training step for TransD: the strategy scores through forward() and autograd."""
+        """No instance of the generic mmre.ns kernels for TransD (a triple has six rows): the
+        strategy asks fused_ns_transd() instead."""
         return None
+
+    def fused_ns_transd(self, neg):
+        """(spec, ent, ent_transfer, rel, rel_transfer) for mmre.transd_ns.fused_ns_loss when the
+        fused TransD training kernels serve this model with `neg` negatives per positive --
+        float32 contiguous device tables, dim_r <= dim_e <= 512, 1 <= neg <= 512 -- else None (the
+        strategy then scores through forward() and autograd)."""
+        tables = (self.ent_embeddings.weight, self.ent_transfer.weight, self.rel_embeddings.weight,
+                  self.rel_transfer.weight)
+        if any(not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() for x in tables):
+            return None
+        if neg < 1 or not _transd_ns.supported(self.dim_e, self.dim_r, neg):
+            return None
+        return (_transd_ns.TDSpec(self.p_norm, self.dim_e, self.dim_r, self.norm_flag, self._m()),) + tables
 
     def score_spec(self):
         # predict() = margin - forward = m - (m - s) when margin_flag, else s   (TransD.py:149-155)

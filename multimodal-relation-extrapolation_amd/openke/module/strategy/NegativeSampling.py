@@ -9,10 +9,12 @@ Trainer calls it for its mmre.optim.SGD or Adagrad) lets that backward also appl
 optimizer's plain step to the tables in the same pass (bit-identical parameters; step() then
 skips them). TransH has its own kernels (mmre.transh_ns.fused_ns_loss, through the model's
 fused_ns() hook): MarginLoss in 'normal' mode on float32 device tables at a supported shape;
-everything else about a TransH model takes the generic branch."""
+everything else about a TransH model takes the generic branch. TransD likewise
+(mmre.transd_ns.fused_ns_loss, through the model's fused_ns_transd() hook)."""
 import torch
 
 from mmre.ns import fused_ns_loss
+from mmre.transd_ns import fused_ns_loss as transd_fused_ns_loss
 from mmre.transh_ns import fused_ns_loss as transh_fused_ns_loss
 
 from ..loss.MarginLoss import MarginLoss
@@ -43,7 +45,15 @@ class NegativeSampling(Strategy):
     def _transh_fused(self, data, mode):
         """((spec, ent, rel, norm_vector), neg) when this batch takes the fused TransH path: a
         MarginLoss, 'normal' mode, a model with the fused_ns hook that offers the shape; else None."""
-        hook = getattr(self.model, "fused_ns", None)
+        return self._offer("fused_ns", data, mode)
+
+    def _transd_fused(self, data, mode):
+        """((spec, ent, ent_transfer, rel, rel_transfer), neg) when this batch takes the fused
+        TransD path: TransH's conditions with the model's fused_ns_transd hook; else None."""
+        return self._offer("fused_ns_transd", data, mode)
+
+    def _offer(self, hook_name, data, mode):
+        hook = getattr(self.model, hook_name, None)
         if hook is None or not isinstance(self.loss, MarginLoss) or mode != "normal":
             return None
         n = int(data["batch_h"].shape[0])
@@ -59,6 +69,7 @@ class NegativeSampling(Strategy):
         fused = isinstance(self.loss, (MarginLoss, SoftplusLoss, SigmoidLoss)) and mode == "normal"
         spec = self.model.ns_spec() if fused else None
         th = self._transh_fused(data, mode) if spec is None else None
+        td = self._transd_fused(data, mode) if spec is None and th is None else None
         if spec is not None:
             ent, rel, ent_im, rel_im = self.model._tables()
             dev = ent.device
@@ -80,6 +91,13 @@ class NegativeSampling(Strategy):
             h, t, r = (torch.as_tensor(data[k]).to(ent.device) for k in ("batch_h", "batch_t", "batch_r"))
             margin, adv = self.loss.fused_args()
             loss_res, _ = transh_fused_ns_loss(spec, ent, rel, nv, h, t, r, self.batch_size, neg, margin, adv,
+                                               self.regul_rate,
+                                               optimizer=self.fused_optimizer if self.l3_regul_rate == 0 else None)
+        elif td is not None:
+            (spec, *tables), neg = td
+            h, t, r = (torch.as_tensor(data[k]).to(tables[0].device) for k in ("batch_h", "batch_t", "batch_r"))
+            margin, adv = self.loss.fused_args()
+            loss_res, _ = transd_fused_ns_loss(spec, *tables, h, t, r, self.batch_size, neg, margin, adv,
                                                self.regul_rate,
                                                optimizer=self.fused_optimizer if self.l3_regul_rate == 0 else None)
         else:
