@@ -38,7 +38,10 @@ enum {
   MMRE_TRANSH_L2 = 6,
   /* TransD (mmre_transd_* only; every other entry point answers MMRE_ERR_MODEL for them) */
   MMRE_TRANSD_L1 = 7,
-  MMRE_TRANSD_L2 = 8
+  MMRE_TRANSD_L2 = 8,
+  /* TransR (mmre_transr_* only; every other entry point answers MMRE_ERR_MODEL for them) */
+  MMRE_TRANSR_L1 = 9,
+  MMRE_TRANSR_L2 = 10
 };
 enum { MMRE_HEAD_BATCH = 0, MMRE_TAIL_BATCH = 1 };
 /* Loss of the negative-sampling entry points (mmre_ns_opts_t) and the optimizer whose step the
@@ -474,6 +477,52 @@ int mmre_transd_ns_grad(int model, int norm_flag, float model_margin, int use_mo
                         const float* d_score, const float* d_grad_loss, float* d_grad_ent,
                         float* d_grad_ent_transfer, float* d_grad_rel, float* d_grad_rel_transfer, float* d_work,
                         float lr, void* stream);
+
+/* ====================================================================== *
+ *  TransR (OpenKE/openke/module/model/TransR.py): link prediction with    *
+ *  entities projected by the matrix of the query's relation, and predict  *
+ *  for arbitrary rows. Models MMRE_TRANSR_L1 / MMRE_TRANSR_L2 (p_norm     *
+ *  1 / 2). Tables: entities (E, dim_e), relations (R, dim_r) and          *
+ *  transfer_matrix (R, dim_e * dim_r), row r the row-major dim_e x dim_r  *
+ *  matrix M_r (TransR.py:57). 1 <= dim_e, dim_r <= 512 in either order.   *
+ *  csrc/transr.hip: the projection on f32 MFMA, a sweep over its planes.  *
+ * ====================================================================== */
+
+/* Bytes of d_work for mmre_transr_evaluate: one projected k-major plane of round_up(dim_r, 8) x
+ * e_pad floats for EVERY used relation (no chunking: 29 relations x 14,208 entities at
+ * dim_r = 200 are 330 MB, all 237 relations of FB15K237 2.8 GB), the relation vectors, the query
+ * planes and the listed scores. 0 for a non-positive size or a dim outside 1 .. 512. */
+int64_t mmre_transr_workspace(int64_t n_ent, int64_t n_rel, int dim_e, int dim_r, int64_t n_tiles, int64_t n_used,
+                              int64_t n_entries);
+
+/* One TransR link-prediction evaluation, enqueued on `stream`: mmre_transh_evaluate's contract
+ * (the Tester loop Tester.py:70-91 around TransR.predict TransR.py:97-103 = forward :65-85 with
+ * _transfer :55-63 and _calc :37-53) with TransR's tables. Queries, the plan of one-relation query
+ * tiles, filter groups, type masks, pred_kind (0 / 1), d_counts and d_truth as
+ * mmre_transh_evaluate takes and writes them. norm_flag: _calc's normalisation of the projected
+ * h and t and of r; without it the projection is used as it is.
+ * Checked in this order, all before any GPU call: the model (MMRE_ERR_MODEL), null tables and
+ * arrays and the sizes (MMRE_ERR_ARG), a dim outside 1 .. 512 (MMRE_ERR_SHAPE), work_bytes
+ * (MMRE_ERR_WORKSPACE). */
+int mmre_transr_evaluate(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                         const float* d_rel, const float* d_transfer_matrix, int64_t n_ent, int64_t n_rel,
+                         int dim_e, int dim_r, const int64_t* d_qh, const int64_t* d_qr, const int64_t* d_qt,
+                         const int8_t* d_qmode, int64_t n_query, const int32_t* d_perm, const int32_t* d_tiles,
+                         int64_t n_tiles, const int32_t* d_used, int64_t n_used, const int32_t* d_rel_slot,
+                         const int64_t* d_grp_qoff, const int32_t* d_grp_q, int64_t n_groups,
+                         const int64_t* d_filt_off, const int32_t* d_filt_ids, const int32_t* d_entry_q,
+                         int64_t n_entries, const uint32_t* d_type_head, const uint32_t* d_type_tail,
+                         int32_t* d_counts, float* d_truth, void* d_work, int64_t work_bytes, void* stream);
+
+/* TransR.predict / forward values of the rows (d_h[i], d_r[i], d_t[i]) (TransR.py:65-85, :97-103)
+ * from the raw tables, bit for bit what mmre_transr_evaluate scores for the same triple and mode:
+ * the projection is the MFMA's fmaf chain in ascending i, restated on the VALU. head_batch != 0:
+ * the grouping h + (r - t) of TransR.py:46-47, else (h + r) - t. pred_kind as apply_pred's 0 .. 4
+ * (4 = m - s, forward() of a model with a margin). A row with an id outside the tables gets NaN. */
+int mmre_transr_score_rows(int model, int norm_flag, int pred_kind, float margin, const float* d_ent,
+                           const float* d_rel, const float* d_transfer_matrix, int64_t n_ent, int64_t n_rel,
+                           int dim_e, int dim_r, const int64_t* d_h, const int64_t* d_r, const int64_t* d_t,
+                           int64_t n_rows, int head_batch, float* d_out, void* stream);
 
 /* ====================================================================== *
  *  Relation prediction: every test pair (h, t) against every relation.   *

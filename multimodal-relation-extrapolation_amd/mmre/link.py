@@ -21,7 +21,8 @@ from ._lib import call, ptr, stream_ptr
 
 MODEL_IDS = {"transe": 0, "transe_l2": 1, "distmult": 2, "complex": 3, "rotate": 4,
              "transh": 5, "transh_l2": 6,  # TransH: mmre.transh (TransHSweep, score_rows) only
-             "transd": 7, "transd_l2": 8}  # TransD: mmre.transd (TransDSweep, score_rows) only
+             "transd": 7, "transd_l2": 8,  # TransD: mmre.transd (TransDSweep, score_rows) only
+             "transr": 9, "transr_l2": 10}  # TransR: mmre.transr (TransRSweep, score_rows) only
 HEAD, TAIL = 0, 1
 METRIC_NAMES = ["mrr", "mr", "hit10", "hit3", "hit1"]
 GROUPS = ["filter", "raw", "filter_tc", "raw_tc"]
@@ -45,6 +46,8 @@ class ScoreSpec:
     ent_transfer: torch.Tensor | None = None   # (E, dim_e)
     rel_transfer: torch.Tensor | None = None   # (R, dim_r)
     dim_e: int = 0
+    # TransR: ent (E, dim_e), rel (R, dim_r), dim is dim_r; row r the row-major dim_e x dim_r matrix M_r
+    transfer_matrix: torch.Tensor | None = None   # (R, dim_e * dim_r)
 
 
 def rotate_phase_denom(margin: float, epsilon: float, dim: int) -> float:
@@ -208,6 +211,8 @@ class LinkSweep:
             raise ValueError("TransH sweeps one relation per query tile: use mmre.transh.TransHSweep")
         if spec.model in ("transd", "transd_l2"):
             raise ValueError("TransD sweeps one relation per query tile: use mmre.transd.TransDSweep")
+        if spec.model in ("transr", "transr_l2"):
+            raise ValueError("TransR sweeps one projected plane per query tile: use mmre.transr.TransRSweep")
         self.spec = spec
         self.model_id = MODEL_IDS[spec.model]
         dev = spec.ent.device
@@ -543,6 +548,11 @@ def evaluate_link_prediction(spec: ScoreSpec, test_h, test_r, test_t, index: Fil
         from .transh import plan_tiles
         res = TransDSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
                                     torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks, plan=plan_tiles(qr))
+    elif spec.model in ("transr", "transr_l2"):  # TransH's plan, TransR's projection and sweep
+        from .transh import plan_tiles
+        from .transr import TransRSweep
+        res = TransRSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
+                                    torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks, plan=plan_tiles(qr))
     else:
         res = LinkSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
                                   torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks)
@@ -616,6 +626,9 @@ def evaluate_relation_prediction(spec: ScoreSpec, test_h, test_r, test_t, index:
     if spec.model in ("transd", "transd_l2"):
         raise NotImplementedError("relation prediction for TransD: every candidate relation moves both "
                                   "entities by its own transfer vector; no TransD relation sweep is built yet")
+    if spec.model in ("transr", "transr_l2"):
+        raise NotImplementedError("relation prediction for TransR: every candidate relation projects both "
+                                  "entities by its own matrix; no TransR relation sweep is built yet")
     test_h, test_r, test_t = (np.asarray(x, np.int64) for x in (test_h, test_r, test_t))
     dev = spec.ent.device
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)

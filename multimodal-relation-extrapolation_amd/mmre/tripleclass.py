@@ -130,14 +130,17 @@ def evaluate_triple_classification(spec: ScoreSpec, test_h, test_r, test_t, trai
     """The whole task in one enqueued call (mmre_tc_evaluate): negatives of the test triples from
     thread 0's `seed_state`, both prediction arrays, and the best threshold (or the counts at a given
     one). Returns dict(accuracy, threshold, P, A, n_nan, n_pos, n_neg, neg_h, neg_t, pos_scores,
-    neg_scores (numpy), seed_state_after). A TransH or TransD spec composes the same result from
-    classification_negatives, its engine's score_rows (mmre.transh / mmre.transd) and
+    neg_scores (numpy), seed_state_after). A TransH, TransD or TransR spec composes the same result from
+    classification_negatives, its engine's score_rows (mmre.transh / mmre.transd / mmre.transr) and
     best_threshold / accuracy_at."""
     if spec.model in ("transh", "transh_l2"):
         from .transh import score_rows
         return _evaluate_rows(score_rows, spec, test_h, test_r, test_t, train_index, seed_state, threshold)
     if spec.model in ("transd", "transd_l2"):
         from .transd import score_rows
+        return _evaluate_rows(score_rows, spec, test_h, test_r, test_t, train_index, seed_state, threshold)
+    if spec.model in ("transr", "transr_l2"):
+        from .transr import score_rows
         return _evaluate_rows(score_rows, spec, test_h, test_r, test_t, train_index, seed_state, threshold)
     ent, rel, ent_im, rel_im = _tables(spec)
     dev = ent.device

@@ -5,5 +5,6 @@ from .RotatE import RotatE
 from .TransD import TransD
 from .TransE import TransE
 from .TransH import TransH
+from .TransR import TransR
 
-__all__ = ["Model", "TransE", "TransH", "TransD", "DistMult", "ComplEx", "RotatE"]
+__all__ = ["Model", "TransE", "TransH", "TransD", "TransR", "DistMult", "ComplEx", "RotatE"]
