@@ -478,6 +478,54 @@ int mmre_transd_ns_grad(int model, int norm_flag, float model_margin, int use_mo
                         float* d_grad_ent_transfer, float* d_grad_rel, float* d_grad_rel_transfer, float* d_work,
                         float lr, void* stream);
 
+/* ---- TransR negative-sampling training (csrc/transh_train.hip) ----
+ * The mmre_transh_ns_* contract for TransR.py:37-85: model(data) in 'normal' mode for the
+ * B (1 + K) rows of [pos | neg_1 | ... | neg_K], MarginLoss(loss_margin, adv_temperature) +
+ * regul_rate ((mean h^2 + mean t^2 + mean r^2 + mean M_r^2) / 4)^2 -- squared, as
+ * TransR.regularization is -- entity means over N dim_e elements, relation means over N dim_r,
+ * matrix means over N dim_e dim_r. Tables: d_ent (n_ent, dim_e), d_rel (n_rel, dim_r) and
+ * d_transfer_matrix (n_rel, dim_e * dim_r), row r the row-major dim_e x dim_r matrix M_r.
+ * model: MMRE_TRANSR_L1 / MMRE_TRANSR_L2 only (anything else: MMRE_ERR_MODEL; mmre_ns_*,
+ * mmre_transh_ns_* and mmre_transd_ns_* keep refusing these two). The arithmetic is the "TransR
+ * training chain" of DESIGN.md §3 -- the projection, the entity gradient and the matrix gradient
+ * are grouped GEMMs on v_mfma_f32_32x32x2_f32 -- so a score agrees with mmre_transr_score_rows to
+ * rounding, not bit for bit. Shapes: 1 <= dim_e, dim_r <= 512 in either order and 1 <= neg <= 512
+ * (mmre_transr_ns_supported asks first); n_ent, n_rel and batch as for TransH; else
+ * MMRE_ERR_SHAPE. Checks run before the first launch: model, null pointers (MMRE_ERR_ARG), shape.
+ * Every call only enqueues on `stream`: launch sizes are upper bounds from (batch, neg, n_rel), and
+ * nothing is read back. Ids are trusted to lie inside their tables. */
+
+/* 1 when the kernels exist for (model, dim_e, dim_r, neg), else 0. */
+int mmre_transr_ns_supported(int model, int dim_e, int dim_r, int64_t neg);
+
+/* Floats of d_work for both calls below; -1 for a shape they answer MMRE_ERR_SHAPE to. Monotone in
+ * every argument. For each of the B (1 + K) rows it reserves two projection slots -- each dim_r
+ * floats of projection, dim_r of its gradient and dim_e of entity record -- and dim_r floats of
+ * relation record; beside them 4 B (1 + K) / 1024 + 1 partial matrices of dim_e dim_r floats.
+ * The forward leaves its index, the projections and the regulariser's value there: the gradient
+ * call takes the same d_work, untouched in between. */
+int64_t mmre_transr_ns_workspace(int64_t batch, int64_t neg, int64_t n_ent, int64_t n_rel, int dim_e, int dim_r);
+
+/* d_score[B (1 + K)] <- forward values, d_loss[0] <- the loss, the same bits every run. */
+int mmre_transr_ns_forward(int model, int norm_flag, float model_margin, int use_model_margin,
+                           const float* d_ent, const float* d_rel, const float* d_transfer_matrix, int64_t n_ent,
+                           int64_t n_rel, int dim_e, int dim_r, const int64_t* d_h, const int64_t* d_t,
+                           const int64_t* d_r, int64_t batch, int64_t neg, float loss_margin,
+                           float adv_temperature, float regul_rate, float* d_score, float* d_loss, float* d_work,
+                           void* stream);
+
+/* The three gradient tables <- d(loss)/d(table) times d_grad_loss[0]: every row written (untouched
+ * rows exactly 0), no float atomics, the same bits every run. d_score and d_work: what the forward
+ * wrote for the same arguments. lr != 0: the owner of a touched row also applies p <- fma(-lr, g, p)
+ * in place to all three tables, bit-identical to backward() + SGD.step(); lr == 0: the tables are
+ * only read. */
+int mmre_transr_ns_grad(int model, int norm_flag, float model_margin, int use_model_margin, float* d_ent,
+                        float* d_rel, float* d_transfer_matrix, int64_t n_ent, int64_t n_rel, int dim_e, int dim_r,
+                        const int64_t* d_h, const int64_t* d_t, const int64_t* d_r, int64_t batch, int64_t neg,
+                        float loss_margin, float adv_temperature, float regul_rate, const float* d_score,
+                        const float* d_grad_loss, float* d_grad_ent, float* d_grad_rel,
+                        float* d_grad_transfer_matrix, float* d_work, float lr, void* stream);
+
 /* ====================================================================== *
  *  TransR (OpenKE/openke/module/model/TransR.py): link prediction with    *
  *  entities projected by the matrix of the query's relation, and predict  *

@@ -4,14 +4,16 @@ transfer_matrix, margin).
 
 forward(data) and regularization(data) are the reference's torch ops (differentiable);
 predict(data) and the Tester's evaluations run on libmmre_hip.so (mmre.transr: the relation
-projection on f32 MFMA, the fused sweep over its planes, and the row kernel). There is no fused
-training path yet: ns_spec() is None and the model has no fused-training hook, so the Trainer
-trains on autograd over forward()."""
+projection on f32 MFMA, the fused sweep over its planes, and the row kernel). Training runs on
+libmmre_hip.so as well: fused_ns_transr() hands the strategy the three tables and the static spec
+of mmre.transr_ns.fused_ns_loss (the fused loss, grouped f32-MFMA GEMMs for the projection and its
+two gradients, row-owner sums, the in-pass SGD step)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from mmre import transr as _transr
+from mmre import transr_ns as _transr_ns
 from mmre.link import ScoreSpec
 
 from .Model import Model
@@ -53,8 +55,21 @@ class TransR(Model):
         return self.ent_embeddings.weight, self.rel_embeddings.weight, None, None
 
     def ns_spec(self):
-        """No fused training for TransR yet: the strategy scores through forward() and autograd."""
+        """No instance of the generic mmre.ns kernels for TransR (a row carries a matrix): the
+        strategy asks fused_ns_transr() instead."""
         return None
+
+    def fused_ns_transr(self, neg):
+        """(spec, ent, rel, transfer_matrix) for mmre.transr_ns.fused_ns_loss when the fused TransR
+        training kernels serve this model with `neg` negatives per positive -- float32 contiguous
+        device tables, 1 <= dim_e, dim_r <= 512, 1 <= neg <= 512 -- else None (the strategy then
+        scores through forward() and autograd)."""
+        tables = (self.ent_embeddings.weight, self.rel_embeddings.weight, self.transfer_matrix.weight)
+        if any(not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() for x in tables):
+            return None
+        if neg < 1 or not _transr_ns.supported(self.dim_e, self.dim_r, neg):
+            return None
+        return (_transr_ns.TRSpec(self.p_norm, self.dim_e, self.dim_r, self.norm_flag, self._m()),) + tables
 
     def score_spec(self):
         # predict() = margin - forward = m - (m - s) when margin_flag, else s   (TransR.py:97-103)

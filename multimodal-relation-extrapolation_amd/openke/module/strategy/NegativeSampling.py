@@ -10,12 +10,14 @@ optimizer's plain step to the tables in the same pass (bit-identical parameters;
 skips them). TransH has its own kernels (mmre.transh_ns.fused_ns_loss, through the model's
 fused_ns() hook): MarginLoss in 'normal' mode on float32 device tables at a supported shape;
 everything else about a TransH model takes the generic branch. TransD likewise
-(mmre.transd_ns.fused_ns_loss, through the model's fused_ns_transd() hook)."""
+(mmre.transd_ns.fused_ns_loss, through the model's fused_ns_transd() hook), and TransR
+(mmre.transr_ns.fused_ns_loss, through fused_ns_transr())."""
 import torch
 
 from mmre.ns import fused_ns_loss
 from mmre.transd_ns import fused_ns_loss as transd_fused_ns_loss
 from mmre.transh_ns import fused_ns_loss as transh_fused_ns_loss
+from mmre.transr_ns import fused_ns_loss as transr_fused_ns_loss
 
 from ..loss.MarginLoss import MarginLoss
 from ..loss.SigmoidLoss import SigmoidLoss
@@ -52,6 +54,11 @@ class NegativeSampling(Strategy):
         TransD path: TransH's conditions with the model's fused_ns_transd hook; else None."""
         return self._offer("fused_ns_transd", data, mode)
 
+    def _transr_fused(self, data, mode):
+        """((spec, ent, rel, transfer_matrix), neg) when this batch takes the fused TransR path:
+        TransH's conditions with the model's fused_ns_transr hook; else None."""
+        return self._offer("fused_ns_transr", data, mode)
+
     def _offer(self, hook_name, data, mode):
         hook = getattr(self.model, hook_name, None)
         if hook is None or not isinstance(self.loss, MarginLoss) or mode != "normal":
@@ -70,6 +77,7 @@ class NegativeSampling(Strategy):
         spec = self.model.ns_spec() if fused else None
         th = self._transh_fused(data, mode) if spec is None else None
         td = self._transd_fused(data, mode) if spec is None and th is None else None
+        tr = self._transr_fused(data, mode) if spec is None and th is None and td is None else None
         if spec is not None:
             ent, rel, ent_im, rel_im = self.model._tables()
             dev = ent.device
@@ -98,6 +106,13 @@ class NegativeSampling(Strategy):
             h, t, r = (torch.as_tensor(data[k]).to(tables[0].device) for k in ("batch_h", "batch_t", "batch_r"))
             margin, adv = self.loss.fused_args()
             loss_res, _ = transd_fused_ns_loss(spec, *tables, h, t, r, self.batch_size, neg, margin, adv,
+                                               self.regul_rate,
+                                               optimizer=self.fused_optimizer if self.l3_regul_rate == 0 else None)
+        elif tr is not None:
+            (spec, *tables), neg = tr
+            h, t, r = (torch.as_tensor(data[k]).to(tables[0].device) for k in ("batch_h", "batch_t", "batch_r"))
+            margin, adv = self.loss.fused_args()
+            loss_res, _ = transr_fused_ns_loss(spec, *tables, h, t, r, self.batch_size, neg, margin, adv,
                                                self.regul_rate,
                                                optimizer=self.fused_optimizer if self.l3_regul_rate == 0 else None)
         else:
