@@ -132,6 +132,19 @@ def spec_of(c, p_norm, norm_flag, margin):
 # (20, 20): kp padded to 24 rows; (72, 72): nine stages; (28, 20): the narrowed planes, s over 28
 @pytest.mark.parametrize("dims", [(20, 20), (72, 72), (28, 20)])
 def test_sweep_equals_the_restatement(dims, p_norm, norm_flag, margin):
+    check_sweep(dims, p_norm, norm_flag, margin)
+
+
+# (1, 1): one value per row; (8, 8): one K stage, kp = dim_r; (9, 8): s over one value more than the
+# planes hold; (512, 1): the longest s chain over the narrowest planes; (512, 512): 64 stages (the
+# shape check bounds neither width, only dim_e >= dim_r)
+@pytest.mark.parametrize("p_norm,norm_flag", [(1, True), (2, False)])
+@pytest.mark.parametrize("dims", [(1, 1), (8, 8), (9, 8), (512, 1), (512, 512)])
+def test_sweep_equals_the_restatement_at_other_widths(dims, p_norm, norm_flag):
+    check_sweep(dims, p_norm, norm_flag, None)
+
+
+def check_sweep(dims, p_norm, norm_flag, margin):
     from mmre.transd import TransDSweep, plan_tiles, score_rows
     c = case(dims)
     d = c["dev"]

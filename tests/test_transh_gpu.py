@@ -104,6 +104,18 @@ def spec_of(c, p_norm, norm_flag, margin):
 @pytest.mark.parametrize("p_norm", [1, 2])
 @pytest.mark.parametrize("dim", [20, 72])   # kp padded at 20 (24 rows); 72: nine stages
 def test_sweep_equals_the_restatement(dim, p_norm, norm_flag, margin):
+    check_sweep(dim, p_norm, norm_flag, margin)
+
+
+# 1: one value per row; 8: one K stage, kp = dim; 9: the second stage holds one row and seven of
+# padding; 512: mmre_transh_evaluate's shape check has no upper bound -- 64 stages
+@pytest.mark.parametrize("p_norm,norm_flag", [(1, True), (2, False)])
+@pytest.mark.parametrize("dim", [1, 8, 9, 512])
+def test_sweep_equals_the_restatement_at_other_widths(dim, p_norm, norm_flag):
+    check_sweep(dim, p_norm, norm_flag, None)
+
+
+def check_sweep(dim, p_norm, norm_flag, margin):
     from mmre.transh import TransHSweep, plan_tiles, score_rows
     c = case(dim)
     d = c["dev"]

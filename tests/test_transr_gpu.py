@@ -35,7 +35,7 @@ def make_case(dim_e, dim_r):
     tm[R_ZERO_M] = 0.0                                               # every entity projects to 0: all tie
     tm[R_IDENT] = 0.0
     tm[R_IDENT][np.arange(min(dim_e, dim_r)), np.arange(min(dim_e, dim_r))] = 1.0   # TransR.py:24-27
-    tm[R_ZCOL][:, ZCOL] = 0.0                                        # m_3 = 0 for every entity
+    tm[R_ZCOL][:, min(ZCOL, dim_r - 1)] = 0.0                        # m_3 = 0 for every entity (the last column below dim_r 4)
     rel[R_ZERO_REL] = 0.0
     ent[ZERO_E] = 0.0                                                # m = 0: the 1e-12 clamp
     tm = tm.reshape(N_REL, dim_e * dim_r)
@@ -74,7 +74,58 @@ def make_case(dim_e, dim_r):
     kh, kr, kt = (np.concatenate([a, b]) for a, b in ((kh, qh), (kr, qr), (kt, qt)))
     th = [np.sort(rng.choice(E, int(rng.integers(20, E)), replace=False)) for _ in range(N_REL)]
     tt = [np.sort(rng.choice(E, int(rng.integers(20, E)), replace=False)) for _ in range(N_REL)]
-    return dict(ent=ent, rel=rel, tm=tm, qh=qh, qr=qr, qt=qt, qm=qm, known=(kh, kr, kt), types=(th, tt), src=src)
+    return dict(ent=ent, rel=rel, tm=tm, qh=qh, qr=qr, qt=qt, qm=qm, known=(kh, kr, kt), types=(th, tt), src=src,
+                E=E, n_rel=N_REL, per_rel=PER_REL, r_zero_m=R_ZERO_M, tiles_per_rel=[0, 1, 1, 1, 1, 1, 2, 3])
+
+
+# The reduced case of the widths whose float32-fma restatement of the full case takes ten seconds and
+# more (dim_e * dim_r > 40,000): three relations -- the zero matrix, the identity, a random one --
+# over two entity tiles, the second one partial, with the zero entity, the copied entity and the
+# last entity as truth and as anchor.
+E_RED, PER_REL_RED = 200, [20, 60, 120]
+REDUCED_ABOVE = 40_000
+
+
+def make_reduced_case(dim_e, dim_r):
+    f = np.float32
+    n_rel, last = len(PER_REL_RED), E_RED - 1
+    rng = np.random.default_rng(900 + 7 * dim_e + dim_r)
+    ent = rng.uniform(-0.5, 0.5, (E_RED, dim_e)).astype(f)
+    rel = rng.uniform(-0.5, 0.5, (n_rel, dim_r)).astype(f)
+    tm = rng.uniform(-0.5, 0.5, (n_rel, dim_e, dim_r)).astype(f)
+    tm[0] = 0.0                                                      # every entity projects to 0: all tie
+    tm[1] = 0.0
+    tm[1][np.arange(min(dim_e, dim_r)), np.arange(min(dim_e, dim_r))] = 1.0   # TransR.py:24-27
+    ent[ZERO_E] = 0.0                                                # m = 0: the 1e-12 clamp
+    ent[COPY] = ent[SRC]
+    tm = tm.reshape(n_rel, dim_e * dim_r)
+    qr = np.repeat(np.arange(n_rel), PER_REL_RED)
+    n = len(qr)
+    qh, qt = rng.integers(0, E_RED, n), rng.integers(0, E_RED, n)
+    qm = rng.integers(0, 2, n).astype(np.int8)
+    for r in range(n_rel):                                           # the special rows under every relation
+        i = int(np.nonzero(qr == r)[0][0])
+        qh[i], qm[i] = ZERO_E, 0                                     # the zero entity as truth
+        qt[i + 1], qm[i + 1] = ZERO_E, 0                             # ... and as the anchor
+        qt[i + 2], qm[i + 2] = last, 1                               # truth 199 (tail side)
+        qh[i + 3], qm[i + 3] = last, 0                               # truth 199 (head side)
+        qt[i + 4], qm[i + 4] = last, 0                               # 199 as the anchor (head batch)
+        qh[i + 5], qm[i + 5] = last, 1                               # 199 as the anchor (tail batch)
+        qt[i + 6], qm[i + 6] = SRC, 1                                # COPY ties with this truth
+        qt[i + 7], qm[i + 7] = COPY, 1
+    qr = qr.astype(np.int64)
+    order = rng.permutation(n)
+    qh, qr, qt, qm = qh[order], qr[order], qt[order], qm[order]
+    kn = 800
+    kh, kr, kt = rng.integers(0, E_RED, kn), rng.integers(0, n_rel, kn), rng.integers(0, E_RED, kn)
+    pick = rng.integers(0, n, kn // 4)
+    kh[:kn // 8], kr[:kn // 8] = qh[pick[:kn // 8]], qr[pick[:kn // 8]]
+    kr[kn // 8:kn // 4], kt[kn // 8:kn // 4] = qr[pick[kn // 8:]], qt[pick[kn // 8:]]
+    kh, kr, kt = (np.concatenate([a, b]) for a, b in ((kh, qh), (kr, qr), (kt, qt)))
+    th = [np.sort(rng.choice(E_RED, int(rng.integers(20, E_RED)), replace=False)) for _ in range(n_rel)]
+    tt = [np.sort(rng.choice(E_RED, int(rng.integers(20, E_RED)), replace=False)) for _ in range(n_rel)]
+    return dict(ent=ent, rel=rel, tm=tm, qh=qh, qr=qr, qt=qt, qm=qm, known=(kh, kr, kt), types=(th, tt), src=SRC,
+                E=E_RED, n_rel=n_rel, per_rel=PER_REL_RED, r_zero_m=0, tiles_per_rel=[1, 1, 1])
 
 
 _cases = {}
@@ -84,8 +135,8 @@ def case(dims):
     """The synthetic case at `dims` with its filter index and device copies, built once."""
     if dims not in _cases:
         from mmre.link import FilterIndex
-        c = make_case(*dims)
-        idx = FilterIndex(*c["known"], E, N_REL, *c["types"])
+        c = (make_reduced_case if dims[0] * dims[1] > REDUCED_ABOVE else make_case)(*dims)
+        idx = FilterIndex(*c["known"], c["E"], c["n_rel"], *c["types"])
         to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
         c["index"] = idx
         c["groups"] = tuple(to(a) for a in idx.groups(c["qh"], c["qr"], c["qt"], c["qm"]))
@@ -93,7 +144,7 @@ def case(dims):
         c["dev"] = {k: to(c[k]) for k in ("ent", "rel", "tm", "qh", "qr", "qt", "qm")}
         off, ids = idx.filters(c["qh"], c["qr"], c["qt"], c["qm"])
         c["lists"] = [ids[off[i]:off[i + 1]] for i in range(len(c["qh"]))]
-        allowed = np.zeros((len(c["qh"]), E), bool)
+        allowed = np.zeros((len(c["qh"]), c["E"]), bool)
         for i, (r, m) in enumerate(zip(c["qr"], c["qm"])):
             allowed[i, c["types"][0 if m == 0 else 1][r]] = True
         c["allowed"] = allowed
@@ -129,16 +180,35 @@ PARAMS += [((200, 200), 1, True, m) for m in (None, 5.0)]
 
 @pytest.mark.parametrize("dims,p_norm,norm_flag,margin", PARAMS)
 def test_sweep_equals_the_restatement(dims, p_norm, norm_flag, margin):
+    check_sweep(dims, p_norm, norm_flag, margin)
+
+
+# k_tr_project off the widths above. (1, 1): one value; (16, 7) / (17, 7): one K block and one row
+# into the second; (7, 1): a single column; (40, 128) / (40, 129): a full column chunk and one column
+# into the next; (256, 256): the last full second chunk; (512, 7) and (7, 512): 32 K blocks under
+# one partly filled tile, and four chunks over half a K block; (512, 512): the widest the shape
+# check accepts, and the largest dynamic LDS request of the library. Above REDUCED_ABOVE the reduced case.
+OTHER_DIMS = [(1, 1), (16, 7), (17, 7), (7, 1), (40, 128), (40, 129), (256, 256), (512, 7), (7, 512), (512, 512)]
+
+
+@pytest.mark.parametrize("p_norm,norm_flag", [(1, True), (2, False)])
+@pytest.mark.parametrize("dims", OTHER_DIMS)
+def test_sweep_equals_the_restatement_at_other_widths(dims, p_norm, norm_flag):
+    check_sweep(dims, p_norm, norm_flag, None)
+
+
+def check_sweep(dims, p_norm, norm_flag, margin):
     from mmre.transr import TransRSweep, plan_tiles, score_rows
     c = case(dims)
     d = c["dev"]
     Q = len(c["qh"])
+    E, N_REL = c["E"], c["n_rel"]
     want_s, want = restated(c, p_norm, norm_flag, margin)
     spec = spec_of(c, p_norm, norm_flag, margin)
     sw = TransRSweep(spec)
     assert (sw.dim_e, sw.dim_r) == dims
     plan = plan_tiles(c["qr"])
-    assert sorted(np.bincount(plan["tiles"][:, 0], minlength=N_REL).tolist()) == [0, 1, 1, 1, 1, 1, 2, 3]
+    assert sorted(np.bincount(plan["tiles"][:, 0], minlength=N_REL).tolist()) == c["tiles_per_rel"]
     res = sw.run(d["qh"], d["qr"], d["qt"], d["qm"], filt=c["groups"], type_masks=c["masks"], plan=plan)
     got = res["counts"].cpu().numpy()
     truth = res["truth"].cpu().numpy()
@@ -176,8 +246,8 @@ def test_sweep_equals_the_restatement(dims, p_norm, norm_flag, margin):
     assert got_s[qi, COPY] == got_s[qi, c["src"]]
     assert np.array_equal(got_s[:, COPY], got_s[:, c["src"]])
     # under the all-zero matrix every candidate ties with the truth: every count is 0
-    zm = c["qr"] == R_ZERO_M
-    assert zm.sum() == PER_REL[R_ZERO_M] and not got[:, zm].any()
+    zm = c["qr"] == c["r_zero_m"]
+    assert zm.sum() == c["per_rel"][c["r_zero_m"]] and not got[:, zm].any()
     assert np.all(got_s[zm] == got_s[zm][:, :1])
 
 
