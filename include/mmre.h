@@ -41,7 +41,9 @@ enum {
   MMRE_TRANSD_L2 = 8,
   /* TransR (mmre_transr_* only; every other entry point answers MMRE_ERR_MODEL for them) */
   MMRE_TRANSR_L1 = 9,
-  MMRE_TRANSR_L2 = 10
+  MMRE_TRANSR_L2 = 10,
+  /* RESCAL (mmre_rescal_* only; every other entry point answers MMRE_ERR_MODEL for it) */
+  MMRE_RESCAL = 11
 };
 enum { MMRE_HEAD_BATCH = 0, MMRE_TAIL_BATCH = 1 };
 /* Loss of the negative-sampling entry points (mmre_ns_opts_t) and the optimizer whose step the
@@ -571,6 +573,52 @@ int mmre_transr_score_rows(int model, int norm_flag, int pred_kind, float margin
                            const float* d_rel, const float* d_transfer_matrix, int64_t n_ent, int64_t n_rel,
                            int dim_e, int dim_r, const int64_t* d_h, const int64_t* d_r, const int64_t* d_t,
                            int64_t n_rows, int head_batch, float* d_out, void* stream);
+
+/* ====================================================================== *
+ *  RESCAL (OpenKE/openke/module/model/RESCAL.py): link prediction with    *
+ *  the bilinear score s = sum_i h_i (M_r t)_i, and predict for arbitrary  *
+ *  rows. Model MMRE_RESCAL. Tables: entities (E, dim) and rel_matrices    *
+ *  (R, dim * dim), row r the row-major matrix M_r[i][j] = row[i * dim +   *
+ *  j] (RESCAL.py:18-19). 1 <= dim <= 512. No margin, norm_flag or p_norm. *
+ *  csrc/rescal.hip: the planes P_r = E . M_r^T on f32 MFMA, an f32 MFMA   *
+ *  sweep whose entity operand is picked per query tile.                   *
+ * ====================================================================== */
+
+/* Bytes of d_work for mmre_rescal_evaluate: one k-major plane of round_up(dim, 16) x e_pad floats
+ * for EVERY used relation (no chunking), the k-major copy of the entity table (one more such
+ * plane), the query planes and the listed scores. FB15K237 (E = 14,541, e_pad = 14,592; all 237
+ * relations used) at dim = 50 (kp = 64): 238 x 64 x 14,592 x 4 = 889 MB of planes; 29 used
+ * relations: 112 MB. 0 for a non-positive size or a dim outside 1 .. 512. */
+int64_t mmre_rescal_workspace(int64_t n_ent, int64_t n_rel, int dim, int64_t n_tiles, int64_t n_used,
+                              int64_t n_entries);
+
+/* One RESCAL link-prediction evaluation, enqueued on `stream`: mmre_transr_evaluate's contract
+ * (the Tester loop Tester.py:70-91 around RESCAL.predict RESCAL.py:44-46 = -forward :24-32)
+ * without norm_flag, margin, the relation vectors and the second dim. The plan differs in one
+ * thing: a query tile holds the queries of one KEY 2 * relation + side (side = the queries'
+ * qmode: MMRE_HEAD_BATCH 0, MMRE_TAIL_BATCH 1), and d_tiles[3 t] is that key; d_used / d_rel_slot
+ * stay per relation. pred_kind 0 (predict = s: the Tester ranks ascending on +s, as the reference
+ * does) or 2 (-s). Filter groups, type masks, d_counts and d_truth as mmre_transh_evaluate takes
+ * and writes them.
+ * Checked in this order, all before any GPU call: the model (MMRE_ERR_MODEL), null tables and
+ * arrays and the sizes (MMRE_ERR_ARG), a dim outside 1 .. 512 (MMRE_ERR_SHAPE), work_bytes
+ * (MMRE_ERR_WORKSPACE). */
+int mmre_rescal_evaluate(int model, int pred_kind, const float* d_ent, const float* d_rel_matrices, int64_t n_ent,
+                         int64_t n_rel, int dim, const int64_t* d_qh, const int64_t* d_qr, const int64_t* d_qt,
+                         const int8_t* d_qmode, int64_t n_query, const int32_t* d_perm, const int32_t* d_tiles,
+                         int64_t n_tiles, const int32_t* d_used, int64_t n_used, const int32_t* d_rel_slot,
+                         const int64_t* d_grp_qoff, const int32_t* d_grp_q, int64_t n_groups,
+                         const int64_t* d_filt_off, const int32_t* d_filt_ids, const int32_t* d_entry_q,
+                         int64_t n_entries, const uint32_t* d_type_head, const uint32_t* d_type_tail,
+                         int32_t* d_counts, float* d_truth, void* d_work, int64_t work_bytes, void* stream);
+
+/* RESCAL.predict / forward values of the rows (d_h[i], d_r[i], d_t[i]) from the raw tables, bit
+ * for bit what mmre_rescal_evaluate scores for the same triple on either side: both chains are the
+ * MFMA's fmaf chains, restated on the VALU. pred_kind as apply_pred's 0 .. 4 with margin 0
+ * (0 = s, predict; 2 = -s, forward). A row with an id outside the tables gets NaN. */
+int mmre_rescal_score_rows(int model, int pred_kind, const float* d_ent, const float* d_rel_matrices, int64_t n_ent,
+                           int64_t n_rel, int dim, const int64_t* d_h, const int64_t* d_r, const int64_t* d_t,
+                           int64_t n_rows, float* d_out, void* stream);
 
 /* ====================================================================== *
  *  Relation prediction: every test pair (h, t) against every relation.   *

@@ -82,6 +82,10 @@ SIGNATURES = {
     "mmre_transr_evaluate": (I32, [I32, I32, I32, F32, P, P, P, I64, I64, I32, I32, P, P, P, P, I64, P, P, I64, P,
                                    I64, P, P, P, I64, P, P, P, I64, P, P, P, P, P, I64, P]),
     "mmre_transr_score_rows": (I32, [I32, I32, I32, F32, P, P, P, I64, I64, I32, I32, P, P, P, I64, I32, P, P]),
+    "mmre_rescal_workspace": (I64, [I64, I64, I32, I64, I64, I64]),
+    "mmre_rescal_evaluate": (I32, [I32, I32, P, P, I64, I64, I32, P, P, P, P, I64, P, P, I64, P, I64, P, P, P, I64, P,
+                                   P, P, I64, P, P, P, P, P, I64, P]),
+    "mmre_rescal_score_rows": (I32, [I32, I32, P, P, I64, I64, I32, P, P, P, I64, P, P]),
     "mmre_transr_ns_supported": (I32, [I32, I32, I32, I64]),
     "mmre_transr_ns_workspace": (I64, [I64, I64, I64, I64, I32, I32]),
     "mmre_transr_ns_forward": (I32, [I32, I32, F32, I32, P, P, P, I64, I64, I32, I32, P, P, P, I64, I64, F32, F32,

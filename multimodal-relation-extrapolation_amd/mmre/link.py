@@ -22,7 +22,8 @@ from ._lib import call, ptr, stream_ptr
 MODEL_IDS = {"transe": 0, "transe_l2": 1, "distmult": 2, "complex": 3, "rotate": 4,
              "transh": 5, "transh_l2": 6,  # TransH: mmre.transh (TransHSweep, score_rows) only
              "transd": 7, "transd_l2": 8,  # TransD: mmre.transd (TransDSweep, score_rows) only
-             "transr": 9, "transr_l2": 10}  # TransR: mmre.transr (TransRSweep, score_rows) only
+             "transr": 9, "transr_l2": 10,  # TransR: mmre.transr (TransRSweep, score_rows) only
+             "rescal": 11}  # RESCAL: mmre.rescal (RescalSweep, score_rows) only
 HEAD, TAIL = 0, 1
 METRIC_NAMES = ["mrr", "mr", "hit10", "hit3", "hit1"]
 GROUPS = ["filter", "raw", "filter_tc", "raw_tc"]
@@ -33,7 +34,7 @@ class ScoreSpec:
     """How a model scores: which kernel, which tables, and predict's transform."""
     model: str                      # key of MODEL_IDS
     ent: torch.Tensor               # (E, d) or RotatE (E, 2d); ComplEx: real part
-    rel: torch.Tensor               # (R, d); ComplEx: real part
+    rel: torch.Tensor | None        # (R, d); ComplEx: real part; RESCAL: None (rel_matrices is its table)
     dim: int
     ent_im: torch.Tensor | None = None
     rel_im: torch.Tensor | None = None
@@ -46,6 +47,9 @@ class ScoreSpec:
     ent_transfer: torch.Tensor | None = None   # (E, dim_e)
     rel_transfer: torch.Tensor | None = None   # (R, dim_r)
     dim_e: int = 0
+    # RESCAL: ent (E, d), dim is d, row r the row-major d x d matrix M_r; there is no relation vector
+    # table, and rel is None (what reads the relation count reads rel_matrices' rows)
+    rel_matrices: torch.Tensor | None = None   # (R, d * d)
     # TransR: ent (E, dim_e), rel (R, dim_r), dim is dim_r; row r the row-major dim_e x dim_r matrix M_r
     transfer_matrix: torch.Tensor | None = None   # (R, dim_e * dim_r)
 
@@ -213,6 +217,8 @@ class LinkSweep:
             raise ValueError("TransD sweeps one relation per query tile: use mmre.transd.TransDSweep")
         if spec.model in ("transr", "transr_l2"):
             raise ValueError("TransR sweeps one projected plane per query tile: use mmre.transr.TransRSweep")
+        if spec.model == "rescal":
+            raise ValueError("RESCAL sweeps one (relation, side) per query tile: use mmre.rescal.RescalSweep")
         self.spec = spec
         self.model_id = MODEL_IDS[spec.model]
         dev = spec.ent.device
@@ -553,6 +559,10 @@ def evaluate_link_prediction(spec: ScoreSpec, test_h, test_r, test_t, index: Fil
         from .transr import TransRSweep
         res = TransRSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
                                     torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks, plan=plan_tiles(qr))
+    elif spec.model == "rescal":  # TransH's plan over (relation, side) keys, RESCAL's planes and sweep
+        from .rescal import RescalSweep, plan_keys
+        res = RescalSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
+                                    torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks, plan=plan_keys(qr, qm))
     else:
         res = LinkSweep(spec).run(*(torch.from_numpy(x).to(dev) for x in (qh, qr, qt)),
                                   torch.from_numpy(qm).to(dev), filt=filt, type_masks=masks)
@@ -629,6 +639,9 @@ def evaluate_relation_prediction(spec: ScoreSpec, test_h, test_r, test_t, index:
     if spec.model in ("transr", "transr_l2"):
         raise NotImplementedError("relation prediction for TransR: every candidate relation projects both "
                                   "entities by its own matrix; no TransR relation sweep is built yet")
+    if spec.model == "rescal":
+        raise NotImplementedError("relation prediction for RESCAL: every candidate relation multiplies the "
+                                  "pair by its own matrix; no RESCAL relation sweep is built yet")
     test_h, test_r, test_t = (np.asarray(x, np.int64) for x in (test_h, test_r, test_t))
     dev = spec.ent.device
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)

@@ -142,6 +142,9 @@ def evaluate_triple_classification(spec: ScoreSpec, test_h, test_r, test_t, trai
     if spec.model in ("transr", "transr_l2"):
         from .transr import score_rows
         return _evaluate_rows(score_rows, spec, test_h, test_r, test_t, train_index, seed_state, threshold)
+    if spec.model == "rescal":
+        from .rescal import score_rows
+        return _evaluate_rows(score_rows, spec, test_h, test_r, test_t, train_index, seed_state, threshold)
     ent, rel, ent_im, rel_im = _tables(spec)
     dev = ent.device
     d = device_index(train_index, dev)
